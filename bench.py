@@ -1,9 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- offline path-embedding build throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs of the last step
+written with --dump-outputs DIR, the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds
+of one timed step, and the roofline of the emit kernel from the timed steps' own events).  Everything else -- the drawn-pool
+and plain-allocation comparisons, the phase step, the closed-form sanity check and every leg listed below -- runs only
+with --full (the --no-* options then switch single legs off).
+
+--dump-outputs DIR: what a caller of the timed path receives from its last step, as float64 .npy files -- `ids.npy` (path
+ids, one row per path) and `pde.npy` (path embeddings) on a fixed, seeded sample of the rows (`rows.npy`: their indices;
+at most 2^18 rows per rank, under 64 MB in all), `paths.npy` (this rank's and all ranks' path counts).  N > 1: every rank
+writes its own slab, the files suffixed `_rank<r>`.  The inputs depend on the arguments only, so two builds can be compared
+output for output.
 
 Launch rule: one process per GPU.  Under a launcher (WORLD_SIZE set) this file is one rank.  Started plainly with
 --gpus N > 1 it starts N rank processes itself (`launch_ranks`: children of `python -m torch.distributed.run`, before this
@@ -17,7 +29,7 @@ when the graph is distributed -- graph structure, like the CSR itself), the proc
 N>1 partitions the SAME graph across the ranks (configs[3]), so scaling is "strong".
 value = paths of all ranks / max-over-ranks step time.
 
-The JSON line also carries
+The JSON line also carries (all but the first with --full only)
   roofline     -- the dominant kernel (k_fill_ranked): algorithmic bytes (92 B/path at l=2,e=2) / its
                   launch duration, timed live with events on the launch stream; `step_frac` = the same bytes over
                   the whole step; `traffic` = HBM bytes per launch from this round's PMC passes (profiles/);
@@ -354,6 +366,32 @@ def guarded(out, key, fn, *a, **kw):
         leg_failed(out, key, ex)
 
 
+DUMP_SEED = 20240607  # fixes the sampled rows of --dump-outputs
+DUMP_BUDGET = 60 << 20  # bytes of all files together, all ranks' included (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, torch, device, pool, total, global_total, suffix="", ranks=1):
+    """--dump-outputs: the rows the last timed step wrote into the output pool, as float64 .npy files.  Up to 2^18 rows (fewer when
+    the rows are wide, or when `ranks` processes share DUMP_BUDGET), one drawn at random from each of that many equal strata of
+    [0, total), so the sample depends only on the path count; every row when there are fewer."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    width = pool.L + pool.D + 1  # ids + pde + the row index, float64 each
+    k = min(total, 1 << 18, max(1, DUMP_BUDGET // ranks // (8 * width)))
+    if k == total:
+        rows = np.arange(total, dtype=np.int64)
+    else:
+        s = np.arange(k + 1, dtype=np.int64) * total // k  # stratum boundaries
+        rows = s[:-1] + (np.random.default_rng(DUMP_SEED).random(k) * (s[1:] - s[:-1])).astype(np.int64)
+    idx = torch.from_numpy(rows).to(device)
+    ids = pool.ids_tensor(device)[idx].to(torch.int64) & 0xFFFFFFFF  # (uint32 ids behind an int32 view)
+    np.save(os.path.join(out_dir, f"ids{suffix}.npy"), ids.to(torch.float64).cpu().numpy())
+    if pool.D:
+        np.save(os.path.join(out_dir, f"pde{suffix}.npy"), pool.pde_tensor(device)[idx].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, f"rows{suffix}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, f"paths{suffix}.npy"), np.array([total, global_total], np.float64))
+
+
 def e2e_leg(g, sn, p, index, label, allow_large=False):
     """Wall-clock of `gnnpe_main -m offline` on text inputs (load + emit + render + file writes [+ index.dat])."""
     free = shutil.disk_usage(tempfile.gettempdir()).free
@@ -436,7 +474,15 @@ def main():
                          "reported that as the headline); reported as roofline.drawn_pool, never as `value`; 0 = skip")
     ap.add_argument("--equal-paths", action="store_true",
                     help="N>1 slab planning: equal path counts instead of the fitted step-cost model (dist.STEP_COST_WEIGHTS)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: drawn-pool / plain-allocation comparisons, the phase step, the "
+                         "closed-form sanity check, the index / online-filter / config-2 / GNN-PGE / config-5 / end-to-end legs and "
+                         "the CPU baselines (each switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as float64 .npy files into DIR (a fixed, seeded sample of the rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N rank processes ourselves (children, never an exec) BEFORE anything
@@ -536,7 +582,9 @@ def main():
     out_ids, out_pde = pool.ids, (pool.pde if D_out else None)
     cap_rows = pool.rows_cap
     ids_view = pool.ids_tensor(device)
-    # both emit shapes timed into the kept buffer (the pool has done this already; again here for the numbers)
+    # the emit shapes' times into the kept buffer (emit_class, calibration_ms).  Where the pool calibrated this buffer (l = 2, buffer
+    # >= 512 MB: the headline) the library answers from that measurement without a launch; where it did not (ids only, 2^24 to about
+    # 4.5e7 paths) this call is the calibration, and it picks the shape the timed steps use -- so it stays in the plain run
     shapes = eng.emit_calibrate_device(out_ids, out_pde, rows_cap=cap_rows) if (args.fill_variant == 4 and total > 0) else None
 
     fill_ms = []
@@ -592,11 +640,13 @@ def main():
         sb.base = 0
     else:
         assert sb.local_total == total
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, device, pool, total, sb.global_total, "" if world == 1 else f"_rank{rank}", world)
 
     # for comparison with rounds 2-3, whose headline was the best of 12 (5) candidate allocations: the same steps into the
     # kept one of `--compare-pool` candidates (transient memory: that many outputs; 0 = skip)
     drawn = None
-    if not multi and args.placements == 1 and args.compare_pool > 1 and args.fill_variant == 4 and total >= (1 << 24):
+    if args.full and not multi and args.placements == 1 and args.compare_pool > 1 and args.fill_variant == 4 and total >= (1 << 24):
         pool2 = binding.OutputPool(eng, max(total, 1), L, D_out, candidates=args.compare_pool)
         d_ev = []
         one_step(False, pool2.ids, pool2.pde if D_out else None)
@@ -614,7 +664,7 @@ def main():
 
     # the same steps into ONE plain allocation that takes what comes (what a caller without the pool gets)
     plain = None
-    if not multi and args.placements > 1:
+    if args.full and not multi and args.placements > 1:
         p_ids = torch.empty((max(total, 1), L), dtype=torch.int32, device=device)
         p_pde = None if args.ids_only else torch.empty((max(total, 1), e * L), dtype=torch.float64, device=device)
         p_ev = []
@@ -638,28 +688,29 @@ def main():
         torch.cuda.synchronize()
         return r, (time.perf_counter() - t) * 1e3
     per_step = {}
-    if multi:
-        _, per_step["vde_and_allgather_ms"] = phase(sb.exchange_vde)
-        t_, per_step["count_ms"] = phase(sb.count)
-    else:
-        _, per_step["vde_ms"] = phase(lambda: eng.vde(want=False))
-        t_, per_step["count_ms"] = phase(sb._count_single)
-    _, per_step["fill_ms"] = phase(lambda: eng.fill_paths_device(0, t_, out_ids, out_pde, None))
+    if args.full:
+        if multi:
+            _, per_step["vde_and_allgather_ms"] = phase(sb.exchange_vde)
+            t_, per_step["count_ms"] = phase(sb.count)
+        else:
+            _, per_step["vde_ms"] = phase(lambda: eng.vde(want=False))
+            t_, per_step["count_ms"] = phase(sb._count_single)
+        _, per_step["fill_ms"] = phase(lambda: eng.fill_paths_device(0, t_, out_ids, out_pde, None))
 
-    # sanity of what was just timed (outside the timed region): global path count = sum C(deg, 2) and the
-    # middle-vertex checksum sum_paths(b) = sum_v v * C(deg v, 2), both closed forms of the input graph
-    deg64 = np.diff(g["offsets"].astype(np.int64))
-    want_paths = int((deg64 * (deg64 - 1) // 2).sum())
-    want_mid = int((np.arange(args.n, dtype=np.int64) * (deg64 * (deg64 - 1) // 2)).sum())
-    chk = torch.stack([ids_view[:total, 1].to(torch.int64).sum(), torch.tensor(total, device=device)]).to(torch.int64)
-    if multi:
-        chk_h = chk.cpu() if staged else chk
-        dist.all_reduce(chk_h, op=dist.ReduceOp.SUM)
-        chk = chk_h
-    got_mid, got_paths = (int(x) for x in chk.tolist())
-    if (got_paths, got_mid) != (want_paths, want_mid) or sb.global_total != want_paths:
-        raise SystemExit(f"bench sanity check failed: paths {got_paths} (want {want_paths}), middle checksum {got_mid} "
-                         f"(want {want_mid})")
+        # sanity of what was just timed (outside the timed region): global path count = sum C(deg, 2) and the
+        # middle-vertex checksum sum_paths(b) = sum_v v * C(deg v, 2), both closed forms of the input graph
+        deg64 = np.diff(g["offsets"].astype(np.int64))
+        want_paths = int((deg64 * (deg64 - 1) // 2).sum())
+        want_mid = int((np.arange(args.n, dtype=np.int64) * (deg64 * (deg64 - 1) // 2)).sum())
+        chk = torch.stack([ids_view[:total, 1].to(torch.int64).sum(), torch.tensor(total, device=device)]).to(torch.int64)
+        if multi:
+            chk_h = chk.cpu() if staged else chk
+            dist.all_reduce(chk_h, op=dist.ReduceOp.SUM)
+            chk = chk_h
+        got_mid, got_paths = (int(x) for x in chk.tolist())
+        if (got_paths, got_mid) != (want_paths, want_mid) or sb.global_total != want_paths:
+            raise SystemExit(f"bench sanity check failed: paths {got_paths} (want {want_paths}), middle checksum {got_mid} "
+                             f"(want {want_mid})")
     if multi:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if staged else device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -736,12 +787,14 @@ def main():
                config=dict(workload=f"{'power-law' if args.powerlaw else 'G'}(n={args.n}, m={args.m}) seed {args.seed}, {args.labels} labels, l=2, e={e}, "
                                     f"degree-sorted order; {'ids only' if args.ids_only else 'ids + pde'}",
                            paths=global_total, parallelism=f"slab{world}", fill_variant=args.fill_variant),
-               roofline=roofline, sanity="path count and middle-vertex checksum match the closed forms",
+               roofline=roofline,
+               sanity="path count and middle-vertex checksum match the closed forms" if args.full else
+                      "path count of the timed steps = the sizing pass (closed forms checked with --full)",
                phases_ms=dict(one_time={k: round(v, 3) for k, v in one_time.items()},
                               per_step={k: round(v, 3) for k, v in per_step.items()},
                               note="one_time = distributing / loading the graph structure (rows, reverse positions, halo rows); "
                                    "per_step = what `value` times, here from one untimed step with a device synchronisation after every "
-                                   "phase (the timed steps run without any)"))
+                                   "phase (the timed steps run without any; --full only)"))
     # what the first hardware SCALE record is to be judged against (per-rank kernels of config 4 emulated on one GPU,
     # scripts/emulate_rank.py, + the 16 MB vde all-gather over xGMI + launch gaps); strong scaling, so ms per step falls with N
     out["expected_ms_per_step"] = {"1": [3.55, 4.35], "2": [2.5, 2.9], "4": [1.5, 1.8], "8": [1.0, 1.3],
@@ -753,7 +806,7 @@ def main():
                            local_paths=int(total), note="rank 0's share; halo rows are truncated to the slab's rank range")
         out["config"]["collectives"] = "gloo, staged through host memory (GNNPE_BENCH_SAME_DEVICE=1)" if staged else "rccl"
 
-    legs = not multi and not args.no_index and not args.ids_only
+    legs = args.full and not multi and not args.no_index and not args.ids_only
     # index-build wallclock (second half of BASELINE.json's metric), measured outside the timed steps.
     # (a) device image: R*-tree file image of every path (p = 1), bulk-loaded on the device
     if legs:
@@ -872,7 +925,7 @@ def main():
             if "index_build" in out:
                 out["index_build"]["files"] = {k: dict(seconds=v.get("index_build_s"), bytes=v.get("index_bytes"))
                                                for k, v in e2e.items() if isinstance(v, dict) and "index_build_s" in v}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 sn_, sm_ = (int(x) for x in args.cpu_sample.split(","))
                 small = cpu_baseline(sn_, sm_, args.seed)

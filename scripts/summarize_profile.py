@@ -1,4 +1,4 @@
-"""Condense the rocprofv3 output of scripts/gpu_profile.sh (gpurun_out/<round>_trace, <round>_pmc_*) into the files kept
+"""Condense the rocprofv3 output of scripts/gpu_profile.sh ($OUT/<round>_trace, <round>_pmc_*) into the files kept
 under profiles/:
   <round>_kernel_stats.csv  per kernel: calls / average / total, with the launches of the emit kernel split by WHAT launched
                             them (sizing pass, the output pool's probes per candidate, warm-up, the timed steps, the plain-
@@ -15,6 +15,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", "profile_out")  # the profiling scripts' output folder, relative to ROOT
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r03"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 2
@@ -25,7 +26,7 @@ PATHS, BPP = 200031576, 92  # config 3: paths per launch, SURVEY 8(d) bytes per 
 
 
 def newest(pattern):
-    files = glob.glob(os.path.join(ROOT, "gpurun_out", pattern))
+    files = glob.glob(os.path.join(ROOT, OUT, pattern))
     return max(files, key=os.path.getmtime) if files else None
 
 
@@ -44,7 +45,7 @@ if trace:
     rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
     groups = {}
     fills = [r for r in rows if kernel in r["Kernel_Name"]]
-    # launch order of the emit kernel in `bench.py --steps S --warmup W` (config 3 on one GPU, device legs only):
+    # launch order of the emit kernel in `bench.py --full --steps S --warmup W` (config 3 on one GPU, device legs only):
     # 1 sizing pass is count-only; pool: 3 launches per candidate; W warm-up; S timed; plain allocation: 1 warm + max(3, S // 2);
     # 1 phase step.  (k_fill_ranked launches of other sizes -- config 2 -- are told apart by their grid.)
     big = [r for r in fills if int(r["Grid_Size_X"]) == max(int(x["Grid_Size_X"]) for x in fills)]
@@ -78,7 +79,7 @@ if trace:
         lines.append((k, len(d), sum(d) / len(d), sum(d)))
     timed = [l for l in lines if "TIMED STEPS" in l[0]]
     with open(os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats.csv"), "w") as f:
-        f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps {steps} --warmup {warm} --no-cpu-baseline --no-index --no-config5 (scripts/gpu_profile.sh)\n")
+        f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps {steps} --warmup {warm} --no-cpu-baseline --no-index --no-config5 (scripts/gpu_profile.sh)\n")
         f.write("# one row per kernel; the emit kernel's launches are split by what launched them (scripts/summarize_profile.py)\n")
         if timed:
             ms = timed[0][2]
@@ -92,10 +93,10 @@ if trace:
         print(f"  {l[0]:70s} calls {l[1]:4d} avg {l[2]:8.3f} ms")
 
 counters = {}
-for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"{rnd}_pmc_*"))):
+for d in sorted(glob.glob(os.path.join(ROOT, OUT, f"{rnd}_pmc_*"))):
     if not os.path.isdir(d):
         continue
-    f = newest(os.path.relpath(d, os.path.join(ROOT, "gpurun_out")) + "/*/*_counter_collection.csv")
+    f = newest(os.path.relpath(d, os.path.join(ROOT, OUT)) + "/*/*_counter_collection.csv")
     if not f:
         continue
     per, grid = {}, {}
@@ -109,7 +110,7 @@ for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"{rnd}_pmc_*"))):
         v = [x for k, x in by_dispatch.items() if grid.get(k, gmax) == gmax]  # config-3 launches only
         counters[name] = dict(launches=len(v), mean=sum(v) / len(v), min=min(v), max=max(v))
 out = dict(kernel=f"{kernel}<2,true,64>",
-           command="python3 bench.py --steps 2 --warmup 1 --placements 1 --no-cpu-baseline --no-index --no-config5 (one rocprofv3 --pmc pass per counter set)",
+           command="python3 bench.py --full --steps 2 --warmup 1 --placements 1 --no-cpu-baseline --no-index --no-config5 (one rocprofv3 --pmc pass per counter set)",
            counters=counters)
 if "WRITE_SIZE" in counters:
     wb = counters["WRITE_SIZE"]["mean"] * 1024

@@ -1,16 +1,17 @@
 """profiles/<round>_kernel_stats.csv from the kernel trace of the round-4 bench command (scripts/gpu_profile_r04.sh):
-    rocprofv3 --kernel-trace --stats -- python3 bench.py --steps S --warmup W --compare-pool 0 --no-cpu-baseline --no-index --no-config5
+    rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps S --warmup W --compare-pool 0 --no-cpu-baseline --no-index --no-config5
 One row per kernel; the launches of the two emit kernels (k_fill_ranked = start-vertex waves, k_fill_tiles = output tiles) at
 config-3 size are split by WHAT launched them, in launch order: the pool's shape calibration (3 + 3), the bench's own
 calibration call (3 + 3), W warm-up steps, S TIMED STEPS, the phase step.  The timed-step row is the one bench.py's
 roofline.launch_ms must agree with.     python scripts/summarize_trace_r04.py r04 [S=10] [W=2]"""
 import csv, glob, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", "profile_out")  # the profiling scripts' output folder, relative to ROOT
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r04"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 HBM, PATHS, BPP = 8000.0, 200031576, 92
-files = glob.glob(os.path.join(ROOT, "gpurun_out", f"{rnd}_trace/*/*_kernel_trace.csv"))
+files = glob.glob(os.path.join(ROOT, OUT, f"{rnd}_trace/*/*_kernel_trace.csv"))
 trace = max(files, key=os.path.getmtime)
 rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
 dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
@@ -54,7 +55,7 @@ for k, d in groups.items():
 timed = [l for l in lines if "TIMED STEPS" in l[0]]
 cal = {l[0]: l[2] for l in lines if "calibration" in l[0]}
 with open(os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats.csv"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps {steps} --warmup {warm} --compare-pool 0 --no-cpu-baseline --no-index --no-config5 (scripts/gpu_profile_r04.sh)\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps {steps} --warmup {warm} --compare-pool 0 --no-cpu-baseline --no-index --no-config5 (scripts/gpu_profile_r04.sh)\n")
     f.write("# one row per kernel; the emit kernels' launches at config-3 size are split by what launched them (scripts/summarize_trace_r04.py)\n")
     if timed:
         ms = timed[0][2]
@@ -62,7 +63,7 @@ with open(os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats.csv"), "w") as f:
                 f"{PATHS * BPP / ms / 1e6 / HBM:.3f} of the {HBM / 1000:.0f} TB/s spec (one allocation as it came; the faster emit shape for it)\n")
     try:  # the bench's own event timing of the SAME run (the JSON line the traced command printed)
         import json
-        line = [l for l in open(os.path.join(ROOT, "gpurun_out", f"{rnd}_trace.log")) if l.startswith('{"metric"')][-1]
+        line = [l for l in open(os.path.join(ROOT, OUT, f"{rnd}_trace.log")) if l.startswith('{"metric"')][-1]
         rf = json.loads(line)["roofline"]
         f.write(f"# bench.py's own timing of the same run: roofline.launch_ms {rf['launch_ms']:.3f} ms, frac {rf['frac']:.3f}, kernel {rf['kernel']}, "
                 f"emit_shapes {rf['emit_shapes']['starts_ms']} / {rf['emit_shapes']['tiles_ms']} ms kept {rf['emit_shapes']['kept']}\n")

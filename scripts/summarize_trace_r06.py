@@ -1,5 +1,5 @@
 """profiles/<round>_kernel_stats.csv from the kernel trace of the round-5 bench command (scripts/gpu_profile_r06.sh):
-    rocprofv3 --kernel-trace --stats -- python3 bench.py --steps S --warmup W --compare-pool 0 --no-cpu-baseline --no-index --no-config5
+    rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps S --warmup W --compare-pool 0 --no-cpu-baseline --no-index --no-config5
 One row per kernel.  The emit kernels' launches at config-3 size are split by WHAT launched them, from the end of the run backwards: the
 phase step (last), the S TIMED STEPS, the W warm-up steps; everything before that is calibration (the pool's and the bench's own call of
 gnnpe_emit_calibrate_device: shapes 1 / 4 / 2, three launches each), grouped by kernel and grid (k_fill_ranked: 1280 workgroups = five per
@@ -7,11 +7,12 @@ CU, 768 = three per CU).  The TIMED STEPS row is the one bench.py's roofline.lau
 other shapes into the SAME buffer.     python scripts/summarize_trace_r06.py r05 [S=10] [W=2]"""
 import csv, glob, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", "profile_out")  # the profiling scripts' output folder, relative to ROOT
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r06"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 warm = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 HBM, PATHS, BPP = 8000.0, 200031576, 92
-files = glob.glob(os.path.join(ROOT, "gpurun_out", f"{rnd}_trace/*/*_kernel_trace.csv"))
+files = glob.glob(os.path.join(ROOT, OUT, f"{rnd}_trace/*/*_kernel_trace.csv"))
 trace = max(files, key=os.path.getmtime)
 rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
 dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
@@ -64,14 +65,14 @@ for r in rows:
 for k, d in others.items():
     lines.append((k, len(d), sum(d) / len(d), sum(d)))
 with open(os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats.csv"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps {steps} --warmup {warm} --compare-pool 0 --no-cpu-baseline --no-index --no-config5 (scripts/gpu_profile_r06.sh)\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps {steps} --warmup {warm} --compare-pool 0 --no-cpu-baseline --no-index --no-config5 (scripts/gpu_profile_r06.sh)\n")
     f.write("# one row per kernel; the emit kernels' launches at config-3 size are split by what launched them (scripts/summarize_trace_r06.py)\n")
     if timed:
         ms = sum(dur(r) for r in timed) / len(timed)
         f.write(f"# timed steps ({label(timed[0])}): {ms:.3f} ms per launch -> {PATHS} paths x {BPP} B / {ms:.3f} ms = {PATHS * BPP / ms / 1e6:.0f} GB/s = "
                 f"{PATHS * BPP / ms / 1e6 / HBM:.3f} of the {HBM / 1000:.0f} TB/s spec (one allocation as it came; the fastest of three emit launches for it)\n")
     try:  # the bench's own event timing of the SAME run (the JSON line the traced command printed)
-        line = [l for l in open(os.path.join(ROOT, "gpurun_out", f"{rnd}_trace.log")) if l.startswith('{"metric"')][-1]
+        line = [l for l in open(os.path.join(ROOT, OUT, f"{rnd}_trace.log")) if l.startswith('{"metric"')][-1]
         d = json.loads(line)
         rf = d["roofline"]
         f.write(f"# bench.py's own timing of the same run: ms_per_step {d['ms_per_step']:.3f}, roofline.launch_ms {rf['launch_ms']:.3f} ms, frac {rf['frac']:.3f}, "

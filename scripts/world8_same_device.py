@@ -67,7 +67,7 @@ for R in (2, 4):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GNNPE_BENCH_SAME_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(R), "--vertices", str(n), "--edges", str(m), "--steps", "5",
-                        "--warmup", "2", "--no-index", "--no-cpu-baseline", "--no-config5"], capture_output=True, text=True, env=env)
+                        "--warmup", "2", "--full", "--no-index", "--no-cpu-baseline", "--no-config5"], capture_output=True, text=True, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     dline = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     print(f"R={R}: n_gpus {dline['n_gpus']}, paths {dline['config']['paths']}, sanity: {dline['sanity']}; ms_per_step {dline['ms_per_step']:.3f} "

@@ -138,7 +138,7 @@ def test_bench_multi_rank_flow_on_one_device(tmp_path):
     env = dict(os.environ, GNNPE_BENCH_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--vertices", "200000", "--edges", "2000000", "--placements", "1"]
+           "--vertices", "200000", "--edges", "2000000", "--placements", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -95,7 +95,7 @@ def test_bench_multi_gpu_path_over_a_one_rank_rccl_group(tmp_path):
     env = dict(os.environ, GNNPE_BENCH_FORCE_RCCL="1", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29541")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--vertices", "200000", "--edges", "2000000", "--steps", "3",
-                        "--warmup", "1", "--placements", "3", "--no-cpu-baseline", "--no-index"], capture_output=True, text=True,
+                        "--warmup", "1", "--placements", "3", "--full", "--no-cpu-baseline", "--no-index"], capture_output=True, text=True,
                        env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -113,7 +113,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GNNPE_BENCH_SAME_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--vertices", "100000", "--edges", "1000000",
-                        "--steps", "3", "--warmup", "1", "--no-index", "--no-cpu-baseline", "--no-config5"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-index", "--no-cpu-baseline", "--no-config5"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
