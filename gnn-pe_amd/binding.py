@@ -108,6 +108,10 @@ SIGNATURES = {
     "gnnpe_pge_groups": (C.c_int, [_vp, _f64p, _f64p]),
     "gnnpe_pge_device_ptr": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "gnnpe_pge_build_index": (C.c_int, [_vp, C.c_uint64, _u32p, C.c_char_p]),
+    "gnnpe_host_pge_query_groups": (C.c_int, [C.c_char_p, C.c_uint32, _u32p, C.POINTER(_u32p), C.POINTER(_u32p),
+                                              C.POINTER(_f64p), C.POINTER(_f64p)]),
+    "gnnpe_pge_set_groups": (C.c_int, [_vp, _f64p, _f64p]),
+    "gnnpe_pge_filter_candidates": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _f64p, _f64p, _u32p, _f64p]),
     "gnnpe_fill_kernel_name": (C.c_char_p, []),
     "gnnpe_set_fill_variant": (C.c_int, [_vp, C.c_int]),
     "gnnpe_set_emit_shape": (C.c_int, [_vp, C.c_int]),
@@ -116,7 +120,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 6  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 7  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 _lib = None
 
 
@@ -282,6 +286,29 @@ def host_query_plan(path, e):
         lib.gnnpe_host_free(ptr)
     out["pde"] = np.ctypeslib.as_array(pp, shape=(max(k * 3 * e, 1),)).copy()[: k * 3 * e].reshape(k, 3 * e)
     lib.gnnpe_host_free(pp)
+    return out
+
+
+def host_pge_query_groups(path, e):
+    """GNN-PGE query side (GNN-PGE/src/main.cpp:253-329) through the library's host code.  Returns dict(n_vertices,
+    labels, degrees (n), pg, plg (n x 4e)).  A query vertex without an edge raises GnnpeError."""
+    lib = load()
+    nv = C.c_uint32()
+    pl, pd = _u32p(), _u32p()
+    pg, plg = _f64p(), _f64p()
+    rc = lib.gnnpe_host_pge_query_groups(path.encode(), int(e), C.byref(nv), C.byref(pl), C.byref(pd), C.byref(pg), C.byref(plg))
+    if rc == -1:
+        raise FileNotFoundError(lib.gnnpe_last_error().decode())
+    if rc:
+        raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
+    n, w = nv.value, 4 * int(e)
+    out = dict(n_vertices=n)
+    for name, ptr in (("labels", pl), ("degrees", pd)):
+        out[name] = np.ctypeslib.as_array(ptr, shape=(max(n, 1),)).copy()[:n]
+        lib.gnnpe_host_free(ptr)
+    for name, ptr in (("pg", pg), ("plg", plg)):
+        out[name] = np.ctypeslib.as_array(ptr, shape=(max(n * w, 1),)).copy()[: n * w].reshape(n, w)
+        lib.gnnpe_host_free(ptr)
     return out
 
 
@@ -820,3 +847,24 @@ class Engine:
     def pge_build_index(self, vertices, path):
         v = _np(vertices, np.uint32)
         self._ck(self.lib.gnnpe_pge_build_index(self.ctx, len(v), _ptr(v, _u32p), path.encode()))
+
+    # GNN-PGE online filter (GNN-PGE/src/main.cpp:197-361, custom.h:327-374)
+    def pge_set_groups(self, pg, plg):
+        """Path groups read from data_vertices.bin instead of pge_groups(): n x 4e doubles each (after load_csr and
+        set_label_table)."""
+        a, b = _np(pg, np.float64), _np(plg, np.float64)
+        assert a.size == b.size == self.n * 4 * self.e, (a.shape, b.shape, self.n, self.e)
+        self._ck(self.lib.gnnpe_pge_set_groups(self.ctx, _ptr(a, _f64p), _ptr(b, _f64p)))
+
+    def pge_filter_candidates(self, q):
+        """q: dict from host_pge_query_groups (labels, degrees, pg, plg).  Returns (bitmap [n_query_vertices x ceil(n/32)]
+        uint32, device ms), the layout of filter_candidates."""
+        l, d = _np(q["labels"], np.uint32), _np(q["degrees"], np.uint32)
+        pg, plg = _np(q["pg"], np.float64), _np(q["plg"], np.float64)
+        nv = len(l)
+        assert len(d) == nv and pg.size == plg.size == nv * 4 * self.e, (nv, pg.shape, plg.shape, self.e)
+        bm = np.zeros((nv, (self.n + 31) // 32), np.uint32)
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_pge_filter_candidates(self.ctx, nv, _ptr(l, _u32p), _ptr(d, _u32p), _ptr(pg, _f64p),
+                                                      _ptr(plg, _f64p), _ptr(bm, _u32p), C.byref(ms)))
+        return bm, ms.value

@@ -266,6 +266,7 @@ struct gnnpe_ctx {
     uint64_t img_gen = 0, img_bytes = 0;
     gnnpe::DevBuf pge_pg, pge_plg;  // GNN-PGE path groups (n x 4e doubles each)
     bool have_pge = false;
+    uint32_t pge_e = 0;  // the e the groups were made for (gnnpe_set_label_table may change c->e after them)
 
     // pinned host words for small read-backs
     uint64_t *h_pinned = nullptr;

@@ -129,6 +129,49 @@ int gnnpe_host_query_plan(const char *query_graph_path, uint32_t e, uint32_t *n_
     return 0;
 }
 
+int gnnpe_host_pge_query_groups(const char *query_graph_path, uint32_t e, uint32_t *n_query_vertices, uint32_t **labels,
+                                uint32_t **degrees, double **path_group, double **path_label_group)
+{
+    if (!query_graph_path || !n_query_vertices || !labels || !degrees || !path_group || !path_label_group) {
+        gnnpe::set_error("gnnpe_host_pge_query_groups: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    int rc = q.load(query_graph_path, &err, true);
+    if (rc != 0) {
+        gnnpe::set_error("%s", err.c_str());
+        return rc;
+    }
+    gnnpe_host::PgeQueryGroups grp;
+    if ((rc = gnnpe_host::build_pge_query_groups(q, e, &grp, &err)) != 0) {
+        gnnpe::set_error("%s: %s", query_graph_path, err.c_str());
+        return rc == -3 ? GNNPE_ERR_UNSUPPORTED : GNNPE_ERR_ARG;
+    }
+    *n_query_vertices = grp.n_vertices;
+    *labels = (uint32_t *)malloc((grp.labels.size() + 1) * sizeof(uint32_t));
+    *degrees = (uint32_t *)malloc((grp.degrees.size() + 1) * sizeof(uint32_t));
+    *path_group = (double *)malloc((grp.pg.size() + 1) * sizeof(double));
+    *path_label_group = (double *)malloc((grp.plg.size() + 1) * sizeof(double));
+    if (!*labels || !*degrees || !*path_group || !*path_label_group) {
+        free(*labels);
+        free(*degrees);
+        free(*path_group);
+        free(*path_label_group);
+        *labels = *degrees = nullptr;
+        *path_group = *path_label_group = nullptr;
+        gnnpe::set_error("gnnpe_host_pge_query_groups: out of host memory");
+        return GNNPE_ERR_ARG;
+    }
+    if (grp.n_vertices) {
+        memcpy(*labels, grp.labels.data(), grp.labels.size() * sizeof(uint32_t));
+        memcpy(*degrees, grp.degrees.data(), grp.degrees.size() * sizeof(uint32_t));
+        memcpy(*path_group, grp.pg.data(), grp.pg.size() * sizeof(double));
+        memcpy(*path_label_group, grp.plg.data(), grp.plg.size() * sizeof(double));
+    }
+    return 0;
+}
+
 void gnnpe_host_free(void *ptr) { free(ptr); }
 
 // ---- the online side's data load from binary sidecars ---------------------------------------------------

@@ -39,6 +39,75 @@ void dfs(const StaticGraph &q, std::vector<uint32_t> &path, std::set<std::vector
 
 }  // namespace
 
+int query_vde(const StaticGraph &q, uint32_t e, std::vector<double> *x_out, std::vector<double> *vde_out, std::string *err)
+{
+    // gen_vde (custom.h:513-544): x from the label, nx summed over ascending neighbours from 0.0, vde = x + nx
+    const uint32_t n = q.n, n_labels = std::max<uint32_t>(q.labels_count, 1);
+    std::vector<double> table((size_t)n_labels * e);
+    std::vector<double> &x = *x_out, &vde = *vde_out;
+    x.assign((size_t)n * e, 0.0);
+    vde.assign((size_t)n * e, 0.0);
+    if (gnnpe_host_label_table(n_labels, e, table.data()) != 0) {
+        if (err) *err = "label table failed";
+        return -2;
+    }
+    for (uint32_t v = 0; v < n; v++)
+        for (uint32_t k = 0; k < e; k++) x[(size_t)v * e + k] = table[(size_t)q.labels[v] * e + k];
+    for (uint32_t v = 0; v < n; v++)
+        for (uint32_t k = 0; k < e; k++) {
+            double nx = 0.0;
+            for (uint32_t i = q.offsets[v]; i < q.offsets[v + 1]; i++) nx += x[(size_t)q.neighbors[i] * e + k];
+            vde[(size_t)v * e + k] = x[(size_t)v * e + k] + nx;
+        }
+    return 0;
+}
+
+int build_pge_query_groups(const StaticGraph &q, uint32_t e, PgeQueryGroups *out, std::string *err)
+{
+    if (!out || e == 0) {
+        if (err) *err = "build_pge_query_groups: null output / e = 0";
+        return -2;
+    }
+    const uint32_t n = q.n, D = 2 * e, W = 2 * D;
+    for (uint32_t u = 0; u < n; u++)
+        if (q.degree(u) == 0) {  // its group stays empty in the reference (main.cpp:278-281), and its leaf test reads past it
+            if (err) *err = "query vertex " + std::to_string(u) + " has no edge: GNN-PGE defines no path group for it";
+            return -3;
+        }
+    std::vector<double> x, vde;
+    if (query_vde(q, e, &x, &vde, err) != 0) return -2;
+    out->n_vertices = n;
+    out->e = e;
+    out->labels.assign(q.labels.begin(), q.labels.begin() + n);
+    out->degrees.resize(n);
+    out->pg.assign((size_t)n * W, 0.0);
+    out->plg.assign((size_t)n * W, 0.0);
+    std::vector<double> pe(D), le(D);
+    for (uint32_t u = 0; u < n; u++) {
+        out->degrees[u] = q.degree(u);
+        double *g = &out->pg[(size_t)u * W], *lg = &out->plg[(size_t)u * W];
+        // main.cpp:253-329: the 1-hop paths (u, w), w in adjacency order; the first path's embedding seeds [lo, hi], the others
+        // replace a bound they pass -- the reference's own compare-and-replace, in its order
+        for (uint32_t i = q.offsets[u]; i < q.offsets[u + 1]; i++) {
+            const uint32_t w = q.neighbors[i];
+            for (uint32_t k = 0; k < e; k++) {
+                pe[k] = vde[(size_t)u * e + k];
+                pe[e + k] = vde[(size_t)w * e + k];
+                le[k] = x[(size_t)u * e + k];
+                le[e + k] = x[(size_t)w * e + k];
+            }
+            const bool first = i == q.offsets[u];
+            for (uint32_t j = 0; j < D; j++) {
+                if (first || g[2 * j] > pe[j]) g[2 * j] = pe[j];
+                if (first || g[2 * j + 1] < pe[j]) g[2 * j + 1] = pe[j];
+                if (first || lg[2 * j] > le[j]) lg[2 * j] = le[j];
+                if (first || lg[2 * j + 1] < le[j]) lg[2 * j + 1] = le[j];
+            }
+        }
+    }
+    return 0;
+}
+
 int build_query_plan(const StaticGraph &q, uint32_t e, QueryPlan *out, std::string *err)
 {
     if (!out || e == 0) {
@@ -63,21 +132,8 @@ int build_query_plan(const StaticGraph &q, uint32_t e, QueryPlan *out, std::stri
         dfs(q, path, seen, all_paths);
     }
 
-    // gen_vde (custom.h:513-544): x from the label, nx summed over ascending neighbours from 0.0, vde = x + nx
-    const uint32_t n_labels = std::max<uint32_t>(q.labels_count, 1);
-    std::vector<double> table((size_t)n_labels * e), x((size_t)n * e), vde((size_t)n * e);
-    if (gnnpe_host_label_table(n_labels, e, table.data()) != 0) {
-        if (err) *err = "label table failed";
-        return -2;
-    }
-    for (uint32_t v = 0; v < n; v++)
-        for (uint32_t k = 0; k < e; k++) x[(size_t)v * e + k] = table[(size_t)q.labels[v] * e + k];
-    for (uint32_t v = 0; v < n; v++)
-        for (uint32_t k = 0; k < e; k++) {
-            double nx = 0.0;
-            for (uint32_t i = q.offsets[v]; i < q.offsets[v + 1]; i++) nx += x[(size_t)q.neighbors[i] * e + k];
-            vde[(size_t)v * e + k] = x[(size_t)v * e + k] + nx;
-        }
+    std::vector<double> x, vde;
+    if (query_vde(q, e, &x, &vde, err) != 0) return -2;
 
     // gen_query_pde (custom.h:574-631): weight = sum of degrees; std::sort by weight, descending -- the same
     // library algorithm and comparator as the reference, so ties fall the same way

@@ -25,6 +25,22 @@ struct QueryPlan {
     uint32_t n_paths() const { return L ? (uint32_t)(vids.size() / L) : 0; }
 };
 
+// gen_vde (custom.h:513-544) of the query vertices: x (n x e) from the label table, vde = x + the neighbours' x summed in
+// adjacency order.  0 = ok; <0 with *err set
+int query_vde(const StaticGraph &query, uint32_t e, std::vector<double> *x, std::vector<double> *vde, std::string *err);
+
+// GNN-PGE query side (GNN-PGE/src/main.cpp:253-329): per query vertex u the per-dimension [lo, hi] of [vde[u], vde[w]]
+// (path_group) and of [x[u], x[w]] (path_label_group) over its 1-hop paths (u, w); n x 4e doubles each, laid out
+// (lo0, hi0, lo1, hi1, ...) like the data side (gnnpe_pge_groups).
+struct PgeQueryGroups {
+    uint32_t n_vertices = 0, e = 0;
+    std::vector<uint32_t> labels, degrees;  // n
+    std::vector<double> pg, plg;            // n x 4e
+};
+
+// 0 = ok; -3 = a query vertex without an edge (no group: the reference's leaf test would read an empty vector); -2 otherwise
+int build_pge_query_groups(const StaticGraph &query, uint32_t e, PgeQueryGroups *out, std::string *err);
+
 // 0 = ok; <0 with *err set
 int build_query_plan(const StaticGraph &query, uint32_t e, QueryPlan *out, std::string *err);
 

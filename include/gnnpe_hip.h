@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GNNPE_ABI_VERSION 6
+#define GNNPE_ABI_VERSION 7
 
 #define GNNPE_OK 0
 #define GNNPE_ERR_ARG (-1)     /* bad argument / call order */
@@ -309,6 +309,29 @@ int gnnpe_pge_device_ptr(gnnpe_ctx *ctx, void **dev_path_group, void **dev_path_
  * host_vertices[i] (the partition's vertices in membership.txt order), son = i; written to `path`
  * (<f>gnn-pge/partitions/partition-i/index.dat). */
 int gnnpe_pge_build_index(gnnpe_ctx *ctx, uint64_t n_sel, const uint32_t *host_vertices, const char *path);
+
+/* ---- GNN-PGE online: the filter (GNN-PGE/src/main.cpp:197-361, custom.h:292-480) --------------------------------- */
+/* Query side (host, no GPU): gen_vde of the query graph, then per query vertex u the per-dimension [lo, hi] of the
+ * embeddings [vde[u], vde[w]] (path_group) and [x[u], x[w]] (path_label_group) over its 1-hop paths (u, w)
+ * (main.cpp:253-329): labels / degrees (n_query_vertices uint32) and pg / plg (n_query_vertices x 4e doubles, laid out
+ * like gnnpe_pge_groups), malloc'ed (gnnpe_host_free).  A query vertex without an edge has no group in the reference
+ * (its leaf test would read an empty vector): such a query is refused with GNNPE_ERR_UNSUPPORTED, the vertex named. */
+int gnnpe_host_pge_query_groups(const char *query_graph_path, uint32_t e, uint32_t *n_query_vertices, uint32_t **labels,
+                                uint32_t **degrees, double **path_group, double **path_label_group);
+/* Installs path groups read back from <f>gnn-pge/data_vertices.bin (n x 4e doubles each, vertex-id indexed) instead of
+ * computing them: the alternative to gnnpe_vde + gnnpe_pge_groups.  Call order: gnnpe_load_csr, gnnpe_set_label_table
+ * (it fixes e), then this; a later load or gnnpe_pge_groups replaces the groups. */
+int gnnpe_pge_set_groups(gnnpe_ctx *ctx, const double *host_path_group, const double *host_path_label_group);
+/* Data side (device): Partition::query of every partition at once.  The R-tree walk only prunes; its result is the leaf
+ * test (custom.h:327-374) applied to every data vertex, which is what this does: v is a candidate of query vertex u iff
+ * deg(u) <= deg(v), label(u) == label(v), and for every k < 2e  plg_v[2k+1] >= plg_u[2k], plg_v[2k] <= plg_u[2k+1] and
+ * pg_v[2k+1] >= pg_u[2k] -- exact fp64 comparisons, inclusive bounds, no epsilon.  Needs the whole graph (gnnpe_load_csr)
+ * and the groups (gnnpe_pge_groups or gnnpe_pge_set_groups).  q_pg / q_plg: n_query_vertices x 4e doubles as
+ * gnnpe_host_pge_query_groups returns them.  host_bitmap: n_query_vertices x ceil(n/32) uint32, the layout of
+ * gnnpe_filter_candidates (gnnpe_refine takes it unchanged).  device_ms (may be NULL): time on the device. */
+int gnnpe_pge_filter_candidates(gnnpe_ctx *ctx, uint32_t n_query_vertices, const uint32_t *q_labels, const uint32_t *q_degrees,
+                                const double *q_path_group, const double *q_path_label_group, uint32_t *host_bitmap,
+                                double *device_ms);
 
 /* ---- the online filter ------------------------------------------------------------ */
 /* Query side (host): what main.cpp:136-151 does to the query graph before it touches the index -- dfs_query
