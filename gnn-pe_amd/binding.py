@@ -98,6 +98,10 @@ SIGNATURES = {
     "gnnpe_set_degrees": (C.c_int, [_vp, _u32p]),
     "gnnpe_filter_candidates": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double, _u32p,
                                           _f64p]),
+    "gnnpe_host_query_plan_exact": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _u32p, _u32p, C.POINTER(_u32p),
+                                              C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_f64p)]),
+    "gnnpe_filter_candidates_exact": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double,
+                                                _u32p, _f64p]),
     "gnnpe_build_index_device": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.POINTER(_vp), _u64p,
                                            C.POINTER(C.c_int32)]),
     "gnnpe_build_index": (C.c_int, [_vp, C.c_uint32, C.c_char_p]),
@@ -120,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 7  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 8  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 _lib = None
 
 
@@ -286,6 +290,39 @@ def host_query_plan(path, e):
         lib.gnnpe_host_free(ptr)
     out["pde"] = np.ctypeslib.as_array(pp, shape=(max(k * 3 * e, 1),)).copy()[: k * 3 * e].reshape(k, 3 * e)
     lib.gnnpe_host_free(pp)
+    return out
+
+
+def host_query_plan_exact(path, e, l):
+    """Exact-mode plan (include/gnnpe_hip.h, gnnpe_host_query_plan_exact) at l = 2 or 3.  Returns dict(n_vertices, l, e,
+    main=(vids, labels, degrees: n x (l+1); pde: n x (l+1)e), tri=(the same at width 3), single=(width 1: the vde of the
+    vertex in pde)), each part a dict of those four arrays."""
+    lib = load()
+    nv = C.c_uint32()
+    counts = (C.c_uint32 * 3)()
+    pv, pl, pd = _u32p(), _u32p(), _u32p()
+    pp = _f64p()
+    rc = lib.gnnpe_host_query_plan_exact(path.encode(), int(e), int(l), C.byref(nv), counts, C.byref(pv), C.byref(pl),
+                                         C.byref(pd), C.byref(pp))
+    if rc == -1:
+        raise FileNotFoundError(lib.gnnpe_last_error().decode())
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    widths = (int(l) + 1, 3, 1)
+    k = sum(c * w for c, w in zip(counts, widths))
+    flat = {}
+    for name, ptr in (("vids", pv), ("labels", pl), ("degrees", pd)):
+        flat[name] = np.ctypeslib.as_array(ptr, shape=(max(k, 1),)).copy()[:k]
+        lib.gnnpe_host_free(ptr)
+    flat["pde"] = np.ctypeslib.as_array(pp, shape=(max(k * e, 1),)).copy()[: k * e]
+    lib.gnnpe_host_free(pp)
+    out = dict(n_vertices=nv.value, l=int(l), e=int(e))
+    o = 0
+    for part, c, w in zip(("main", "tri", "single"), counts, widths):
+        out[part] = dict(vids=flat["vids"][o:o + c * w].reshape(c, w), labels=flat["labels"][o:o + c * w].reshape(c, w),
+                         degrees=flat["degrees"][o:o + c * w].reshape(c, w),
+                         pde=flat["pde"][o * e:(o + c * w) * e].reshape(c, w * e))
+        o += c * w
     return out
 
 
@@ -660,6 +697,21 @@ class Engine:
         p = _np(plan["pde"], np.float64)
         self._ck(self.lib.gnnpe_filter_candidates(self.ctx, len(v), _ptr(v, _u32p), _ptr(l, _u32p), _ptr(d, _u32p),
                                                   _ptr(p, _f64p), nv, float(eps), _ptr(bm, _u32p), C.byref(ms)))
+        return bm, ms.value
+
+    def filter_candidates_exact(self, plan, eps=1e-6):
+        """Exact-mode filter.  plan: dict from host_query_plan_exact (each path once: the library adds the reverses).
+        Returns (bitmap [n_query_vertices x ceil(n/32)] uint32, device ms)."""
+        nv, l = int(plan["n_vertices"]), int(plan["l"])
+        parts = [plan[k] for k in ("main", "tri", "single")]
+        counts = (C.c_uint32 * 3)(*[len(p["vids"]) for p in parts])
+        v, lb, d = (np.ascontiguousarray(np.concatenate([np.asarray(p[k], np.uint32).ravel() for p in parts]))
+                    for k in ("vids", "labels", "degrees"))
+        pde = np.ascontiguousarray(np.concatenate([np.asarray(p["pde"], np.float64).ravel() for p in parts]))
+        bm = np.zeros((nv, (self.n + 31) // 32), np.uint32)
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_filter_candidates_exact(self.ctx, l, counts, _ptr(v, _u32p), _ptr(lb, _u32p), _ptr(d, _u32p),
+                                                        _ptr(pde, _f64p), nv, float(eps), _ptr(bm, _u32p), C.byref(ms)))
         return bm, ms.value
 
     def refine(self, query_path, bitmap, limit=0xFFFFFFFF):

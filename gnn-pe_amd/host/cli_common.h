@@ -33,6 +33,8 @@ struct Options {
     int gpus = 1;
     uint64_t chunk_paths = 8ull << 20;  // 8M paths per pass: small enough to pipeline render, copy-back and file writes
     bool allow_large = false, timing = false, sidecars = false, write_index = false;
+    bool exact = false;   // -m online / filter at -l 2: the orientation-complete filter (always on at -l 3; refused in other
+                          // modes; INTEGRATION.md "Exact mode")
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
     std::string transport = "rccl";  // --gpus N > 1: "rccl" (ncclSend/ncclRecv over xGMI) or "copy" (device-to-device copies)
@@ -107,7 +109,9 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         char key = 0;
         if (a == "-h" || a == "--help") {
             printf("%s -f <dataset dir/> -d <data.graph> -m offline -p <partitions> [-l 2] [-e 2]\n"
-                   "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n", tool);
+                   "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
+                   "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n",
+                   tool, tool);
             exit(0);
         }
         if (a == "--gpus" || a == "--chunk") {
@@ -129,6 +133,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "--index") { o.write_index = true; continue; }
         if (a == "--same-device") { o.same_device = true; continue; }
         if (a == "--strict") { o.strict = true; continue; }
+        if (a == "--exact") { o.exact = true; continue; }
         if (a.rfind("--", 0) == 0) {
             std::string name = a.substr(2);
             size_t eq = name.find('=');

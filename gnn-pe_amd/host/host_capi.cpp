@@ -129,6 +129,61 @@ int gnnpe_host_query_plan(const char *query_graph_path, uint32_t e, uint32_t *n_
     return 0;
 }
 
+int gnnpe_host_query_plan_exact(const char *query_graph_path, uint32_t e, uint32_t l, uint32_t *n_query_vertices,
+                                uint32_t counts[3], uint32_t **vids, uint32_t **labels, uint32_t **degrees, double **pde)
+{
+    if (!query_graph_path || !n_query_vertices || !counts || !vids || !labels || !degrees || !pde) {
+        gnnpe::set_error("gnnpe_host_query_plan_exact: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    if (l != 2 && l != 3) {
+        gnnpe::set_error("gnnpe_host_query_plan_exact: l = %u (2 or 3)", l);
+        return GNNPE_ERR_UNSUPPORTED;
+    }
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    int rc = q.load(query_graph_path, &err, true);
+    if (rc != 0) {
+        gnnpe::set_error("%s", err.c_str());
+        return rc;
+    }
+    gnnpe_host::ExactPlan plan;
+    if ((rc = gnnpe_host::build_query_plan_exact(q, e, l, &plan, &err)) != 0) {
+        gnnpe::set_error("%s", err.c_str());
+        return GNNPE_ERR_ARG;
+    }
+    const gnnpe_host::QueryPlan *parts[3] = {&plan.main, &plan.tri, &plan.single};
+    size_t k = 0;
+    for (int i = 0; i < 3; i++) k += parts[i]->vids.size();
+    uint32_t *v = (uint32_t *)malloc((k + 1) * 4), *lb = (uint32_t *)malloc((k + 1) * 4), *dg = (uint32_t *)malloc((k + 1) * 4);
+    double *p = (double *)malloc((k * e + 1) * 8);
+    if (!v || !lb || !dg || !p) {
+        free(v);
+        free(lb);
+        free(dg);
+        free(p);
+        gnnpe::set_error("gnnpe_host_query_plan_exact: out of host memory");
+        return GNNPE_ERR_ARG;
+    }
+    size_t o = 0;
+    for (int i = 0; i < 3; i++) {
+        const gnnpe_host::QueryPlan &q3 = *parts[i];
+        counts[i] = q3.n_paths();
+        if (q3.vids.empty()) continue;
+        memcpy(v + o, q3.vids.data(), q3.vids.size() * 4);
+        memcpy(lb + o, q3.labels.data(), q3.labels.size() * 4);
+        memcpy(dg + o, q3.degrees.data(), q3.degrees.size() * 4);
+        memcpy(p + o * e, q3.pde.data(), q3.pde.size() * 8);
+        o += q3.vids.size();
+    }
+    *n_query_vertices = q.n;
+    *vids = v;
+    *labels = lb;
+    *degrees = dg;
+    *pde = p;
+    return 0;
+}
+
 int gnnpe_host_pge_query_groups(const char *query_graph_path, uint32_t e, uint32_t *n_query_vertices, uint32_t **labels,
                                 uint32_t **degrees, double **path_group, double **path_label_group)
 {

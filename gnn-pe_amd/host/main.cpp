@@ -15,7 +15,8 @@
 //     writes nothing: main.cpp:80,101,110 never check their streams);
 //   - `-l 3` writes 4-vertex paths (the rule of custom.h:66-92 with the DFS depth fixed; BASELINE config 5),
 //     where the reference enumerates 3-vertex paths whatever -l says and prints a garbage 4th column
-//     (SURVEY D4); its online binary cannot read those files.  Other -l values are refused;
+//     (SURVEY D4); its online binary cannot read those files.  `-m online|filter -l 3` queries with 4-vertex paths, in exact
+//     mode (the reference has no l = 3 semantics to follow).  Other -l values are refused;
 //   - path counts beyond 2^32-1 are refused unless --allow-large (the reference's `ui` overflows).
 #include <dlfcn.h>
 #include <sys/stat.h>
@@ -154,6 +155,10 @@ struct Device {
     uint64_t total = 0, base = 0;
 };
 
+// Exact mode (--exact at -l 2, always at -l 3): the plan of gnnpe_host_query_plan_exact, every path tested in
+// both orientations, so that the refinement counts every embedding.  Same answer line and candidates.bin; --timing adds the plan
+// sizes by path width and the candidate count of every query vertex.
+//
 // -m online / -m filter: the reference's `-m online` (main.cpp:121-185) without its files.  Filter on the GPU -- query plan on the host
 // (dfs_query / gen_query_pde), then the leaf test of Partition::query over every enumerated data path.  No
 // all_paths.txt, no index.dat: only the data graph and membership.txt (any order gives the same candidate sets).
@@ -163,7 +168,7 @@ struct Device {
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
-    if (o.path_length != 2) die("-m filter: only -l 2 (the reference's online side only works for it)");
+    const bool exact = o.exact || o.path_length == 3;  // (main() admits -l 2 and -l 3 only)
     StaticGraph g;
     std::string err;
     int rc = g.load(o.data_graph, &err, o.strict);
@@ -172,14 +177,21 @@ int run_filter(const Options &o)
         exit(-1);
     }
     if (rc != 0) die(o.data_graph + ": " + err);
+    if (exact && o.mode == "online" && !g.simple)  // the refinement counts embeddings in simple graphs only (gnnpe_refine)
+        die(o.data_graph + " repeats an edge (duplicate `e` lines): exact -m online (--exact, -l 3) needs a simple graph");
     fputs(g.metadata_text().c_str(), stdout);
     std::vector<uint32_t> sorted_nodes, membership;
     if (gnnpe_host::read_membership(o.dataset_path + "gnn-pe/membership.txt", g.n, o.partition_num, &sorted_nodes,
                                     &membership, &err) != 0)
         die(err);
-    uint32_t n_qv = 0, n_qp = 0, *qv = nullptr, *ql = nullptr, *qd = nullptr;
+    uint32_t n_qv = 0, n_qp = 0, *qv = nullptr, *ql = nullptr, *qd = nullptr, counts[3] = {0, 0, 0};
     double *qp = nullptr;
-    rc = gnnpe_host_query_plan(o.query_graph.c_str(), o.vde_dim, &n_qv, &n_qp, &qv, &ql, &qd, &qp);
+    if (exact) {
+        rc = gnnpe_host_query_plan_exact(o.query_graph.c_str(), o.vde_dim, o.path_length, &n_qv, counts, &qv, &ql, &qd, &qp);
+        n_qp = counts[0];
+    } else {
+        rc = gnnpe_host_query_plan(o.query_graph.c_str(), o.vde_dim, &n_qv, &n_qp, &qv, &ql, &qd, &qp);
+    }
     if (rc == -1) {
         printf("%s\n", gnnpe_last_error());
         exit(-1);
@@ -197,11 +209,29 @@ int run_filter(const Options &o)
     check(gnnpe_set_label_table(ctx, n_labels, o.vde_dim, table.data()), "set_label_table");
     check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
     uint64_t P = 0;
-    check(gnnpe_count_paths(ctx, 2, nullptr, &P), "count_paths");
+    check(gnnpe_count_paths(ctx, o.path_length, nullptr, &P), "count_paths");
     const uint64_t words = ((uint64_t)g.n + 31) / 32;
     std::vector<uint32_t> bitmap((size_t)n_qv * words);
     double ms = 0.0;
-    check(gnnpe_filter_candidates(ctx, n_qp, qv, ql, qd, qp, n_qv, 1e-6 /* custom.h:43 */, bitmap.data(), &ms), "filter");
+    if (exact)
+        check(gnnpe_filter_candidates_exact(ctx, o.path_length, counts, qv, ql, qd, qp, n_qv, 1e-6, bitmap.data(), &ms), "filter");
+    else
+        check(gnnpe_filter_candidates(ctx, n_qp, qv, ql, qd, qp, n_qv, 1e-6 /* custom.h:43 */, bitmap.data(), &ms), "filter");
+    // --timing in exact mode: plan sizes by path width, candidates per query vertex (the reference mode's line is unchanged)
+    std::string exact_json;
+    if (exact && o.timing) {
+        const uint32_t W = o.path_length + 1;
+        exact_json = "\"exact\": true, \"l\": " + std::to_string(o.path_length) + ", \"plan_paths_by_width\": {\"" +
+                     std::to_string(W) + "\": " + std::to_string(counts[0]);
+        if (W != 3) exact_json += ", \"3\": " + std::to_string(counts[1]);
+        exact_json += ", \"1\": " + std::to_string(counts[2]) + "}, \"candidates\": [";
+        for (uint32_t u = 0; u < n_qv; u++) {
+            uint64_t k = 0;
+            for (uint64_t w = 0; w < words; w++) k += __builtin_popcount(bitmap[(size_t)u * words + w]);
+            exact_json += (u ? ", " : "") + std::to_string(k);
+        }
+        exact_json += "], ";
+    }
     if (o.mode == "online") {  // main.cpp:173-181: refinement on the candidate sets, then the answer line
         uint64_t limit = 0xFFFFFFFFull, answers = 0;  // MAX_LIMIT = UINT_MAX (main.cpp:62-69)
         if (o.answers != "MAX") {
@@ -221,9 +251,9 @@ int run_filter(const Options &o)
         gnnpe_destroy(ctx);
         printf("Answer Number: %llu Query Time (ms): %g\n", (unsigned long long)answers, ms + refine_ms);
         if (o.timing)
-            fprintf(stderr, "{\"paths\": %llu, \"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, "
+            fprintf(stderr, "{%s\"paths\": %llu, \"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, "
                             "\"end_to_end_s\": %.3f}\n",
-                    (unsigned long long)P, n_qp, ms, refine_ms, secs(t0, Clock::now()));
+                    exact_json.c_str(), (unsigned long long)P, n_qp, ms, refine_ms, secs(t0, Clock::now()));
         gnnpe_host_free(qv);
         gnnpe_host_free(ql);
         gnnpe_host_free(qd);
@@ -250,8 +280,8 @@ int run_filter(const Options &o)
     gnnpe_host_free(qd);
     gnnpe_host_free(qp);
     if (o.timing)
-        fprintf(stderr, "{\"paths\": %llu, \"query_paths\": %u, \"filter_device_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
-                (unsigned long long)P, n_qp, ms, secs(t0, Clock::now()));
+        fprintf(stderr, "{%s\"paths\": %llu, \"query_paths\": %u, \"filter_device_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
+                exact_json.c_str(), (unsigned long long)P, n_qp, ms, secs(t0, Clock::now()));
     return 0;
 }
 
@@ -267,7 +297,7 @@ int main(int argc, char **argv)
     if (o.path_length != 2 && o.path_length != 3)
         die("-l " + std::to_string(o.path_length) + ": only -l 2 and -l 3 are supported (the reference always enumerates "
             "3-vertex paths and mis-prints them for any other -l)");
-    if (o.path_length == 3)
+    if (o.path_length == 3 && o.mode != "online" && o.mode != "filter")
         fprintf(stderr, "note: -l 3 writes 4-vertex paths; the reference's online binary only reads -l 2 files (SURVEY D4)\n");
     const uint32_t L = o.path_length + 1;
     if (o.answers != "MAX") {  // main.cpp:62-69 (MAX_LIMIT is an online-only knob)
@@ -276,6 +306,7 @@ int main(int argc, char **argv)
     }
     if (o.partition_num == 0) die("-p must be >= 1");
     if (o.mode == "online" || o.mode == "filter") return run_filter(o);
+    if (o.exact) die("--exact applies to -m online and -m filter only");
     if (o.mode != "offline") return 0;  // the reference does nothing for other modes
     if (o.write_index && gnnpe_index_file_bytes(1, L * o.vde_dim, 0) == 0)  // before the graph is read or a GPU is touched
         die("--index: an entry of " + std::to_string(L * o.vde_dim) + " dimensions (" + std::to_string(16ull * L * o.vde_dim + 4) +

@@ -15,11 +15,11 @@ struct PlanPath {
     uint32_t weight;
 };
 
-// dfs_query (custom.h:94-119) for 3-vertex paths
+// dfs_query (custom.h:94-119) for paths of `len` vertices (the reference's: 3)
 void dfs(const StaticGraph &q, std::vector<uint32_t> &path, std::set<std::vector<uint32_t>> &seen,
-         std::vector<std::vector<uint32_t>> &out)
+         std::vector<std::vector<uint32_t>> &out, size_t len = 3)
 {
-    if (path.size() == 3) {
+    if (path.size() == len) {
         if (seen.count(path)) return;
         std::vector<uint32_t> rev(path.rbegin(), path.rend());
         if (seen.count(rev)) return;
@@ -32,7 +32,7 @@ void dfs(const StaticGraph &q, std::vector<uint32_t> &path, std::set<std::vector
         const uint32_t nb = q.neighbors[i];
         if (std::find(path.begin(), path.end(), nb) != path.end()) continue;
         path.push_back(nb);
-        dfs(q, path, seen, out);
+        dfs(q, path, seen, out, len);
         path.pop_back();
     }
 }
@@ -164,6 +164,87 @@ int build_query_plan(const StaticGraph &q, uint32_t e, QueryPlan *out, std::stri
         }
         if (covered.size() == n) break;
     }
+    return 0;
+}
+
+namespace {
+
+// one path (or, at width 1, one vertex) onto a plan: vids, labels, degrees, and the vde / x of every position
+void append_path(const StaticGraph &q, uint32_t e, const uint32_t *v, uint32_t width, const std::vector<double> &x,
+                 const std::vector<double> &vde, QueryPlan *out)
+{
+    for (uint32_t j = 0; j < width; j++) {
+        out->vids.push_back(v[j]);
+        out->labels.push_back(q.labels[v[j]]);
+        out->degrees.push_back(q.degree(v[j]));
+        for (uint32_t k = 0; k < e; k++) {
+            out->pde.push_back(vde[(size_t)v[j] * e + k]);
+            out->pde_label.push_back(x[(size_t)v[j] * e + k]);
+        }
+    }
+}
+
+void reset_plan(QueryPlan *p, uint32_t n, uint32_t L, uint32_t e)
+{
+    *p = QueryPlan();
+    p->n_vertices = n;
+    p->L = L;
+    p->e = e;
+}
+
+}  // namespace
+
+int build_query_plan_exact(const StaticGraph &q, uint32_t e, uint32_t l, ExactPlan *out, std::string *err)
+{
+    if (!out || e == 0 || (l != 2 && l != 3)) {
+        if (err) *err = "build_query_plan_exact: null output / e = 0 / l not 2 or 3";
+        return -2;
+    }
+    const uint32_t n = q.n;
+    QueryPlan ref;  // the reference's plan: the main plan at l = 2, the pool of (b) at l = 3
+    if (build_query_plan(q, e, &ref, err) != 0) return -2;
+    std::vector<double> x, vde;
+    if (query_vde(q, e, &x, &vde, err) != 0) return -2;
+    reset_plan(&out->main, n, l + 1, e);
+    reset_plan(&out->tri, n, 3, e);
+    reset_plan(&out->single, n, 1, e);
+    std::set<uint32_t> covered;
+    // the gen_query_pde rule (custom.h:606-626): a path is taken while it still covers a new vertex, until all are covered
+    auto take = [&](const uint32_t *v, uint32_t width, QueryPlan *dst) {
+        if (covered.size() == n) return;
+        uint32_t hit = 0;
+        for (uint32_t j = 0; j < width; j++) hit += covered.count(v[j]) ? 1u : 0u;
+        if (hit == width) return;
+        for (uint32_t j = 0; j < width; j++) covered.insert(v[j]);
+        append_path(q, e, v, width, x, vde, dst);
+    };
+    if (l == 2) {
+        out->main = ref;
+        for (uint32_t v : ref.vids) covered.insert(v);
+    } else {
+        // (a) every simple 4-vertex path by the dfs_query rule (a path whose reverse was kept is dropped), sorted by weight =
+        // the sum of its degrees, descending.  The reference has no 4-vertex plan, hence no tie order to follow: std::stable_sort
+        // keeps ties in DFS order, so the plan does not depend on the standard library's sort
+        std::vector<std::vector<uint32_t>> all4;
+        std::set<std::vector<uint32_t>> seen;
+        for (uint32_t node = 0; node < n; node++) {
+            std::vector<uint32_t> path = {node};
+            dfs(q, path, seen, all4, 4);
+        }
+        std::vector<uint32_t> weight(all4.size(), 0);
+        std::vector<size_t> order(all4.size());
+        for (size_t i = 0; i < all4.size(); i++) {
+            order[i] = i;
+            for (uint32_t v : all4[i]) weight[i] += q.degree(v);
+        }
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weight[a] > weight[b]; });
+        for (size_t i : order) take(all4[i].data(), 4, &out->main);
+        // (b) what no 4-vertex path covers, from the reference's 3-vertex plan in its order
+        for (uint32_t i = 0; i < ref.n_paths(); i++) take(&ref.vids[(size_t)i * 3], 3, &out->tri);
+    }
+    // (c) a query vertex on no plan path (no 3- or 4-vertex path through it, e.g. a single-edge query) is tested alone
+    for (uint32_t u = 0; u < n; u++)
+        if (!covered.count(u)) append_path(q, e, &u, 1, x, vde, &out->single);
     return 0;
 }
 

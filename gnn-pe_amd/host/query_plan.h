@@ -44,4 +44,18 @@ int build_pge_query_groups(const StaticGraph &query, uint32_t e, PgeQueryGroups 
 // 0 = ok; <0 with *err set
 int build_query_plan(const StaticGraph &query, uint32_t e, QueryPlan *out, std::string *err);
 
+// Exact mode: the plan of the orientation-complete filter, where a query vertex's candidate set holds every
+// data vertex some embedding maps it to.  Three parts, taken in this order by the gen_query_pde rule (a path is taken while
+// it covers a vertex not covered yet):
+//   main    l = 2: the reference's plan (build_query_plan), unchanged.  l = 3: every simple 4-vertex query path (dfs_query
+//           rule at depth 3), sorted by degree weight, descending, with std::stable_sort
+//   tri     l = 3 only: for the vertices no 4-vertex path covers, paths of the reference's 3-vertex plan, in its order
+//   single  the vertices still uncovered, width 1: label, degree and vde (in `pde`), tested vertex by vertex
+// The plan lists each path in one orientation; the filter (gnnpe_filter_candidates_exact) adds the reverses.
+struct ExactPlan {
+    QueryPlan main, tri, single;
+};
+// l = 2 or 3.  0 = ok; <0 with *err set
+int build_query_plan_exact(const StaticGraph &query, uint32_t e, uint32_t l, ExactPlan *out, std::string *err);
+
 }  // namespace gnnpe_host

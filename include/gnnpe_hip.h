@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GNNPE_ABI_VERSION 7
+#define GNNPE_ABI_VERSION 8
 
 #define GNNPE_OK 0
 #define GNNPE_ERR_ARG (-1)     /* bad argument / call order */
@@ -352,6 +352,31 @@ int gnnpe_set_degrees(gnnpe_ctx *ctx, const uint32_t *host_degrees);
 int gnnpe_filter_candidates(gnnpe_ctx *ctx, uint32_t n_paths, const uint32_t *q_vids, const uint32_t *q_labels,
                             const uint32_t *q_degrees, const double *q_pde, uint32_t n_query_vertices, double epsilon,
                             uint32_t *host_bitmap, double *device_ms);
+
+/* ---- exact online queries (INTEGRATION.md "Exact mode") ---------------------------------------------------------------- */
+/* The reference keeps every path in one orientation on both sides and compares position by position, so its candidate sets can
+ * miss the image of a query vertex.  Exact mode tests every plan path in both orientations: for every embedding f, f(u) is in
+ * the candidate set of u, and the refinement on these sets counts every embedding.  l = 3 (4-vertex plan paths) is exact only.
+ * Query side (host): the exact plan, three parts concatenated in every output array --
+ *   counts[0] paths of l + 1 vertices: l = 2 the reference's plan (gnnpe_host_query_plan); l = 3 every simple 4-vertex query
+ *             path (dfs_query at depth 3), by degree weight descending (stable), taken while it covers a new vertex;
+ *   counts[1] l = 3 only: 3-vertex paths of the reference's plan, in its order, for the vertices no 4-vertex path covers;
+ *   counts[2] the query vertices still uncovered, one entry each (tested alone: label, degree, vde).
+ * vids / labels / degrees: (l + 1) counts[0] + 3 counts[1] + counts[2] uint32; pde: e doubles per entry (the vde of the entry's
+ * query vertex).  Each path is listed once; the filter adds the reverses.  malloc'ed (gnnpe_host_free). */
+int gnnpe_host_query_plan_exact(const char *query_graph_path, uint32_t e, uint32_t l, uint32_t *n_query_vertices,
+                                uint32_t counts[3], uint32_t **vids, uint32_t **labels, uint32_t **degrees, double **pde);
+/* Data side (device): the plan of gnnpe_host_query_plan_exact, every path doubled with its reverse inside the library (at most
+ * 512 paths per width after doubling, else GNNPE_ERR_UNSUPPORTED); the leaf test of gnnpe_filter_candidates over the
+ * enumeration of the context's slab for each width, and label / degree / vde for the single vertices (the slab's own
+ * vertices).  Same requirements as gnnpe_filter_candidates.  A slab-only context at l = 3 also needs the rows two hops out
+ * (gnnpe_halo_need after the first gnnpe_rows_append) AND the vde of every vertex three hops out -- the fourth vertex of a
+ * path; gnnpe_vde computes it for the rows the context holds only, so install the all-gathered table (gnnpe_vde_unpack_all, as
+ * dist.py does) or hold those rows too.  Nothing checks this: a missing vde reads as zeros and drops candidates.
+ * host_bitmap: the layout gnnpe_refine takes. */
+int gnnpe_filter_candidates_exact(gnnpe_ctx *ctx, uint32_t l, const uint32_t counts[3], const uint32_t *q_vids,
+                                  const uint32_t *q_labels, const uint32_t *q_degrees, const double *q_pde,
+                                  uint32_t n_query_vertices, double epsilon, uint32_t *host_bitmap, double *device_ms);
 
 /* The refinement half of the reference's online step (custom.h:634-932) is outside SURVEY section 8's scope (frozen since round 1)
  * and ships in a library of its own since round 6: include/gnnpe_online.h, libgnnpe_online.so (gnnpe_refine, gnnpe_host_refine). */
