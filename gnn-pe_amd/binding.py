@@ -124,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 8  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 9  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 _lib = None
 
 
@@ -138,6 +138,8 @@ ONLINE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gnnpe_onli
 ONLINE_SIGNATURES = {
     "gnnpe_host_refine": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
     "gnnpe_refine": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _f64p]),
+    "gnnpe_host_refine_sets": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
+    "gnnpe_refine_sets": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _u32p, C.c_uint64, _f64p]),
 }
 _online = None
 
@@ -357,6 +359,20 @@ def host_refine(g, query_path, bitmap, limit=0xFFFFFFFF):
     bm = _np(bitmap, np.uint32)
     rc = load_online().gnnpe_host_refine(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
                                _ptr(bm, _u32p), int(limit), C.byref(out))
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return out.value
+
+
+def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF):
+    """Set-restricted refinement on the host (include/gnnpe_online.h, R(C, limit)): the embeddings whose every image lies in its
+    query vertex's set, counted up to `limit`."""
+    lib = load()
+    out = C.c_uint64()
+    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm = _np(bitmap, np.uint32)
+    rc = load_online().gnnpe_host_refine_sets(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
+                                              _ptr(bm, _u32p), int(limit), C.byref(out))
     if rc:
         raise GnnpeError(lib.gnnpe_last_error().decode())
     return out.value
@@ -720,6 +736,23 @@ class Engine:
         bm = _np(bitmap, np.uint32)
         self._ck(load_online().gnnpe_refine(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out), C.byref(ms)))
         return out.value, ms.value
+
+    def refine_sets(self, query_path, bitmap, limit=0xFFFFFFFF, matches_cap=0):
+        """Set-restricted refinement on the device (gnnpe_refine_sets): (answers, device ms), or with matches_cap > 0
+        (answers, device ms, matches) -- matches[k, u] = image of query vertex u in the k-th embedding kept,
+        min(answers, matches_cap) rows."""
+        out, ms = C.c_uint64(), C.c_double()
+        bm = _np(bitmap, np.uint32)
+        cap = min(int(matches_cap), int(limit))
+        rows = None
+        if matches_cap > 0:
+            nq = bm.shape[0] if bm.ndim == 2 else bm.size // ((self.n + 31) // 32)
+            rows = np.zeros((max(cap, 1), nq), np.uint32)
+        self._ck(load_online().gnnpe_refine_sets(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out),
+                                                 _ptr(rows, _u32p) if rows is not None else None, cap, C.byref(ms)))
+        if rows is None:
+            return out.value, ms.value
+        return out.value, ms.value, rows[:min(out.value, cap)]
 
     def path_partitions_device(self, begin, end, dev_part):
         self._ck(self.lib.gnnpe_path_partitions_device(self.ctx, begin, end, _dev(dev_part)))

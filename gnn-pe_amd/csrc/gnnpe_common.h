@@ -245,6 +245,7 @@ struct gnnpe_ctx {
     uint64_t n_units = 0;
     gnnpe::DevBuf deg_all;          // online filter on a slab: degree of EVERY vertex (gnnpe_set_degrees)
     gnnpe::DevBuf q_plan, q_bitmap, q_work, q_tmp;  // online side: grow-only, so that a query allocates nothing
+    gnnpe::DevBuf q_matches;  // ... the embeddings gnnpe_refine_sets hands back (matches_cap x n_qv uint32)
     bool have_deg_all = false;
     bool vkey_valid = false;
     uint32_t vkey_zb = 0, vkey_lb = 0, vkey_sbits = 32;  // sbits 32 = wide (64-bit) table only

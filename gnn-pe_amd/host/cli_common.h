@@ -35,6 +35,9 @@ struct Options {
     bool allow_large = false, timing = false, sidecars = false, write_index = false;
     bool exact = false;   // -m online / filter at -l 2: the orientation-complete filter (always on at -l 3; refused in other
                           // modes; INTEGRATION.md "Exact mode")
+    // -m online with complete sets (--exact, -l 3): "start" = the frozen refinement (gnnpe_refine), "sets" = the set-restricted
+    // one (gnnpe_refine_sets); --matches FILE (needs sets) writes the embeddings, one per line
+    std::string refine = "start", matches_file;
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
     std::string transport = "rccl";  // --gpus N > 1: "rccl" (ncclSend/ncclRecv over xGMI) or "copy" (device-to-device copies)
@@ -110,7 +113,8 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "-h" || a == "--help") {
             printf("%s -f <dataset dir/> -d <data.graph> -m offline -p <partitions> [-l 2] [-e 2]\n"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
-                   "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n",
+                   "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
+                   "           [--refine start|sets] [--matches FILE]\n",
                    tool, tool);
             exit(0);
         }
@@ -125,6 +129,13 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             o.transport = argv[++i];
             if (o.transport != "rccl" && o.transport != "copy") die("--transport must be rccl or copy");
             o.transport_explicit = true;
+            continue;
+        }
+        if (a == "--refine" || a == "--matches") {
+            if (i + 1 >= argc) die(a + " needs a value");
+            if (a == "--matches") { o.matches_file = argv[++i]; continue; }
+            o.refine = argv[++i];
+            if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;
         }
         if (a == "--allow-large") { o.allow_large = true; continue; }

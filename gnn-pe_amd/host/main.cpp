@@ -164,7 +164,8 @@ struct Device {
 // all_paths.txt, no index.dat: only the data graph and membership.txt (any order gives the same candidate sets).
 // Writes <f>gnn-pe/candidates.bin: uint32 n_query_vertices; per query vertex uint32 count + ascending data vertex
 // ids -- the reference's candidate_set, ready for its refinement (main.cpp:176-179).  -m online goes on with the
-// refinement on the device (gnnpe_refine) and prints the reference's answer line instead of writing the file.
+// refinement on the device (gnnpe_refine; with --refine sets, where the sets are complete, gnnpe_refine_sets, which can
+// also hand back the embeddings: --matches) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -247,10 +248,38 @@ int run_filter(const Options &o)
         if (!online) die(std::string("-m online needs libgnnpe_online.so beside ") + o.tool + ": " + dlerror());
         refine_fn refine = (refine_fn)dlsym(online, "gnnpe_refine");
         if (!refine) die("libgnnpe_online.so does not export gnnpe_refine");
-        check(refine(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, &refine_ms), "refine");
+        const bool sets = o.refine == "sets";
+        uint64_t n_written = 0;
+        if (sets) {
+            // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
+            typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t *, uint32_t *, uint64_t,
+                                          double *);
+            refine_sets_fn refine_sets = (refine_sets_fn)dlsym(online, "gnnpe_refine_sets");
+            if (!refine_sets) die("libgnnpe_online.so does not export gnnpe_refine_sets");
+            const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
+            std::vector<uint32_t> rows((size_t)cap * n_qv);
+            check(refine_sets(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, cap ? rows.data() : nullptr, cap,
+                              &refine_ms), "refine_sets");
+            if (!o.matches_file.empty()) {
+                FILE *mf = fopen(o.matches_file.c_str(), "w");
+                if (!mf) die("cannot write " + o.matches_file);
+                n_written = std::min(answers, cap);
+                for (uint64_t k = 0; k < n_written; k++)
+                    for (uint32_t u = 0; u < n_qv; u++)
+                        fprintf(mf, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
+                if (fclose(mf) != 0) die("write failed on " + o.matches_file);
+            }
+        } else {
+            check(refine(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, &refine_ms), "refine");
+        }
         gnnpe_destroy(ctx);
         printf("Answer Number: %llu Query Time (ms): %g\n", (unsigned long long)answers, ms + refine_ms);
-        if (o.timing)
+        if (o.timing && sets)
+            fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"paths\": %llu, \"query_paths\": %u, "
+                            "\"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
+                    exact_json.c_str(), (unsigned long long)n_written, (unsigned long long)P, n_qp, ms, refine_ms,
+                    secs(t0, Clock::now()));
+        else if (o.timing)
             fprintf(stderr, "{%s\"paths\": %llu, \"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, "
                             "\"end_to_end_s\": %.3f}\n",
                     exact_json.c_str(), (unsigned long long)P, n_qp, ms, refine_ms, secs(t0, Clock::now()));
@@ -305,6 +334,12 @@ int main(int argc, char **argv)
         if (!parse_u32(o.answers, &lim)) die("-n must be MAX or an integer");
     }
     if (o.partition_num == 0) die("-p must be >= 1");
+    // --refine sets counts inside EVERY candidate set, so it needs complete sets (INTEGRATION.md "Exact mode")
+    if (!o.matches_file.empty() && o.refine != "sets") die("--matches needs --refine sets");
+    if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
+    if (o.refine == "sets" && !(o.exact || o.path_length == 3))
+        die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "
+            "embeddings, and only the start vertex's set may restrict the search there)");
     if (o.mode == "online" || o.mode == "filter") return run_filter(o);
     if (o.exact) die("--exact applies to -m online and -m filter only");
     if (o.mode != "offline") return 0;  // the reference does nothing for other modes

@@ -1,0 +1,93 @@
+// refine_sets.cpp -- see refine_sets.h
+#include "refine_sets.h"
+
+#include <algorithm>
+#include <vector>
+
+#include "refine.h"
+
+namespace gnnpe_host {
+
+namespace {
+
+struct SetSearch {
+    const StaticGraph &g, &q;
+    const uint32_t *bitmap;
+    uint64_t words;
+    std::vector<uint32_t> order, pivot;       // matching order; an earlier neighbour of order[i] for i >= 1
+    std::vector<std::vector<uint32_t>> back;  // the other earlier neighbours of order[i]
+    std::vector<uint32_t> image;              // query vertex -> data vertex
+    std::vector<uint8_t> used;                // data vertex taken
+    uint64_t count = 0, limit;
+
+    bool in_set(uint32_t u, uint32_t v) const { return (bitmap[(size_t)u * words + (v >> 5)] >> (v & 31)) & 1u; }
+    bool fits(uint32_t u, uint32_t v) const
+    {
+        return in_set(u, v) && !used[v] && g.labels[v] == q.labels[u] && g.degree(v) >= q.degree(u);
+    }
+    bool edge(uint32_t a, uint32_t b) const
+    {
+        if (g.degree(b) < g.degree(a)) std::swap(a, b);  // the shorter row
+        return std::binary_search(g.neighbors.begin() + g.offsets[a], g.neighbors.begin() + g.offsets[a + 1], b);
+    }
+    void extend(size_t depth)
+    {
+        if (depth == order.size()) {
+            count++;
+            return;
+        }
+        const uint32_t u = order[depth], p = image[pivot[depth]];
+        for (uint32_t i = g.offsets[p]; i < g.offsets[p + 1] && count < limit; i++) {
+            const uint32_t v = g.neighbors[i];
+            if (!fits(u, v)) continue;
+            bool ok = true;
+            for (uint32_t w : back[depth])
+                if (!edge(v, image[w])) {
+                    ok = false;
+                    break;
+                }
+            if (!ok) continue;
+            image[u] = v;
+            used[v] = 1;
+            extend(depth + 1);
+            used[v] = 0;
+        }
+    }
+};
+
+}  // namespace
+
+int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                      uint64_t limit, uint64_t *answers, std::string *err)
+{
+    const uint32_t nq = query.n;
+    if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
+        if (err) *err = "refine_sets_count: one bitmap row of ceil(n / 32) words per query vertex expected";
+        return -2;
+    }
+    *answers = 0;
+    if (nq == 0) return 0;
+    std::vector<uint64_t> cnt(nq, 0);
+    for (uint32_t u = 0; u < nq; u++)
+        for (uint64_t w = 0; w < words; w++) cnt[u] += (uint64_t)__builtin_popcount(bitmap[(size_t)u * words + w]);
+    MatchOrder mo;
+    if (build_match_order(query, cnt, &mo, err) != 0) return -2;  // (a disconnected query is refused whatever the limit)
+    if (limit == 0) return 0;
+    SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<uint32_t>(nq, 0),
+                std::vector<uint8_t>(data.n, 0), 0, limit};
+    for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
+    const uint32_t start = mo.order[0];
+    for (uint64_t w = 0; w < words && s.count < limit; w++)
+        for (uint32_t bits = bitmap[(size_t)start * words + w]; bits && s.count < limit; bits &= bits - 1) {
+            const uint32_t v = (uint32_t)(w * 32 + __builtin_ctz(bits));
+            if (v >= data.n || !s.fits(start, v)) continue;
+            s.image[start] = v;
+            s.used[v] = 1;
+            s.extend(1);
+            s.used[v] = 0;
+        }
+    *answers = std::min(s.count, limit);
+    return 0;
+}
+
+}  // namespace gnnpe_host

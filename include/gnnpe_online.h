@@ -1,8 +1,9 @@
 /* gnnpe_online.h -- C-ABI of libgnnpe_online.so: the REFINEMENT half of the reference's online step (custom.h:634-932).
  *
- * Outside SURVEY section 8's scope: built in round 1 so that `gnnpe_main -m online` can print the reference's answer line, frozen
- * since, and since round 6 kept out of libgnnpe_hip.so -- the offline hot path and its (f) rows link and load
- * without it.  libgnnpe_online.so links against libgnnpe_hip.so (contexts, error text); `gnnpe_main` dlopen()s it for -m online
+ * gnnpe_host_refine / gnnpe_refine restate the reference (start vertex only) and are frozen: built in round 1 so that
+ * `gnnpe_main -m online` can print the reference's answer line.  gnnpe_host_refine_sets / gnnpe_refine_sets (below) restrict
+ * every query vertex to its set, for exact mode.  The library is kept out of libgnnpe_hip.so since round 6:
+ * the offline hot path and its (f) rows link and load without it.  libgnnpe_online.so links against libgnnpe_hip.so (contexts, error text); `gnnpe_main` dlopen()s it for -m online
  * only.  Same conventions as gnnpe_hip.h: 0 = GNNPE_OK, gnnpe_last_error() for the text.
  */
 #ifndef GNNPE_ONLINE_H
@@ -26,6 +27,31 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
  * Needs the whole graph on the device (gnnpe_load_csr); query graphs of up to 32 vertices.  device_ms may be NULL. */
 int gnnpe_refine(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                  uint64_t *answers, double *device_ms);
+
+/* ---- ABI version 9: the set-restricted refinement ------------------------------------------------------------------
+ * R(C, limit) = min(limit, number of maps f from query vertices to data vertices that are injective, keep labels, have
+ * query degree <= data degree, map every query edge onto a data edge, AND have f(u) in C(u) for EVERY query vertex u),
+ * with C the bitmap layout of gnnpe_filter_candidates (n_query_vertices x ceil(n / 32) uint32).
+ *   - If every C(u) is complete -- exact-mode filter output (gnnpe_filter_candidates_exact), or a label/degree-only
+ *     bitmap -- R(C, limit) equals what the two functions above return on the same bitmap, and equals the true count.
+ *   - For arbitrary C it is the count of the embeddings that lie inside the sets.
+ * The reference-mode filter's sets are NOT complete: there the functions above (start vertex only) give the reference's
+ * answer and these give a smaller one.  The count does not depend on the matching order. */
+
+/* Host form: plain backtracking that applies the set test at every level.  Arguments as gnnpe_host_refine. */
+int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                           const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers);
+
+/* Device form: one wave per search subtree, the whole wave on every adjacency row (csrc/gnnpe_refine_sets.hip).
+ * Requirements as gnnpe_refine: whole simple graph on the device, connected query graph of up to 32 vertices; a context
+ * in the multigraph state is refused.  *answers is clamped to limit; a count far above the limit costs no more time than
+ * the limit does.  matches may be NULL; otherwise it is a host array of matches_cap x n_query_vertices uint32, and on
+ * return its first min(*answers, matches_cap) rows are pairwise different embeddings, row k column u = f_k(u) (column =
+ * query vertex id as in the query file).  Which embeddings are kept when there are more than matches_cap, and their
+ * order, are unspecified; matches_cap > limit is treated as limit.  device_ms (may be NULL) covers the kernels, not the
+ * uploads of the bitmap and the start candidates, as gnnpe_refine's does. */
+int gnnpe_refine_sets(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                      uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
 
 #ifdef __cplusplus
 }
