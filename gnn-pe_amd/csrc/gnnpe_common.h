@@ -227,6 +227,29 @@ struct gnnpe_ctx {
     // waves, 2 = output tiles, 3 = ticket waves, 4 = start-vertex waves at three workgroups per CU (include/gnnpe_hip.h)
     int emit_shape = 0;
     bool ranked_vde_valid = false;  // the ranked records carry the current vde table
+    // The STRUCTURE of a ranked count -- the pair records, the id words and the order of the neighbour records, the start records,
+    // the total in eoff[n_edges], the hub rows' pairs -- depends on the held rows, the order, the membership, the slab and the
+    // record layout, not on the embeddings.  ranked_struct_valid: the last full ranked count built it and nothing it depends on
+    // has changed since (every setter / loader / other kind of count clears it); ranked_struct_key: the buffers it lives in and the
+    // generations it was built for, compared again before it is reused (a grow-only buffer that moved has lost its contents).
+    // While it holds, a count only refreshes the vde doubles of the row blocks (k_rows_refresh).
+    bool ranked_struct_valid = false;
+    struct RankedStructKey {
+        const void *rpairs = nullptr, *rrecs = nullptr, *srec = nullptr, *eoff = nullptr, *rpos = nullptr;
+        uint64_t slab_struct_gen = 0, rblock_gen = 0, n_edges = 0;
+        uint32_t e = 0, n_held = 0;
+        bool packed = false;
+        bool operator==(const RankedStructKey &o) const
+        {
+            return rpairs == o.rpairs && rrecs == o.rrecs && srec == o.srec && eoff == o.eoff && rpos == o.rpos &&
+                   slab_struct_gen == o.slab_struct_gen && rblock_gen == o.rblock_gen && n_edges == o.n_edges && e == o.e &&
+                   n_held == o.n_held && packed == o.packed;
+        }
+    } ranked_struct_key;
+    bool ranked_reused = false;  // what the last build_ranked did: refreshed the embeddings of a valid structure / built it
+    gnnpe::DevBuf rpos;  // position of every held adjacency entry's record inside its row block (rows of degree <= 64): structure
+    uint32_t *heads_words = nullptr;  // set by the count around build_ranked: the emit kernel's ticket heads, zeroed by the refresh kernel
+    uint32_t n_heads_words = 0;
     // round 6, launches folded into their neighbours: k_vde wrote the count kernel's per-vertex records for the slab structure of
     // generation vinfo_gen (k_pack_vinfo is skipped while that is current); k_start_scan left the emit kernel's ticket heads zero;
     // the zero sentinel behind the pair records is in place for this many pairs
@@ -253,7 +276,7 @@ struct gnnpe_ctx {
     // row blocks of the ranked records: first 128-byte unit of every held row's block, total units; depends on the held
     // rows and the record size (e, packed ids) only, so it is laid out when one of them changes
     gnnpe::DevBuf rblock;
-    uint64_t rblock_units = 0;
+    uint64_t rblock_units = 0, rblock_gen = 0;  // rblock_gen: counts the layouts (ensure_row_blocks)
     bool rblock_valid = false;
     uint32_t rblock_e = 0;
     gnnpe::DevBuf slab_bounds;  // gnnpe_vde_unpack_all: the ranks' slab bounds on the device

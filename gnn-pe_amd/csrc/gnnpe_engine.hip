@@ -364,6 +364,7 @@ static void invalidate_derived(gnnpe_ctx *c)
     c->nbr_vde_valid = false;
     c->counted = false;
     c->slab_struct_valid = false;
+    c->ranked_struct_valid = false;
     c->labels_checked = false;
 }
 
@@ -393,6 +394,7 @@ static int finish_rows(gnnpe_ctx *c, uint64_t n_new, const uint32_t *dev_new_row
     // hub rows over everything held
     const uint32_t *held = c->rows_identity ? nullptr : c->held.as<uint32_t>();
     c->rblock_valid = false;
+    c->ranked_struct_valid = false;  // (the held rows changed: the row blocks, the pairs and the hub list are laid out again)
     c->n_hub = 0;
     c->hub_entries = 0;
     if (c->n_held) {
@@ -588,6 +590,7 @@ int gnnpe_set_multigraph_rows(gnnpe_ctx *c, uint32_t n_rows, const uint64_t *row
     GNNPE_HIP_TRY(hipGetLastError());
     GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
     c->multigraph = true;
+    c->ranked_struct_valid = false;  // (the simple rows stay what they were; a loader call all the same)
     c->have_vde = false;
     c->nbr_vde_valid = false;
     c->have_pge = false;
@@ -626,6 +629,7 @@ int gnnpe_set_order(gnnpe_ctx *c, const uint32_t *sorted_nodes, const uint32_t *
     c->have_order = true;
     c->counted = false;
     c->slab_struct_valid = false;
+    c->ranked_struct_valid = false;  // (ranks, membership and p are in the pair and start records)
     return GNNPE_OK;
 }
 
@@ -643,6 +647,7 @@ int gnnpe_set_slab(gnnpe_ctx *c, uint32_t begin, uint32_t end)
     c->slab_set = true;
     c->counted = false;
     c->slab_struct_valid = false;
+    c->ranked_struct_valid = false;
     return GNNPE_OK;
 }
 
@@ -673,6 +678,9 @@ int gnnpe_set_label_table(gnnpe_ctx *c, uint32_t n_labels, uint32_t e, const dou
         GNNPE_HIP_TRY(hipMemcpyAsync(c->xsorted.p, xs.data(), xs.size() * 8, hipMemcpyHostToDevice, c->stream));
     }
     GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    // a table of the width the records were laid out for keeps the structure of the last count (values are payload); another
+    // width is another record size (before any table a count lays out records of width 2)
+    if (e != (c->have_table ? c->e : 2u)) c->ranked_struct_valid = false;
     c->n_labels = n_labels;
     c->e = e;
     c->have_table = true;
@@ -933,11 +941,32 @@ static int ensure_row_blocks(gnnpe_ctx *c, uint32_t e)
     c->rblock_units = (uint32_t)tot;
     c->rblock_valid = true;
     c->rblock_e = e;
+    c->rblock_gen++;
+    c->ranked_struct_valid = false;
     return GNNPE_OK;
 }
 
+// what the structure of a ranked count lives in and was built for (gnnpe_common.h: ranked_struct_valid)
+static gnnpe_ctx::RankedStructKey ranked_struct_key(const gnnpe_ctx *c, uint64_t ne, uint32_t e)
+{
+    gnnpe_ctx::RankedStructKey k;
+    k.rpairs = c->rpairs.p;
+    k.rrecs = c->rrecs.p;
+    k.srec = c->srec.p;
+    k.eoff = c->eoff.p;
+    k.rpos = c->rpos.p;
+    k.slab_struct_gen = c->slab_struct_gen;
+    k.rblock_gen = c->rblock_gen;
+    k.n_edges = ne;
+    k.e = e;
+    k.n_held = c->n_held;
+    k.packed = packed_ids(c);
+    return k;
+}
+
 // row blocks {vde[b] | records by descending rank} + per-pair {block, count, G}; hub rows: id-ordered records, counts
-// from a per-row sort of the ranks
+// from a per-row sort of the ranks.  Where the structure of the last full count still holds (c->ranked_reused on return), only the
+// embeddings in the row blocks are written again -- or nothing, when they are current or there are none yet.
 static int build_ranked(gnnpe_ctx *c, uint64_t ne)
 {
     const uint32_t e = c->have_table ? c->e : 2;
@@ -945,18 +974,29 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
     int rc;
     if ((rc = ensure_row_blocks(c, e))) return rc;
     if ((rc = c->rpairs.reserve((ne + 1) * sizeof(RankedPair))) || (rc = c->rrecs.reserve((c->rblock_units + 1) * kRowAlign)) ||
-        (rc = c->vinfo.reserve(((size_t)c->n + 1) * GNNPE_VINFO_STRIDE(e) * 8)))
+        (rc = c->vinfo.reserve(((size_t)c->n + 1) * GNNPE_VINFO_STRIDE(e) * 8)) || (rc = c->rpos.reserve(c->nbr_used + 1)))
         return rc;
-    // pairs whose middle row is not on the device stay empty; with the whole graph loaded every pair is written by
-    // the row kernels and only the scan's sentinel entry needs clearing
-    if (!c->rows_identity) {
-        GNNPE_HIP_TRY(hipMemsetAsync(c->rpairs.p, 0, (ne + 1) * sizeof(RankedPair), c->stream));
-    } else if (c->rpairs_sentinel_buf != c->rpairs.p || c->rpairs_sentinel_at != ne) {  // (nobody writes slot ne: once per buffer and pair count)
-        GNNPE_HIP_TRY(hipMemsetAsync(c->rpairs.as<RankedPair>() + ne, 0, sizeof(RankedPair), c->stream));
-        c->rpairs_sentinel_buf = c->rpairs.p;
-        c->rpairs_sentinel_at = ne;
+    // (after the reserves: a buffer that moved has another address than the key's.  GNNPE_COUNT_REUSE=0 in a diagnostic build
+    // takes the full count every time: the same-process A/B of scripts/count_reuse_ab.py)
+    const bool reuse = c->ranked_struct_valid && c->ranked_struct_key == ranked_struct_key(c, ne, e) &&
+                       diag_int("GNNPE_COUNT_REUSE", 1) != 0;
+    c->ranked_reused = reuse;
+    if (!reuse) c->ranked_struct_valid = false;  // (set again by the count that finishes the structure: count_paths_impl)
+    if (c->sw.debug) fprintf(stderr, "[count] structure: %s\n", reuse ? "reused" : "built");
+    // a valid structure whose records carry the current embeddings, or no embeddings to carry: nothing to launch
+    const bool launch = !reuse || (c->have_vde && !c->ranked_vde_valid);
+    if (!reuse) {
+        // pairs whose middle row is not on the device stay empty; with the whole graph loaded every pair is written by
+        // the row kernels and only the scan's sentinel entry needs clearing
+        if (!c->rows_identity) {
+            GNNPE_HIP_TRY(hipMemsetAsync(c->rpairs.p, 0, (ne + 1) * sizeof(RankedPair), c->stream));
+        } else if (c->rpairs_sentinel_buf != c->rpairs.p || c->rpairs_sentinel_at != ne) {  // (nobody writes slot ne: once per buffer and pair count)
+            GNNPE_HIP_TRY(hipMemsetAsync(c->rpairs.as<RankedPair>() + ne, 0, sizeof(RankedPair), c->stream));
+            c->rpairs_sentinel_buf = c->rpairs.p;
+            c->rpairs_sentinel_at = ne;
+        }
+        if (!c->rows_identity) c->rpairs_sentinel_buf = nullptr;
     }
-    if (!c->rows_identity) c->rpairs_sentinel_buf = nullptr;
     if (c->n_held) {
         const uint32_t *held = c->rows_identity ? nullptr : c->held.as<uint32_t>();
         const double *vde = c->have_vde ? c->vde.as<double>() : nullptr;
@@ -972,7 +1012,13 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
         // k_start_scan's status words + ticket are zeroed by the row kernel (count_paths passes them through the context)
         uint32_t *clear_words = c->clear_words;
         const uint32_t n_clear = c->n_clear;
-        c->clear_done = clear_words != nullptr;
+        c->clear_done = clear_words != nullptr && !reuse;
+        // ... and on a refresh the emit kernel's ticket heads, which k_start_scan zeroes in a full count, by the refresh kernel
+        uint32_t *heads_words = c->heads_words;
+        const uint32_t n_heads_words = c->n_heads_words;
+        if (reuse && launch && heads_words) c->heads_clean = true;
+        const dim3 gridf((unsigned)std::min<uint64_t>(((uint64_t)c->n_held + 15) / 16, 1u << 30));
+        [[maybe_unused]] const bool refresh_from_blocks = diag_int("GNNPE_REFRESH_SHAPE", 0) == 1;
         int rows_ilp = (int)diag_int("GNNPE_ROWS_ILP", 4);  // (diagnostic builds: 1 | 2 | 8 for the A/B of DESIGN 3.2)
         if (rows_ilp != 1 && rows_ilp != 2 && rows_ilp != 8) rows_ilp = 4;
         const dim3 gridk((unsigned)std::min<uint64_t>(((uint64_t)c->n_held + 4 * rows_ilp - 1) / (4 * rows_ilp), 1u << 30));
@@ -980,8 +1026,13 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
     hipLaunchKernelGGL((k_rows_rank_multi<EE, PK, KK>), gridk, block, 0, c->stream, c->n_held, held,                \
                        c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),              \
                        c->vinfo.as<double>(), c->revpos.as<uint32_t>(), c->rblock.as<uint32_t>(),                   \
-                       c->rrecs.as<char>(), c->rpairs.as<RankedPair>(), clear_words, n_clear,                       \
+                       c->rrecs.as<char>(), c->rpairs.as<RankedPair>(), c->rpos.as<uint8_t>(), clear_words, n_clear, \
                        (uint32_t)diag_int("GNNPE_ROWS_PAIR8", 0))
+#define GNNPE_RFS(EE, PK, FB)                                                                                       \
+    hipLaunchKernelGGL((k_rows_refresh<EE, PK, 4, FB>), gridf, block, 0, c->stream, c->n_held, held,                \
+                       c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),              \
+                       c->vinfo.as<double>(), c->rpos.as<uint8_t>(), c->rblock.as<uint32_t>(), c->rrecs.as<char>(), \
+                       heads_words, n_heads_words)
 #ifdef GNNPE_DIAG
 #define GNNPE_RRK(EE, PK)                                                                                           \
     do {                                                                                                            \
@@ -993,11 +1044,16 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
             hipLaunchKernelGGL((k_rows_rank<EE, PK>), grid, block, 0, c->stream, c->n_held, held,                   \
                                c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),      \
                                c->vinfo.as<double>(), c->revpos.as<uint32_t>(), c->rblock.as<uint32_t>(),           \
-                               c->rrecs.as<char>(), c->rpairs.as<RankedPair>());                                    \
+                               c->rrecs.as<char>(), c->rpairs.as<RankedPair>(), c->rpos.as<uint8_t>());             \
         }                                                                                                           \
+    } while (0)
+#define GNNPE_RF(EE, PK)                                                                                            \
+    do {                                                                                                            \
+        if (refresh_from_blocks) GNNPE_RFS(EE, PK, true); else GNNPE_RFS(EE, PK, false);                            \
     } while (0)
 #else
 #define GNNPE_RRK(EE, PK) GNNPE_RRM(EE, PK, 4)
+#define GNNPE_RF(EE, PK) GNNPE_RFS(EE, PK, false)
 #endif
 #define GNNPE_RR(EE)                                                                                               \
     do {                                                                                                           \
@@ -1005,16 +1061,24 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
             hipLaunchKernelGGL((k_pack_vinfo<EE>), dim3(grid_for(c->n)), block, 0, c->stream, c->n, vde,            \
                                c->rank.as<uint32_t>(), c->slab_begin, c->slab_end, c->poffs.as<uint32_t>(),         \
                                c->vinfo.as<double>());                                                              \
-        if (packed) GNNPE_RRK(EE, true); else GNNPE_RRK(EE, false);                                                 \
+        if (reuse) {                                                                                               \
+            if (packed) GNNPE_RF(EE, true); else GNNPE_RF(EE, false);                                               \
+        } else {                                                                                                   \
+            if (packed) GNNPE_RRK(EE, true); else GNNPE_RRK(EE, false);                                             \
+        }                                                                                                          \
     } while (0)
-        GNNPE_BY_E(e, GNNPE_RR)
+        if (launch) {
+            GNNPE_BY_E(e, GNNPE_RR)
+        }
 #undef GNNPE_RR
 #undef GNNPE_RRK
+#undef GNNPE_RF
+#undef GNNPE_RFS
 #undef GNNPE_RRM
         // diagnostic launches beside the real one (GNNPE_ROWS_PROBE, scripts/count_ab.py): pieces of the kernel on their own,
         // into scratch copies of its outputs; whole graph on one device, e = 2, packed ids only
 #ifdef GNNPE_DIAG
-        if (const int mode = (int)diag_int("GNNPE_ROWS_PROBE", 0)) {
+        if (const int mode = reuse ? 0 : (int)diag_int("GNNPE_ROWS_PROBE", 0)) {
             if (mode >= 1 && mode <= 3 && c->rows_identity && e == 2 && packed && c->slab_begin == 0 && c->slab_end == c->n) {
                 DevBuf probe_recs, probe_pairs;  // freed on return (a diagnostic path may allocate)
                 if ((rc = probe_recs.reserve((c->rblock_units + 1) * kRowAlign)) || (rc = probe_pairs.reserve((ne + 1) * sizeof(RankedPair)))) return rc;
@@ -1032,9 +1096,9 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
 #endif
         GNNPE_HIP_TRY(hipGetLastError());
     }
-    if (c->n_hub) {
+    if (c->n_hub && launch) {
         // hub rows (known since the rows were loaded): id-ordered records, the rows' ranks sorted per row, counts by
-        // binary search
+        // binary search (a refresh: the records again -- k_hub_records knows nothing of the pairs -- and no sort, no pairs)
         if ((rc = c->nbr_rank.reserve((c->nbr_used + 1) * 4)) || (rc = c->rank_sorted.reserve((c->nbr_used + 1) * 4))) return rc;
         const dim3 grid(grid_for((uint64_t)c->n_hub * 64)), block(kBlock);
 #define GNNPE_HR(EE)                                                                                               \
@@ -1043,22 +1107,24 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
                        c->vinfo.as<double>(), c->rblock.as<uint32_t>(), c->rrecs.as<char>(), c->nbr_rank.as<uint32_t>())
         GNNPE_BY_E(e, GNNPE_HR)
 #undef GNNPE_HR
-        size_t ts = 0;
-        GNNPE_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(
-            nullptr, ts, c->nbr_rank.as<uint32_t>(), c->rank_sorted.as<uint32_t>(), (int)c->nbr_used, (int)c->n_hub,
-            c->hub_beg.as<uint32_t>(), c->hub_end.as<uint32_t>(), 0, 32, c->stream));
-        if ((rc = c->cub_tmp.reserve(ts))) return rc;
-        ts = c->cub_tmp.bytes;
-        GNNPE_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(
-            c->cub_tmp.p, ts, c->nbr_rank.as<uint32_t>(), c->rank_sorted.as<uint32_t>(), (int)c->nbr_used, (int)c->n_hub,
-            c->hub_beg.as<uint32_t>(), c->hub_end.as<uint32_t>(), 0, 32, c->stream));
+        if (!reuse) {
+            size_t ts = 0;
+            GNNPE_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(
+                nullptr, ts, c->nbr_rank.as<uint32_t>(), c->rank_sorted.as<uint32_t>(), (int)c->nbr_used, (int)c->n_hub,
+                c->hub_beg.as<uint32_t>(), c->hub_end.as<uint32_t>(), 0, 32, c->stream));
+            if ((rc = c->cub_tmp.reserve(ts))) return rc;
+            ts = c->cub_tmp.bytes;
+            GNNPE_HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(
+                c->cub_tmp.p, ts, c->nbr_rank.as<uint32_t>(), c->rank_sorted.as<uint32_t>(), (int)c->nbr_used, (int)c->n_hub,
+                c->hub_beg.as<uint32_t>(), c->hub_end.as<uint32_t>(), 0, 32, c->stream));
 #define GNNPE_HP(EE)                                                                                               \
     hipLaunchKernelGGL((k_hub_pairs<EE>), grid, block, 0, c->stream, c->n_hub, c->hub_rows.as<uint32_t>(),          \
                        c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),              \
                        c->vinfo.as<double>(), c->revpos.as<uint32_t>(), c->rank_sorted.as<uint32_t>(),              \
                        c->rblock.as<uint32_t>(), c->rpairs.as<RankedPair>())
-        GNNPE_BY_E(e, GNNPE_HP)
+            GNNPE_BY_E(e, GNNPE_HP)
 #undef GNNPE_HP
+        }
         GNNPE_HIP_TRY(hipGetLastError());
     }
     c->ranked_vde_valid = c->have_vde;
@@ -1083,6 +1149,7 @@ static int ensure_slab_struct(gnnpe_ctx *c)
     c->n_edges = (uint32_t)w;
     c->slab_struct_valid = true;
     c->slab_struct_gen++;
+    c->ranked_struct_valid = false;
     c->pst_valid = false;
     return GNNPE_OK;
 }
@@ -1164,18 +1231,26 @@ static int count_paths_impl(gnnpe_ctx *c, uint32_t l, uint64_t *host_per_start, 
     uint64_t w = 0;
 
     // 2. per-pair path counts
+    const bool eoff_was_valid = c->eoff_valid;
+    bool reused = false;  // the structure of the last full ranked count still holds: only the embeddings were refreshed
     if (var == kVarRanked) {
-        // k_start_scan's status words and ticket counter (step 4) are zeroed by the row kernel in front of it
+        // k_start_scan's status words and ticket counter (step 4) are zeroed by the row kernel in front of it; where the
+        // structure is reused and no k_start_scan runs, the refresh kernel zeroes the emit kernel's ticket heads in its place
         const uint32_t n_tiles_c = (len + kStartTile - 1) / kStartTile;
-        if ((rc = c->scan_status.reserve((size_t)n_tiles_c * 8 + 64))) return rc;
+        if ((rc = c->scan_status.reserve((size_t)n_tiles_c * 8 + 64)) || (rc = c->tk_ctl.reserve(kStartHeadsBytes + 64))) return rc;
         c->clear_words = c->scan_status.as<uint32_t>();
         c->n_clear = n_tiles_c * 2 + 16;
+        c->heads_words = c->tk_ctl.as<uint32_t>();
+        c->n_heads_words = kStartHeadsBytes / 4u;
         c->clear_done = false;
+        c->heads_clean = false;
         rc = build_ranked(c, ne);
-        c->clear_words = nullptr;
-        c->n_clear = 0;
+        c->clear_words = c->heads_words = nullptr;
+        c->n_clear = c->n_heads_words = 0;
         if (rc) return rc;
+        reused = c->ranked_reused;
     } else {
+        c->ranked_struct_valid = false;  // (these counts write eoff and the scratch arrays of the hub rows)
         if ((rc = c->ecnt.reserve((ne + 2) * 4)) || (rc = c->nbr_rank.reserve((c->nbr_used + 1) * 4))) return rc;
         // rank of every held neighbour entry: the rank test becomes a contiguous stream
         if (c->nbr_used)
@@ -1301,7 +1376,7 @@ static int count_paths_impl(gnnpe_ctx *c, uint32_t l, uint64_t *host_per_start, 
     // default emit needs the STARTS' offsets only: k_start_scan below; eoff itself is built on demand (ensure_eoff)
     c->eoff_valid = true;
     if (var == kVarRanked) {
-        c->eoff_valid = false;
+        c->eoff_valid = reused && eoff_was_valid;  // (a scan of the pairs' counts: structure, like the total behind it)
     } else if (var == kVarDeep) {
         // unit counts -> unit offsets (in place), then the pair offsets the per-start counts read
         uint64_t *uoff = c->uoff.as<uint64_t>();
@@ -1317,15 +1392,14 @@ static int count_paths_impl(gnnpe_ctx *c, uint32_t l, uint64_t *host_per_start, 
     }
 
     // 4. per-start records that shorten the emit kernel's dependent-load chain; enqueued before the one read-back
-    if (var == kVarRanked) {
+    // (structure: where it is reused the start records and the total in eoff[ne] are the last full count's)
+    if (var == kVarRanked && !reused) {
         const uint32_t n_tiles = (len + kStartTile - 1) / kStartTile;
         if ((rc = c->srec.reserve((size_t)(len + 1) * sizeof(StartRec))) || (rc = c->scan_status.reserve((size_t)n_tiles * 8 + 64))) return rc;
         // status words, then the ticket counter (a line of its own behind them): zeroed by the row kernel of step 2 where one ran
         if (!c->clear_done) GNNPE_HIP_TRY(hipMemsetAsync(c->scan_status.p, 0, (size_t)n_tiles * 8 + 64, c->stream));
         c->clear_done = false;
         if (!len) GNNPE_HIP_TRY(hipMemsetAsync(c->eoff.as<uint64_t>() + ne, 0, 8, c->stream));  // (no start vertices: no paths; else the last tile writes the total)
-        if ((rc = c->tk_ctl.reserve(kStartHeadsBytes + 64))) return rc;
-        c->heads_clean = false;
         if (len) {
             unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, (uint64_t)blocks_per_cu(k_start_scan) * c->num_cus));
             grid = (unsigned)std::max<long>(1, std::min<long>((long)n_tiles, diag_int("GNNPE_START_SCAN_GRID", (long)grid)));
@@ -1337,13 +1411,17 @@ static int count_paths_impl(gnnpe_ctx *c, uint32_t l, uint64_t *host_per_start, 
             c->heads_clean = true;  // (the emit kernel's ticket heads: no memset in front of the first fill of this count)
         }
         GNNPE_HIP_TRY(hipGetLastError());
+        c->ranked_struct_key = ranked_struct_key(c, ne, e);
+        c->ranked_struct_valid = true;
     }
     c->l = l;
     c->counted = true;
-    c->count_gen++;
+    c->count_gen++;  // (also on a refresh: the index build's pair order carries keys of the embeddings)
     c->counted_variant = var;
-    c->total_known = false;
-    c->total_paths = 0;
+    if (!reused) {  // (a reused structure keeps its total: on the host if it was fetched, else still in eoff[ne])
+        c->total_known = false;
+        c->total_paths = 0;
+    }
     if (!fetch_total) return GNNPE_OK;  // enqueue-only: the total stays in eoff[ne] until somebody asks (resolve_total)
     if ((rc = resolve_total(c))) {
         c->counted = false;
@@ -1909,7 +1987,10 @@ int gnnpe_emit_calibrate_device(gnnpe_ctx *c, uint64_t rows_cap, void *dev_vids,
 int gnnpe_set_fill_variant(gnnpe_ctx *c, int variant)
 {
     GNNPE_REQUIRE(c && (variant == kVarPairWave || variant == kVarRanked), GNNPE_ERR_ARG, "fill variant must be 1 or 4");
-    if (variant != c->fill_variant) c->counted = false;
+    if (variant != c->fill_variant) {
+        c->counted = false;
+        c->ranked_struct_valid = false;
+    }
     c->fill_variant = variant;
     return GNNPE_OK;
 }

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_rows_rank(uint32_t n_held, const uint32
                                                    const uint32_t *__restrict__ nbrs, const double *__restrict__ vinfo,
                                                    const uint32_t *__restrict__ revpos,
                                                    const uint32_t *__restrict__ rblock, char *__restrict__ recs,
-                                                   RankedPair *__restrict__ pairs)
+                                                   RankedPair *__restrict__ pairs, uint8_t *__restrict__ rpos)
 {
     typedef typename RecOf<E, PACKED>::type Rec;
     const unsigned lane = lane_id();
@@ -131,6 +131,7 @@ __global__ __launch_bounds__(256) void k_rows_rank(uint32_t n_held, const uint32
 #pragma unroll
             for (int k = 0; k < E; k++) rec.vde[k] = vu[k];
             reinterpret_cast<Rec *>(base + 8 * E)[cnt] = rec;
+            rpos[st + lane] = (uint8_t)cnt;  // (structure: where k_rows_refresh finds this entry's record again)
             if (rp != kNoEdge && po != kNoEdge) {  // (u, b) is a pair of this slab: u starts here and its row is held
                 RankedPair pr = {blk, cnt, G};
                 // the one random store per adjacency entry.  Round-3 knock-outs at config 3 (count phase, same process: 1.07 ms):
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(256) void k_rows_rank_multi(uint32_t n_held, const 
                                                          const uint32_t *__restrict__ nbrs, const double *__restrict__ vinfo,
                                                          const uint32_t *__restrict__ revpos,
                                                          const uint32_t *__restrict__ rblock, char *__restrict__ recs,
-                                                         RankedPair *__restrict__ pairs, uint32_t *__restrict__ clear_words,
-                                                         uint32_t n_clear, uint32_t pair8)
+                                                         RankedPair *__restrict__ pairs, uint8_t *__restrict__ rpos,
+                                                         uint32_t *__restrict__ clear_words, uint32_t n_clear, uint32_t pair8)
 {
     typedef typename RecOf<E, PACKED>::type Rec;
     constexpr int S = GNNPE_VINFO_STRIDE(E);
@@ -228,6 +229,7 @@ __global__ __launch_bounds__(256) void k_rows_rank_multi(uint32_t n_held, const 
 #pragma unroll
             for (int j = 0; j < E; j++) rec.vde[j] = vu[k][j];
             reinterpret_cast<Rec *>(base + 8 * E)[cnt] = rec;
+            rpos[st[k] + lane] = (uint8_t)cnt;  // (structure: where k_rows_refresh finds this entry's record again)
             if (rp[k] != kNoEdge && po != kNoEdge) {
                 if (pair8) {  // diagnostic builds, GNNPE_ROWS_PAIR8=1: what an 8-byte pair record {block, count} would cost the scatter
                     reinterpret_cast<uint2 *>(pairs)[po + rp[k]] = make_uint2(blk[k], cnt);  // (no G: the emit kernel cannot use these)
@@ -235,6 +237,100 @@ __global__ __launch_bounds__(256) void k_rows_rank_multi(uint32_t n_held, const 
                     RankedPair pr = {blk[k], cnt, G};
                     pairs[po + rp[k]] = pr;
                 }
+            }
+        }
+    }
+}
+
+// The EMBEDDING REFRESH of a count whose structure is still valid (gnnpe_common.h: ranked_struct_valid): for every held row of
+// degree <= 64 the block header vde[b] and every record's vde again -- nothing of what k_rows_rank_multi computes besides: no
+// reverse positions, no ranks, no G loop, no pair scatter, and k_start_scan does not run behind it.  Row-driven like
+// k_rows_rank_multi (K rows per wave, the K rows' loads batched, no load under a lane mask, every gathered value waited for once):
+// the entry's id comes from the adjacency row, its record's position from rpos (a byte per entry, left by the full count), so the
+// WHOLE record {id | id-position, vde} is stored again -- the id word with the bits it had -- and the blocks' lines are written in
+// full as the full count writes them, never read.  One gather per entry from the per-vertex records (the vde half only).
+// FROM_BLOCKS (diagnostic builds, GNNPE_REFRESH_SHAPE=1: the shape this one was measured against): a lane per record in block
+// order reads the record's own id word and stores the E doubles in place -- no position array, but the blocks are read (as many
+// lines again as the gathers) and 16 of every 20 bytes of a line are written.
+// (clear_words: the emit kernel's ticket heads, which k_start_scan zeroes in a full count.)
+template <int E, bool PACKED, int K, bool FROM_BLOCKS>
+__global__ __launch_bounds__(256) void k_rows_refresh(uint32_t n_held, const uint32_t *__restrict__ held,
+                                                      const uint32_t *__restrict__ adj_start,
+                                                      const uint32_t *__restrict__ adj_deg,
+                                                      const uint32_t *__restrict__ nbrs, const double *__restrict__ vinfo,
+                                                      const uint8_t *__restrict__ rpos, const uint32_t *__restrict__ rblock,
+                                                      char *__restrict__ recs, uint32_t *__restrict__ clear_words, uint32_t n_clear)
+{
+    typedef typename RecOf<E, PACKED>::type Rec;
+    constexpr int S = GNNPE_VINFO_STRIDE(E);
+    const unsigned lane = lane_id();
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_clear; i += gridDim.x * blockDim.x) clear_words[i] = 0u;
+    const uint64_t w = (uint64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    uint32_t b[K], st[K], d[K], blk[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint64_t idx = w * K + k;
+        const bool ok = idx < n_held;
+        b[k] = ok ? (held ? held[idx] : (uint32_t)idx) : 0u;
+        st[k] = adj_start[b[k]];
+        d[k] = ok ? adj_deg[b[k]] : 0u;
+        if (d[k] > kHubDegree) d[k] = 0;  // hub rows: k_hub_records
+        blk[k] = rblock[b[k]];
+    }
+    uint32_t u[K], pos[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t j = d[k] ? min(lane, d[k] - 1u) : 0u;  // (idle lanes re-read the row's last entry)
+        if constexpr (FROM_BLOCKS) {
+            // (a row without entries has no block: it reads the first word of the buffer)
+            const char *src = d[k] ? recs + (uint64_t)blk[k] * kRowAlign + 8 * E + (uint64_t)j * sizeof(Rec) : recs;
+            const uint32_t first = *reinterpret_cast<const uint32_t *>(src);
+            u[k] = d[k] ? (PACKED ? first & ((1u << kPackedIdBits) - 1u) : first) : 0u;
+            pos[k] = j;
+        } else {
+            const uint32_t q = d[k] ? st[k] + j : 0u;
+            const uint32_t uq = nbrs[q];
+            u[k] = d[k] ? uq : 0u;  // (a row without entries gathers vertex 0's record: entry 0 may not exist)
+            pos[k] = min((uint32_t)rpos[q], d[k] ? d[k] - 1u : 0u);  // (a position never leaves its block, whatever the byte holds)
+        }
+    }
+    double vu[K][E], hb[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const double *vi = vinfo + (uint64_t)u[k] * S;
+#pragma unroll
+        for (int j = 0; j < E; j++) vu[k][j] = vi[j];
+        hb[k] = vinfo[(uint64_t)b[k] * S + min(lane, (unsigned)(E - 1))];  // header: vde of the row's vertex
+    }
+    // every gathered value is waited for HERE, once (k_rows_rank_multi's comment)
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        asm volatile("" : "+v"(hb[k]), "+v"(pos[k]));
+#pragma unroll
+        for (int j = 0; j < E; j++) asm volatile("" : "+v"(vu[k][j]));
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t du = (uint32_t)__builtin_amdgcn_readfirstlane((int)d[k]);
+        if (du == 0) continue;
+        char *const base = recs + (uint64_t)blk[k] * kRowAlign;
+        if (lane < (unsigned)E) reinterpret_cast<double *>(base)[lane] = hb[k];
+        if (lane < du) {
+            Rec *const dst = reinterpret_cast<Rec *>(base + 8 * E) + pos[k];
+            if constexpr (FROM_BLOCKS) {
+#pragma unroll
+                for (int j = 0; j < E; j++) dst->vde[j] = vu[k][j];
+            } else {
+                Rec rec;
+                if constexpr (PACKED) {
+                    rec.idp = u[k] | (lane << kPackedIdBits);
+                } else {
+                    rec.id = u[k];
+                    rec.aux = lane;
+                }
+#pragma unroll
+                for (int j = 0; j < E; j++) rec.vde[j] = vu[k][j];
+                *dst = rec;
             }
         }
     }
