@@ -98,7 +98,8 @@ namespace gnnpe {
 //   GNNPE_DEBUG=1                        launch shapes / pool candidates on stderr
 //   GNNPE_TESTING=k=v,...                testing aids: pool_min_probe_bytes (below it the pool takes what comes: 512 MiB),
 //                                        index_keep_bytes (cap on the device copies gnnpe_build_index_files keeps per wave),
-//                                        index_max_units (sort units the l = 3 index build accepts before it takes the tuple-array build: 2^31)
+//                                        index_max_units (sort units the l = 3 index build accepts before it takes the tuple-array build: 2^31),
+//                                        sets_first_shift (0..6: gnnpe_refine_sets takes it for sets_first_level_shift's answer; larger values are ignored)
 // Everything else that rounds 2-5 switched by environment for A/B runs exists in diagnostic builds only (make DIAG=1:
 // gnnpe::diag_int below): the static start-vertex walk, staged rows, LDS pads, the ticket / strip-job emit kernels, tile heights,
 // rows per wave of the count kernel, the leaf kernel's XCD chunks, candidate draws of the image buffer, knock-outs, stamps.
@@ -107,6 +108,7 @@ struct Switches {
     bool deep_merge = false, aux_wide = false, debug = false;
     int deep_emit = 0;  // 1 slices, 2 units
     uint64_t pool_min_probe_bytes = 512ull << 20, index_keep_bytes = ~0ull, index_max_units = 1ull << 31;
+    int sets_first_shift = -1;  // -1 unset: the heuristic
 };
 Switches read_switches();  // gnnpe_engine.hip
 #ifdef GNNPE_DIAG

@@ -178,6 +178,7 @@ gnnpe::Switches gnnpe::read_switches()
                 if (k == "pool_min_probe_bytes") w.pool_min_probe_bytes = v;
                 else if (k == "index_keep_bytes") w.index_keep_bytes = v;
                 else if (k == "index_max_units") w.index_max_units = v;
+                else if (k == "sets_first_shift" && v <= 6) w.sets_first_shift = (int)v;
             }
             at = end + 1;
         }

@@ -317,7 +317,12 @@ int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t
     if (he == hipSuccess && device_ms) he = hipEventCreate(&ev0);
     if (he == hipSuccess && device_ms) he = hipEventCreate(&ev1);
     if (he == hipSuccess && device_ms) he = hipEventRecord(ev0, c->stream);
-    const uint32_t w_shift = sets_first_level_shift(n_cand, c->nbr_used, c->n, c->num_cus, c->n_hub);
+    // GNNPE_TESTING=sets_first_shift=K stands in for the heuristic; the 32-bit item offsets still come first
+    const bool forced = c->sw.sets_first_shift >= 0 && c->nbr_used + c->n < (1ull << 32);
+    const uint32_t w_shift = forced ? (uint32_t)c->sw.sets_first_shift
+                                    : sets_first_level_shift(n_cand, c->nbr_used, c->n, c->num_cus, c->n_hub);
+    if (c->sw.debug)
+        fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d\n", w_shift, (int)forced, n_cand, c->n_hub, c->num_cus);
     if (he == hipSuccess && nq > 1) {
         hipLaunchKernelGGL(k_sets_cand_chunks, dim3((n_cand + 256) / 256), dim3(256), 0, c->stream, n_cand, d_cand,
                            c->adj_deg.as<uint32_t>(), w_shift, d_chunks);

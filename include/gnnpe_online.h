@@ -38,7 +38,8 @@ int gnnpe_refine(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *c
  * The reference-mode filter's sets are NOT complete: there the functions above (start vertex only) give the reference's
  * answer and these give a smaller one.  The count does not depend on the matching order. */
 
-/* Host form: plain backtracking that applies the set test at every level.  Arguments as gnnpe_host_refine. */
+/* Host form: plain backtracking that applies the set test at every level.  Arguments as gnnpe_host_refine.  It has no
+ * limit on the query's size: a connected query of 33 or more vertices, which the device form refuses, is counted here. */
 int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                            const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers);
 
