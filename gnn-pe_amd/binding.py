@@ -124,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 9  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 10  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 _lib = None
 
 
@@ -140,6 +140,11 @@ ONLINE_SIGNATURES = {
     "gnnpe_refine": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _f64p]),
     "gnnpe_host_refine_sets": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
     "gnnpe_refine_sets": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_refine_pages_open": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
+    "gnnpe_refine_pages_next": (C.c_int, [_vp, _u32p, _u64p, C.POINTER(C.c_int), _f64p]),
+    "gnnpe_refine_pages_device_ptr": (C.c_int, [_vp, C.POINTER(_vp), _u32p]),
+    "gnnpe_refine_pages_info": (C.c_int, [_vp, _u64p]),
+    "gnnpe_refine_pages_close": (None, [_vp]),
 }
 _online = None
 
@@ -454,6 +459,7 @@ class _DevArray:
 
     def __init__(self, ptr, shape, typestr, owner=None):
         self.owner = owner  # keeps the pool (and through it the engine) alive for as long as a tensor shares the memory
+        self.shape = tuple(int(x) for x in shape)
         self.__cuda_array_interface__ = dict(shape=tuple(int(x) for x in shape), typestr=typestr, data=(int(ptr), False),
                                              version=2, strides=None)
 
@@ -522,6 +528,71 @@ class OutputPool:
             pass
 
 
+class MatchCursor:
+    """gnnpe_refine_pages_*: a cursor over the embeddings of a query inside its candidate sets.  next() delivers the next page of
+    at most page_rows embeddings as (rows, done); across the pages every embedding comes out exactly once, up to `limit`.  With
+    device=False rows is a fresh np.uint32 array of n_rows x n_query_vertices; with device=True it is a zero-copy view of the
+    cursor's device page (`torch.as_tensor(rows, device=...)` shares it: int32 words holding the uint32 ids, like
+    OutputPool.ids_tensor), valid until the next next() or close().  Loading another graph into the engine invalidates the
+    cursor: next() raises.  Engine.close() closes the engine's open cursors."""
+
+    INFO_FIELDS = ("pages", "rows", "suspended_waves", "items_left", "slots")
+
+    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False):
+        self.eng, self.lib, self.h = eng, load_online(), None
+        bm = _np(bitmap, np.uint32)
+        self.page_rows, self.device = int(page_rows), bool(device)
+        self.done = False
+        h = C.c_void_p()
+        eng._ck(self.lib.gnnpe_refine_pages_open(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows,
+                                                 C.byref(h)))
+        self.h = h
+        ptr, nq = C.c_void_p(), C.c_uint32()
+        eng._ck(self.lib.gnnpe_refine_pages_device_ptr(self.h, C.byref(ptr), C.byref(nq)))
+        self.nq = int(nq.value)
+        self._host_rows = min(self.page_rows, int(limit))  # rows a page can hold
+        eng._cursors.append(self)
+
+    def next(self):
+        """(rows, done): the next page; after done, an empty page and done again"""
+        if not self.h:
+            raise GnnpeError("MatchCursor.next(): the cursor is closed")
+        n, done, ms = C.c_uint64(), C.c_int(), C.c_double()
+        rows = None if self.device or self.done else np.empty((self._host_rows, self.nq), np.uint32)
+        self.eng._ck(self.lib.gnnpe_refine_pages_next(self.h, _ptr(rows, _u32p), C.byref(n), C.byref(done), C.byref(ms)))
+        self.done, self.device_ms = bool(done.value), ms.value
+        k = int(n.value)
+        if not self.device:
+            return (np.zeros((0, self.nq), np.uint32) if rows is None else rows[:k].copy() if k < len(rows) else rows), self.done
+        ptr = C.c_void_p()
+        self.eng._ck(self.lib.gnnpe_refine_pages_device_ptr(self.h, C.byref(ptr), None))
+        return _DevArray(int(ptr.value or 0), (k, self.nq), "<i4", owner=self), self.done
+
+    def info(self):
+        out = (C.c_uint64 * 5)()
+        self.eng._ck(self.lib.gnnpe_refine_pages_info(self.h, out))
+        return dict(zip(self.INFO_FIELDS, (int(x) for x in out)))
+
+    def close(self):
+        if self.h and self.eng.ctx:
+            self.lib.gnnpe_refine_pages_close(self.h)
+        self.h = None
+        if self in self.eng._cursors:
+            self.eng._cursors.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One context = one GPU.  Method names follow the reference functions they replace."""
 
@@ -535,12 +606,15 @@ class Engine:
         self.slab = (0, 0)
         self.total = None
         self._pools = []
+        self._cursors = []  # open match cursors: closed before the context goes
         self.stream_handle = None  # None = the context's own stream
         if stream is not None:
             self.set_stream(stream)
 
     def close(self):
         if self.ctx:
+            for cur in list(getattr(self, "_cursors", [])):
+                cur.close()
             for p in list(getattr(self, "_pools", [])):
                 p.close(force=True)
             self.lib.gnnpe_destroy(self.ctx)
@@ -753,6 +827,23 @@ class Engine:
         if rows is None:
             return out.value, ms.value
         return out.value, ms.value, rows[:min(out.value, cap)]
+
+    def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False):
+        """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open)."""
+        return MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device)
+
+    def match_pages(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False):
+        """Generator over the pages of a MatchCursor: every embedding inside the sets exactly once, up to `limit`, at most
+        page_rows per page (an empty last page is not yielded).  The cursor is closed when the generator ends or is dropped."""
+        cur = MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device)
+        try:
+            done = False
+            while not done:
+                rows, done = cur.next()
+                if rows.shape[0]:
+                    yield rows
+        finally:
+            cur.close()
 
     def path_partitions_device(self, begin, end, dev_part):
         self._ck(self.lib.gnnpe_path_partitions_device(self.ctx, begin, end, _dev(dev_part)))

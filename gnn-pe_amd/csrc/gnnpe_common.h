@@ -99,7 +99,7 @@ namespace gnnpe {
 //   GNNPE_TESTING=k=v,...                testing aids: pool_min_probe_bytes (below it the pool takes what comes: 512 MiB),
 //                                        index_keep_bytes (cap on the device copies gnnpe_build_index_files keeps per wave),
 //                                        index_max_units (sort units the l = 3 index build accepts before it takes the tuple-array build: 2^31),
-//                                        sets_first_shift (0..6: gnnpe_refine_sets takes it for sets_first_level_shift's answer; larger values are ignored)
+//                                        sets_first_shift (0..6: gnnpe_refine_sets and gnnpe_refine_pages_open take it for sets_first_level_shift's answer; larger values are ignored)
 // Everything else that rounds 2-5 switched by environment for A/B runs exists in diagnostic builds only (make DIAG=1:
 // gnnpe::diag_int below): the static start-vertex walk, staged rows, LDS pads, the ticket / strip-job emit kernels, tile heights,
 // rows per wave of the count kernel, the leaf kernel's XCD chunks, candidate draws of the image buffer, knock-outs, stamps.
@@ -144,6 +144,9 @@ struct gnnpe_ctx {
     // position and the entries' labels -- for gen_vde; everything else runs on the simple rows above
     bool multigraph = false;
     gnnpe::DevBuf mg_off, mg_label;
+    // counts the calls that load or change the rows (gnnpe_load_csr, gnnpe_load_rows, gnnpe_set_multigraph_rows, gnnpe_rows_append,
+    // gnnpe_rows_drop_halo): what was opened on an earlier graph -- a match cursor, gnnpe_refine_pages_open -- refuses to go on
+    uint64_t graph_gen = 0;
     // rows longer than 64 entries ("hub" rows of the l=2 enumeration): ids and adjacency ranges; graph-only, rebuilt
     // whenever rows are loaded / appended / dropped
     gnnpe::DevBuf hub_rows, hub_beg, hub_end;

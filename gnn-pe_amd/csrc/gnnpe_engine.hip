@@ -446,6 +446,7 @@ int gnnpe_load_csr(gnnpe_ctx *c, uint32_t n, const uint32_t *offs, const uint32_
 {
     GNNPE_REQUIRE(c && offs && labels && (nbrs || offs[n] == 0), GNNPE_ERR_ARG, "gnnpe_load_csr: null argument");
     GNNPE_HIP_TRY(hipSetDevice(c->device));
+    c->graph_gen++;
     const uint64_t m2 = offs[n];
     for (uint32_t i = 0; i < n; i++)
         GNNPE_REQUIRE(offs[i] <= offs[i + 1], GNNPE_ERR_ARG, "offsets not monotone at %u", i);
@@ -492,6 +493,7 @@ int gnnpe_load_rows(gnnpe_ctx *c, uint32_t n, const uint32_t *labels, uint32_t n
     GNNPE_REQUIRE(c && labels && (n_rows == 0 || (rows && row_offsets)), GNNPE_ERR_ARG,
                   "gnnpe_load_rows: null argument");
     GNNPE_HIP_TRY(hipSetDevice(c->device));
+    c->graph_gen++;
     const uint64_t used = n_rows ? row_offsets[n_rows] : 0;
     GNNPE_REQUIRE(used == 0 || row_nbrs, GNNPE_ERR_ARG, "gnnpe_load_rows: null neighbour buffer");
     for (uint32_t k = 0; k < n_rows; k++)
@@ -549,6 +551,7 @@ int gnnpe_set_multigraph_rows(gnnpe_ctx *c, uint32_t n_rows, const uint64_t *row
     GNNPE_REQUIRE(n_rows == c->n_rows, GNNPE_ERR_ARG, "gnnpe_set_multigraph_rows: %u rows given, %u loaded", n_rows, c->n_rows);
     GNNPE_REQUIRE(c->n_held == c->n_rows, GNNPE_ERR_ARG, "gnnpe_set_multigraph_rows: call it before halo rows are appended");
     GNNPE_HIP_TRY(hipSetDevice(c->device));
+    c->graph_gen++;
     for (uint32_t k = 0; k < n_rows; k++)
         GNNPE_REQUIRE(row_offsets[k] <= row_offsets[k + 1], GNNPE_ERR_ARG, "gnnpe_set_multigraph_rows: offsets not monotone at row %u", k);
     const uint64_t used = row_offsets[n_rows] - row_offsets[0];
@@ -2053,6 +2056,7 @@ int gnnpe_rows_drop_halo(gnnpe_ctx *c)
     GNNPE_REQUIRE(c && c->have_graph, GNNPE_ERR_ARG, "gnnpe_rows_drop_halo: no graph");
     GNNPE_HIP_TRY(hipSetDevice(c->device));
     if (c->rows_identity || c->n_held == c->n_rows) return GNNPE_OK;
+    c->graph_gen++;
     hipLaunchKernelGGL(k_drop_halo, dim3(grid_for(c->n)), dim3(kBlock), 0, c->stream, c->n, c->owned.as<uint8_t>(),
                        c->present.as<uint8_t>(), c->adj_deg.as<uint32_t>());
     GNNPE_HIP_TRY(hipGetLastError());
@@ -2111,6 +2115,7 @@ int gnnpe_rows_append(gnnpe_ctx *c, uint64_t n_rows, const void *dev_ids, const 
     GNNPE_REQUIRE(min_rank == 0 || c->have_order, GNNPE_ERR_ARG, "gnnpe_rows_append: min_rank needs gnnpe_set_order first");
     GNNPE_REQUIRE(!c->rows_identity && (uint64_t)c->n_held + n_rows <= c->n, GNNPE_ERR_ARG,
                   "gnnpe_rows_append: more rows than vertices");
+    c->graph_gen++;
     int rc;
     // scratch: src_off u64[n_rows+1] | dst_off u64[n_rows+1] | deg u32[n_rows+1] | kept u32[n_rows+1]
     if ((rc = c->scratch.reserve((n_rows + 1) * 24 + 64))) return rc;

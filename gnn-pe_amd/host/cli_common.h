@@ -38,6 +38,10 @@ struct Options {
     // -m online with complete sets (--exact, -l 3): "start" = the frozen refinement (gnnpe_refine), "sets" = the set-restricted
     // one (gnnpe_refine_sets); --matches FILE (needs sets) writes the embeddings, one per line
     std::string refine = "start", matches_file;
+    // --all-matches (needs --matches): every embedding up to -n, page by page through the match cursor (gnnpe_refine_pages_*);
+    // --match-page ROWS (needs --all-matches): rows per page
+    bool all_matches = false, match_page_given = false;
+    uint64_t match_page = 1ull << 20;
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
     std::string transport = "rccl";  // --gpus N > 1: "rccl" (ncclSend/ncclRecv over xGMI) or "copy" (device-to-device copies)
@@ -114,7 +118,9 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             printf("%s -f <dataset dir/> -d <data.graph> -m offline -p <partitions> [-l 2] [-e 2]\n"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
-                   "           [--refine start|sets] [--matches FILE]\n",
+                   "           [--refine start|sets] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
+                   "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
+                   "       in pages of ROWS embeddings (default 1048576)\n",
                    tool, tool);
             exit(0);
         }
@@ -138,6 +144,15 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;
         }
+        if (a == "--match-page") {
+            if (i + 1 >= argc) die(a + " needs a value");
+            char *end = nullptr;
+            o.match_page = strtoull(argv[++i], &end, 10);
+            if (*end || end == argv[i] || o.match_page == 0) die("--match-page must be an integer of at least 1");
+            o.match_page_given = true;
+            continue;
+        }
+        if (a == "--all-matches") { o.all_matches = true; continue; }
         if (a == "--allow-large") { o.allow_large = true; continue; }
         if (a == "--timing") { o.timing = true; continue; }
         if (a == "--sidecars") { o.sidecars = true; continue; }

@@ -165,7 +165,8 @@ struct Device {
 // Writes <f>gnn-pe/candidates.bin: uint32 n_query_vertices; per query vertex uint32 count + ascending data vertex
 // ids -- the reference's candidate_set, ready for its refinement (main.cpp:176-179).  -m online goes on with the
 // refinement on the device (gnnpe_refine; with --refine sets, where the sets are complete, gnnpe_refine_sets, which can
-// also hand back the embeddings: --matches) and prints the reference's answer line instead of writing the file.
+// also hand back the embeddings: --matches, at most 2^20 of them, or with --all-matches all of them page by page through
+// the match cursor, gnnpe_refine_pages_*) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -250,7 +251,38 @@ int run_filter(const Options &o)
         if (!refine) die("libgnnpe_online.so does not export gnnpe_refine");
         const bool sets = o.refine == "sets";
         uint64_t n_written = 0;
-        if (sets) {
+        uint64_t n_pages = 0;
+        if (sets && o.all_matches) {
+            // every embedding up to -n through the match cursor (gnnpe_refine_pages_*): one page on the host at a time
+            typedef struct gnnpe_match_cursor cursor_t;
+            typedef int (*open_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t, cursor_t **);
+            typedef int (*next_fn)(cursor_t *, uint32_t *, uint64_t *, int *, double *);
+            typedef void (*close_fn)(cursor_t *);
+            open_fn pages_open = (open_fn)dlsym(online, "gnnpe_refine_pages_open");
+            next_fn pages_next = (next_fn)dlsym(online, "gnnpe_refine_pages_next");
+            close_fn pages_close = (close_fn)dlsym(online, "gnnpe_refine_pages_close");
+            if (!pages_open || !pages_next || !pages_close) die("libgnnpe_online.so does not export gnnpe_refine_pages_*");
+            const uint64_t page = std::min<uint64_t>(o.match_page, std::max<uint64_t>(limit, 1));
+            cursor_t *cur = nullptr;
+            check(pages_open(ctx, o.query_graph.c_str(), bitmap.data(), limit, page, &cur), "refine_pages_open");
+            FILE *mf = fopen(o.matches_file.c_str(), "w");
+            if (!mf) die("cannot write " + o.matches_file);
+            std::vector<uint32_t> rows((size_t)page * n_qv);
+            for (int done = 0; !done;) {
+                uint64_t got = 0;
+                double page_ms = 0.0;
+                check(pages_next(cur, rows.data(), &got, &done, &page_ms), "refine_pages_next");
+                for (uint64_t k = 0; k < got; k++)
+                    for (uint32_t u = 0; u < n_qv; u++)
+                        fprintf(mf, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
+                answers += got;
+                refine_ms += page_ms;
+                n_pages++;
+            }
+            pages_close(cur);
+            if (fclose(mf) != 0) die("write failed on " + o.matches_file);
+            n_written = answers;
+        } else if (sets) {
             // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
             typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t *, uint32_t *, uint64_t,
                                           double *);
@@ -274,7 +306,12 @@ int run_filter(const Options &o)
         }
         gnnpe_destroy(ctx);
         printf("Answer Number: %llu Query Time (ms): %g\n", (unsigned long long)answers, ms + refine_ms);
-        if (o.timing && sets)
+        if (o.timing && sets && o.all_matches)
+            fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"match_pages\": %llu, \"paths\": %llu, "
+                            "\"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
+                    exact_json.c_str(), (unsigned long long)n_written, (unsigned long long)n_pages, (unsigned long long)P, n_qp, ms,
+                    refine_ms, secs(t0, Clock::now()));
+        else if (o.timing && sets)
             fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"paths\": %llu, \"query_paths\": %u, "
                             "\"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
                     exact_json.c_str(), (unsigned long long)n_written, (unsigned long long)P, n_qp, ms, refine_ms,
@@ -336,6 +373,8 @@ int main(int argc, char **argv)
     if (o.partition_num == 0) die("-p must be >= 1");
     // --refine sets counts inside EVERY candidate set, so it needs complete sets (INTEGRATION.md "Exact mode")
     if (!o.matches_file.empty() && o.refine != "sets") die("--matches needs --refine sets");
+    if (o.all_matches && o.matches_file.empty()) die("--all-matches needs --matches FILE");
+    if (o.match_page_given && !o.all_matches) die("--match-page needs --all-matches");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "

@@ -54,6 +54,41 @@ int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *
 int gnnpe_refine_sets(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                       uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
 
+/* ---- ABI version 10: paged match enumeration -----------------------------------------------------------------------
+ * A cursor over the embeddings gnnpe_refine_sets counts: every call of next delivers the next page of at most page_rows
+ * embeddings, and across the pages every embedding inside the sets comes out exactly once, up to `limit`, whatever the
+ * page size (csrc/gnnpe_refine_pages.hip: a wave that finds the page full stores its search state and the next launch
+ * carries on from it; nothing is walked or counted twice).
+ *
+ * open: requirements and refusals as gnnpe_refine_sets -- the whole simple graph on the device, a connected query graph
+ *   of 1..32 vertices, no multigraph state; page_rows == 0 is refused.  The cursor OWNS its device memory (its copy of
+ *   the bitmap, start candidates, item offsets, counters, suspend slots, one page of min(page_rows, limit) rows), so
+ *   two cursors may be open on one context with their pages interleaved, and gnnpe_refine_sets and the filters may run
+ *   between two pages.  candidate_bitmap may be freed once open returns.
+ * next: fills the device page and, unless host_rows (page_rows x n_query_vertices uint32) is NULL, copies its *n_rows
+ *   rows there; row k column u = f_k(u), column = query vertex id as in the query file.  Every page except the last
+ *   holds exactly page_rows rows.  *done = 1 with the last page; a page of 0 rows comes only together with *done = 1
+ *   (limit == 0, an empty set, no embedding, or a count that is a multiple of page_rows).  After *done a call returns
+ *   0 rows and *done = 1 and launches nothing.  The rows of all pages together are pairwise different embeddings
+ *   inside the sets, min(R(C, 2^64 - 1), limit) of them; their order, and which embeddings come out when `limit`
+ *   cuts, are unspecified.  device_ms (may be NULL) is the page's kernel time.  The small counter block comes back
+ *   once per page, as in gnnpe_refine_sets.
+ * device_ptr: the device page the last next filled (its first *n_rows rows), valid until the next call of next or
+ *   close: the path for consumers on the device, who pass host_rows == NULL.
+ * info: {pages delivered (launches), rows delivered, waves suspended at the end of the last page, first-level items not
+ *   yet taken, suspend slots (resident waves)}.  After *done the third and fourth are 0.
+ * Lifetime: loading or changing the context's rows (gnnpe_load_csr, gnnpe_load_rows, gnnpe_set_multigraph_rows,
+ *   gnnpe_rows_append, gnnpe_rows_drop_halo) invalidates the open cursors: their next call of next returns GNNPE_ERR_ARG
+ *   with a message and launches nothing; close still works.  Cursors MUST be closed before gnnpe_destroy.  close(NULL)
+ *   does nothing. */
+typedef struct gnnpe_match_cursor gnnpe_match_cursor;
+int gnnpe_refine_pages_open(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                            uint64_t page_rows, gnnpe_match_cursor **cursor);
+int gnnpe_refine_pages_next(gnnpe_match_cursor *cursor, uint32_t *host_rows, uint64_t *n_rows, int *done, double *device_ms);
+int gnnpe_refine_pages_device_ptr(gnnpe_match_cursor *cursor, void **dev_rows, uint32_t *n_query_vertices);
+int gnnpe_refine_pages_info(gnnpe_match_cursor *cursor, uint64_t info[5]);
+void gnnpe_refine_pages_close(gnnpe_match_cursor *cursor);
+
 #ifdef __cplusplus
 }
 #endif
