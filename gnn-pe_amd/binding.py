@@ -124,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 10  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 11  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 _lib = None
 
 
@@ -145,6 +145,10 @@ ONLINE_SIGNATURES = {
     "gnnpe_refine_pages_device_ptr": (C.c_int, [_vp, C.POINTER(_vp), _u32p]),
     "gnnpe_refine_pages_info": (C.c_int, [_vp, _u64p]),
     "gnnpe_refine_pages_close": (None, [_vp]),
+    "gnnpe_host_query_symmetry": (C.c_int, [C.c_char_p, _u64p, _u32p, C.c_uint32, _u32p]),
+    "gnnpe_host_refine_sets_distinct": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
+    "gnnpe_refine_sets_distinct": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_refine_pages_open_distinct": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
 }
 _online = None
 
@@ -369,18 +373,35 @@ def host_refine(g, query_path, bitmap, limit=0xFFFFFFFF):
     return out.value
 
 
-def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF):
+def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF, distinct=False):
     """Set-restricted refinement on the host (include/gnnpe_online.h, R(C, limit)): the embeddings whose every image lies in its
-    query vertex's set, counted up to `limit`."""
+    query vertex's set, counted up to `limit`.  distinct=True: D(C, limit), one embedding per distinct subgraph."""
     lib = load()
     out = C.c_uint64()
     o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
     bm = _np(bitmap, np.uint32)
-    rc = load_online().gnnpe_host_refine_sets(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
-                                              _ptr(bm, _u32p), int(limit), C.byref(out))
+    fn = load_online().gnnpe_host_refine_sets_distinct if distinct else load_online().gnnpe_host_refine_sets
+    rc = fn(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(), _ptr(bm, _u32p), int(limit),
+            C.byref(out))
     if rc:
         raise GnnpeError(lib.gnnpe_last_error().decode())
     return out.value
+
+
+def host_query_symmetry(query_path, pairs_cap=None):
+    """gnnpe_host_query_symmetry: (|Aut(Q)| saturated at 2^64 - 1, pairs ndarray [k, 2]); a pair (a, b) asks for f(a) < f(b), and of
+    the |Aut(Q)| embeddings of one subgraph exactly one satisfies every pair.  pairs_cap (default: whatever is needed) is the room
+    offered to the library; too little raises with the needed number in the message."""
+    lib, online = load(), load_online()
+    aut, k = C.c_uint64(), C.c_uint32()
+    if pairs_cap is None:
+        online.gnnpe_host_query_symmetry(query_path.encode(), C.byref(aut), None, 0, C.byref(k))
+        pairs_cap = k.value
+    pairs = np.zeros((max(int(pairs_cap), 1), 2), np.uint32)
+    rc = online.gnnpe_host_query_symmetry(query_path.encode(), C.byref(aut), _ptr(pairs, _u32p), int(pairs_cap), C.byref(k))
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return aut.value, pairs[:k.value].copy()
 
 
 def host_load_path_sidecar(paths_bin, vde_bin, labels, degrees):
@@ -533,19 +554,20 @@ class MatchCursor:
     at most page_rows embeddings as (rows, done); across the pages every embedding comes out exactly once, up to `limit`.  With
     device=False rows is a fresh np.uint32 array of n_rows x n_query_vertices; with device=True it is a zero-copy view of the
     cursor's device page (`torch.as_tensor(rows, device=...)` shares it: int32 words holding the uint32 ids, like
-    OutputPool.ids_tensor), valid until the next next() or close().  Loading another graph into the engine invalidates the
+    OutputPool.ids_tensor), valid until the next next() or close().  distinct=True: one embedding per distinct subgraph
+    (gnnpe_refine_pages_open_distinct).  Loading another graph into the engine invalidates the
     cursor: next() raises.  Engine.close() closes the engine's open cursors."""
 
     INFO_FIELDS = ("pages", "rows", "suspended_waves", "items_left", "slots")
 
-    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False):
+    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False):
         self.eng, self.lib, self.h = eng, load_online(), None
         bm = _np(bitmap, np.uint32)
         self.page_rows, self.device = int(page_rows), bool(device)
         self.done = False
         h = C.c_void_p()
-        eng._ck(self.lib.gnnpe_refine_pages_open(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows,
-                                                 C.byref(h)))
+        open_fn = self.lib.gnnpe_refine_pages_open_distinct if distinct else self.lib.gnnpe_refine_pages_open
+        eng._ck(open_fn(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows, C.byref(h)))
         self.h = h
         ptr, nq = C.c_void_p(), C.c_uint32()
         eng._ck(self.lib.gnnpe_refine_pages_device_ptr(self.h, C.byref(ptr), C.byref(nq)))
@@ -811,10 +833,10 @@ class Engine:
         self._ck(load_online().gnnpe_refine(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out), C.byref(ms)))
         return out.value, ms.value
 
-    def refine_sets(self, query_path, bitmap, limit=0xFFFFFFFF, matches_cap=0):
+    def refine_sets(self, query_path, bitmap, limit=0xFFFFFFFF, matches_cap=0, distinct=False):
         """Set-restricted refinement on the device (gnnpe_refine_sets): (answers, device ms), or with matches_cap > 0
         (answers, device ms, matches) -- matches[k, u] = image of query vertex u in the k-th embedding kept,
-        min(answers, matches_cap) rows."""
+        min(answers, matches_cap) rows.  distinct=True: gnnpe_refine_sets_distinct, one embedding per distinct subgraph."""
         out, ms = C.c_uint64(), C.c_double()
         bm = _np(bitmap, np.uint32)
         cap = min(int(matches_cap), int(limit))
@@ -822,20 +844,22 @@ class Engine:
         if matches_cap > 0:
             nq = bm.shape[0] if bm.ndim == 2 else bm.size // ((self.n + 31) // 32)
             rows = np.zeros((max(cap, 1), nq), np.uint32)
-        self._ck(load_online().gnnpe_refine_sets(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out),
-                                                 _ptr(rows, _u32p) if rows is not None else None, cap, C.byref(ms)))
+        fn = load_online().gnnpe_refine_sets_distinct if distinct else load_online().gnnpe_refine_sets
+        self._ck(fn(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out),
+                    _ptr(rows, _u32p) if rows is not None else None, cap, C.byref(ms)))
         if rows is None:
             return out.value, ms.value
         return out.value, ms.value, rows[:min(out.value, cap)]
 
-    def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False):
-        """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open)."""
-        return MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device)
+    def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False):
+        """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open), or with distinct=True over the ones
+        gnnpe_refine_sets_distinct counts."""
+        return MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct)
 
-    def match_pages(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False):
+    def match_pages(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False):
         """Generator over the pages of a MatchCursor: every embedding inside the sets exactly once, up to `limit`, at most
         page_rows per page (an empty last page is not yielded).  The cursor is closed when the generator ends or is dropped."""
-        cur = MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device)
+        cur = MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct)
         try:
             done = False
             while not done:

@@ -99,7 +99,9 @@ namespace gnnpe {
 //   GNNPE_TESTING=k=v,...                testing aids: pool_min_probe_bytes (below it the pool takes what comes: 512 MiB),
 //                                        index_keep_bytes (cap on the device copies gnnpe_build_index_files keeps per wave),
 //                                        index_max_units (sort units the l = 3 index build accepts before it takes the tuple-array build: 2^31),
-//                                        sets_first_shift (0..6: gnnpe_refine_sets and gnnpe_refine_pages_open take it for sets_first_level_shift's answer; larger values are ignored)
+//                                        sets_first_shift (0..6: gnnpe_refine_sets and gnnpe_refine_pages_open take it for sets_first_level_shift's answer; larger values are ignored),
+//                                        sets_trim (0: the ordered searches of gnnpe_refine_sets_distinct / gnnpe_refine_pages_open_distinct
+//                                        leave the pivot rows whole and only compare; for the measurement of DESIGN.md section 3.7)
 // Everything else that rounds 2-5 switched by environment for A/B runs exists in diagnostic builds only (make DIAG=1:
 // gnnpe::diag_int below): the static start-vertex walk, staged rows, LDS pads, the ticket / strip-job emit kernels, tile heights,
 // rows per wave of the count kernel, the leaf kernel's XCD chunks, candidate draws of the image buffer, knock-outs, stamps.
@@ -109,6 +111,7 @@ struct Switches {
     int deep_emit = 0;  // 1 slices, 2 units
     uint64_t pool_min_probe_bytes = 512ull << 20, index_keep_bytes = ~0ull, index_max_units = 1ull << 31;
     int sets_first_shift = -1;  // -1 unset: the heuristic
+    bool sets_trim = true;      // the ordered searches cut long pivot rows to their bounds
 };
 Switches read_switches();  // gnnpe_engine.hip
 #ifdef GNNPE_DIAG

@@ -179,6 +179,7 @@ gnnpe::Switches gnnpe::read_switches()
                 else if (k == "index_keep_bytes") w.index_keep_bytes = v;
                 else if (k == "index_max_units") w.index_max_units = v;
                 else if (k == "sets_first_shift" && v <= 6) w.sets_first_shift = (int)v;
+                else if (k == "sets_trim") w.sets_trim = v != 0;
             }
             at = end + 1;
         }

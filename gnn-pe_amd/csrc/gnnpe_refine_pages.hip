@@ -24,7 +24,8 @@
 // A launch ends with the page exactly full, or with every item taken and no slot valid: the enumeration is over.
 //
 // Resources (gfx950, -O3): 53 VGPRs (k_refine_sets: 30), no scratch, 896 B of LDS per wave (3 584 B per workgroup) as
-// k_refine_sets; a suspend slot is 912 B of global memory per resident wave (3.6 MiB on 256 CUs).
+// k_refine_sets; a suspend slot is 912 B of global memory per resident wave (3.6 MiB on 256 CUs).  The ordered instantiation
+// (gnnpe_refine_pages_open_distinct) has 58 VGPRs and no scratch; slot and LDS are the same.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -33,6 +34,7 @@
 
 #include "../../include/gnnpe_online.h"
 #include "../host/graph_loader.h"
+#include "../host/query_symmetry.h"
 #include "../host/refine.h"
 #include "gnnpe_common.h"
 #include "gnnpe_refine_sets.hip.h"
@@ -53,13 +55,19 @@ struct PagesSlot {  // saved state of one wave
     uint32_t w[kWaveWords];  // the SetsWave words of depths 0 .. depth
 };
 
+// One kernel, two instantiations.  k_refine_pages<false> is the plain search: the parameter pack is empty, nothing below that is
+// `if constexpr (kOrdered)` exists, and the code is instruction for instruction what it was before the ordered form existed.
+// k_refine_pages<true, SetsOrder> is the ordered search (D(C, limit): one embedding per distinct subgraph): one more by-value
+// argument, the bounds of SetsOrder in every chunk's test, and the long pivot rows trimmed to them.  The bounds are
+// derived from the images, which a suspended wave saves and restores: the slot holds nothing new.
+template <bool kOrdered, class... Ord>
 __global__ __launch_bounds__(kBlock) void k_refine_pages(SetsPlan P, uint32_t n_cand, const uint32_t *__restrict__ cand,
                                                         const uint32_t *__restrict__ item_off, uint32_t n_items, uint32_t w_shift,
                                                         const uint32_t *__restrict__ adj_start,
                                                         const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
                                                         const uint32_t *__restrict__ labels, const uint32_t *__restrict__ bitmap,
                                                         uint64_t words, PagesCounters *ctr, PagesSlot *slots,
-                                                        uint32_t *__restrict__ page, unsigned long long page_rows)
+                                                        uint32_t *__restrict__ page, unsigned long long page_rows, Ord... ord)
 {
     __shared__ SetsWave s_wave[kSetsWavesPerBlock];
     volatile SetsWave &S = s_wave[threadIdx.x >> 6];
@@ -183,6 +191,11 @@ __global__ __launch_bounds__(kBlock) void k_refine_pages(SetsPlan P, uint32_t n_
                 const uint32_t v = ok ? nbrs[idx] : 0u;
                 const uint32_t word = bitmap[(uint64_t)P.qv[d] * words + (v >> 5)], lab = labels[v], dv = adj_deg[v];
                 ok = ok & (((word >> (v & 31u)) & 1u) != 0) & (lab == P.label[d]) & (dv >= P.degree[d]);
+                if constexpr (kOrdered) {
+                    uint32_t lo, hi;
+                    order_bounds(sets_order(ord...), S, d, lo, hi);
+                    ok = ok & (v >= lo) & (v < hi);
+                }
                 for (uint32_t i = 0; i < d; i++) ok &= S.image[i] != v;
                 if (ok && P.back_off[d] < P.back_off[d + 1]) {
                     const uint32_t vs = adj_start[v];
@@ -226,8 +239,19 @@ __global__ __launch_bounds__(kBlock) void k_refine_pages(SetsPlan P, uint32_t n_
             S.ideg[d] = uni(adj_deg[v]);
             d++;
             const uint32_t p = P.pivot[d], ps = uni(S.istart[p]);
-            S.cbase[d] = ps - 64u;
-            S.end[d] = ps + uni(S.ideg[p]);
+            if constexpr (kOrdered) {
+                uint32_t rb = ps, re = ps + uni(S.ideg[p]);
+                if (sets_order(ord...).trim) {
+                    uint32_t lo, hi;
+                    order_bounds(sets_order(ord...), S, d, lo, hi);
+                    order_trim(nbrs, lo, hi, lane, rb, re);
+                }
+                S.cbase[d] = rb - 64u;
+                S.end[d] = re;
+            } else {
+                S.cbase[d] = ps - 64u;
+                S.end[d] = ps + uni(S.ideg[p]);
+            }
             S.mask_lo[d] = 0;
             S.mask_hi[d] = 0;
         }
@@ -244,6 +268,8 @@ struct gnnpe_match_cursor {
     gnnpe_ctx *c = nullptr;
     uint64_t graph_gen = 0;  // the context's graph when the cursor was opened
     SetsPlan P = {};
+    SetsOrder O = {};  // of a distinct cursor
+    uint32_t n_pairs = 0;  // 0: the plain kernel
     uint32_t nq = 0, n_cand = 0, n_items = 0, w_shift = 6, blocks = 0;
     uint64_t words = 0, limit = 0, page_rows = 0, page_cap = 0;  // page_cap: rows the page buffer holds, min(page_rows, limit)
     uint64_t delivered = 0, pages = 0;
@@ -266,16 +292,17 @@ void gnnpe_refine_pages_close(gnnpe_match_cursor *cur)
     delete cur;  // the buffers free themselves
 }
 
-int gnnpe_refine_pages_open(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
-                            uint64_t page_rows, gnnpe_match_cursor **out)
+}  // extern "C"
+
+// gnnpe_refine_pages_open (distinct = false) and gnnpe_refine_pages_open_distinct
+static int refine_pages_open(const char *who, bool distinct, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                             uint64_t limit, uint64_t page_rows, gnnpe_match_cursor **out)
 {
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && out, GNNPE_ERR_ARG, "gnnpe_refine_pages_open: null argument");
+    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && out, GNNPE_ERR_ARG, "%s: null argument", who);
     *out = nullptr;
-    GNNPE_REQUIRE(page_rows > 0, GNNPE_ERR_ARG, "gnnpe_refine_pages_open: page_rows must be at least 1");
-    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED,
-                  "gnnpe_refine_pages_open: the whole graph must be on the device (gnnpe_load_csr)");
-    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED,
-                  "gnnpe_refine_pages_open: simple graphs only (gnnpe_set_multigraph_rows was called)");
+    GNNPE_REQUIRE(page_rows > 0, GNNPE_ERR_ARG, "%s: page_rows must be at least 1", who);
+    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
+    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
     GNNPE_HIP_TRY(hipSetDevice(c->device));
     gnnpe_host::StaticGraph q;
     std::string err;
@@ -322,6 +349,8 @@ int gnnpe_refine_pages_open(gnnpe_ctx *c, const char *query_graph_path, const ui
     }
     P.back_off[nq] = (uint16_t)mo.back_off[nq];
     for (size_t j = 0; j < mo.back.size(); j++) P.back[j] = (uint8_t)pos_of[mo.back[j]];
+    // the ordering constraints by position; a query without symmetry has none and runs the plain kernel
+    if (distinct) cur->n_pairs = sets_order_from_pairs(gnnpe_host::query_symmetry(q).pairs, pos_of, c->sw.sets_trim, &cur->O);
     // start candidates; limit 0 or an empty set anywhere: a cursor that is done before its first page
     std::vector<uint32_t> cand;
     bool empty = limit == 0;
@@ -350,7 +379,7 @@ int gnnpe_refine_pages_open(gnnpe_ctx *c, const char *query_graph_path, const ui
     cur->blocks = (uint32_t)blocks;
     const size_t bm_bytes = (size_t)nq * words * 4, slot_bytes = (size_t)blocks * kSetsWavesPerBlock * sizeof(PagesSlot);
     GNNPE_REQUIRE(cur->page_cap <= (~(size_t)0 >> 1) / ((size_t)nq * 4), GNNPE_ERR_RANGE,
-                  "gnnpe_refine_pages_open: a page of %llu rows does not fit an allocation", (unsigned long long)cur->page_cap);
+                  "%s: a page of %llu rows does not fit an allocation", who, (unsigned long long)cur->page_cap);
     if ((rc = cur->work.reserve(sizeof(PagesCounters) + ((size_t)n_cand * 3 + 2) * 4 + 64)) || (rc = cur->bitmap.reserve(bm_bytes)) ||
         (rc = cur->slots.reserve(slot_bytes)) || (rc = cur->page.reserve((size_t)cur->page_cap * nq * 4)))
         return rc;
@@ -386,6 +415,20 @@ int gnnpe_refine_pages_open(gnnpe_ctx *c, const char *query_graph_path, const ui
     return GNNPE_OK;
 }
 
+extern "C" {
+
+int gnnpe_refine_pages_open(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                            uint64_t page_rows, gnnpe_match_cursor **out)
+{
+    return refine_pages_open("gnnpe_refine_pages_open", false, c, query_graph_path, candidate_bitmap, limit, page_rows, out);
+}
+
+int gnnpe_refine_pages_open_distinct(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                                     uint64_t page_rows, gnnpe_match_cursor **out)
+{
+    return refine_pages_open("gnnpe_refine_pages_open_distinct", true, c, query_graph_path, candidate_bitmap, limit, page_rows, out);
+}
+
 int gnnpe_refine_pages_next(gnnpe_match_cursor *cur, uint32_t *host_rows, uint64_t *n_rows, int *done, double *device_ms)
 {
     GNNPE_REQUIRE(cur && n_rows && done, GNNPE_ERR_ARG, "gnnpe_refine_pages_next: null argument");
@@ -402,10 +445,16 @@ int gnnpe_refine_pages_next(gnnpe_match_cursor *cur, uint32_t *host_rows, uint64
     uint32_t *item_off = reinterpret_cast<uint32_t *>(d_ctr + 1), *d_cand = item_off + cur->n_cand + 1;
     GNNPE_HIP_TRY(hipMemsetAsync(d_ctr, 0, kPagesPerLaunchBytes, c->stream));
     GNNPE_HIP_TRY(hipEventRecord(cur->ev0, c->stream));
-    hipLaunchKernelGGL(k_refine_pages, dim3(cur->blocks), dim3(kBlock), 0, c->stream, cur->P, cur->n_cand, d_cand, item_off,
-                       cur->n_items, cur->w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),
-                       c->labels.as<uint32_t>(), cur->bitmap.as<uint32_t>(), cur->words, d_ctr, cur->slots.as<PagesSlot>(),
-                       cur->page.as<uint32_t>(), (unsigned long long)rows_now);
+    if (cur->n_pairs)
+        hipLaunchKernelGGL((k_refine_pages<true, SetsOrder>), dim3(cur->blocks), dim3(kBlock), 0, c->stream, cur->P, cur->n_cand, d_cand,
+                           item_off, cur->n_items, cur->w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(),
+                           c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), cur->bitmap.as<uint32_t>(), cur->words, d_ctr,
+                           cur->slots.as<PagesSlot>(), cur->page.as<uint32_t>(), (unsigned long long)rows_now, cur->O);
+    else
+        hipLaunchKernelGGL((k_refine_pages<false>), dim3(cur->blocks), dim3(kBlock), 0, c->stream, cur->P, cur->n_cand, d_cand, item_off,
+                           cur->n_items, cur->w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),
+                           c->labels.as<uint32_t>(), cur->bitmap.as<uint32_t>(), cur->words, d_ctr, cur->slots.as<PagesSlot>(),
+                           cur->page.as<uint32_t>(), (unsigned long long)rows_now);
     GNNPE_HIP_TRY(hipGetLastError());
     GNNPE_HIP_TRY(hipEventRecord(cur->ev1, c->stream));
     GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned, d_ctr, sizeof(PagesCounters), hipMemcpyDeviceToHost, c->stream));

@@ -20,6 +20,12 @@
 //     an item, with each of those adds and every 1024 chunks, and leaves once the total has reached the limit.
 //   * matches: at the last depth one atomic add on a row cursor reserves popcount(mask) rows; lanes whose row is below the
 //     cap store image + own v in query-vertex order.
+//   * ordered form (gnnpe_refine_sets_distinct: D(C, limit), one embedding per distinct subgraph): the pairs of
+//     host/query_symmetry.h become, per position, two masks of earlier positions whose images bound this one from below and
+//     from above (SetsOrder).  Per chunk the wave derives the two bounds from the images in LDS and every lane adds
+//     lo <= v < hi to its test; when a depth is entered over a pivot row longer than a chunk, the row is first cut to the
+//     part that can hold such ids by a wave-wide search (row_lower_bound: 64 probes and a ballot per step).  31 VGPRs, no
+//     scratch; the plain instantiation is instruction for instruction the kernel it was (30 VGPRs).
 // host/refine_sets.cpp is the host form.  The plan, the wave state and the first-level items are in gnnpe_refine_sets.hip.h, shared with
 // the paged form of this search (gnnpe_refine_pages.hip).
 #include <hipcub/hipcub.hpp>
@@ -28,7 +34,9 @@
 #include <string>
 #include <vector>
 
+#include "../../include/gnnpe_online.h"
 #include "../host/graph_loader.h"
+#include "../host/query_symmetry.h"
 #include "../host/refine.h"
 #include "gnnpe_common.h"
 #include "gnnpe_refine_sets.hip.h"
@@ -40,13 +48,18 @@ struct SetsCounters {  // one 32-byte block, zeroed before every launch
     uint32_t ticket, pad[3];
 };
 
+// One kernel, two instantiations.  k_refine_sets<false> is the plain search: the parameter pack is empty, nothing below that is
+// `if constexpr (kOrdered)` exists, and the code is instruction for instruction what it was before the ordered form existed.
+// k_refine_sets<true, SetsOrder> is the ordered search (D(C, limit): one embedding per distinct subgraph): one more by-value
+// argument, the bounds of SetsOrder in every chunk's test, and the long pivot rows trimmed to them.
+template <bool kOrdered, class... Ord>
 __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_cand, const uint32_t *__restrict__ cand,
                                                        const uint32_t *__restrict__ item_off, uint32_t w_shift,
                                                        const uint32_t *__restrict__ adj_start,
                                                        const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
                                                        const uint32_t *__restrict__ labels, const uint32_t *__restrict__ bitmap,
                                                        uint64_t words, unsigned long long limit, SetsCounters *ctr,
-                                                       uint32_t *__restrict__ matches, unsigned long long matches_cap)
+                                                       uint32_t *__restrict__ matches, unsigned long long matches_cap, Ord... ord)
 {
     __shared__ SetsWave s_wave[kSetsWavesPerBlock];
     volatile SetsWave &S = s_wave[threadIdx.x >> 6];
@@ -138,6 +151,11 @@ __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_c
                         const uint32_t v = ok ? nbrs[idx] : 0u;
                         const uint32_t word = bitmap[(uint64_t)P.qv[d] * words + (v >> 5)], lab = labels[v], dv = adj_deg[v];
                         ok = ok & (((word >> (v & 31u)) & 1u) != 0) & (lab == P.label[d]) & (dv >= P.degree[d]);
+                        if constexpr (kOrdered) {
+                            uint32_t lo, hi;
+                            order_bounds(sets_order(ord...), S, d, lo, hi);
+                            ok = ok & (v >= lo) & (v < hi);
+                        }
                         for (uint32_t i = 0; i < d; i++) ok &= S.image[i] != v;
                         if (ok && P.back_off[d] < P.back_off[d + 1]) {
                             const uint32_t vs = adj_start[v];
@@ -164,8 +182,19 @@ __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_c
                     S.ideg[d] = uni(adj_deg[v]);
                     d++;
                     const uint32_t p = P.pivot[d], ps = uni(S.istart[p]);
-                    S.cbase[d] = ps - 64u;
-                    S.end[d] = ps + uni(S.ideg[p]);
+                    if constexpr (kOrdered) {
+                        uint32_t rb = ps, re = ps + uni(S.ideg[p]);
+                        if (sets_order(ord...).trim) {
+                            uint32_t lo, hi;
+                            order_bounds(sets_order(ord...), S, d, lo, hi);
+                            order_trim(nbrs, lo, hi, lane, rb, re);
+                        }
+                        S.cbase[d] = rb - 64u;
+                        S.end[d] = re;
+                    } else {
+                        S.cbase[d] = ps - 64u;
+                        S.end[d] = ps + uni(S.ideg[p]);
+                    }
                     S.mask_lo[d] = 0;
                     S.mask_hi[d] = 0;
                 }
@@ -180,15 +209,13 @@ __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_c
 
 using namespace gnnpe;
 
-extern "C" {
-
-int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
-                      uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+// gnnpe_refine_sets (distinct = false: R) and gnnpe_refine_sets_distinct (D: the ordered kernel, unless the query has no symmetry)
+static int refine_sets_run(const char *who, bool distinct, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                           uint64_t limit, uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
 {
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers, GNNPE_ERR_ARG, "gnnpe_refine_sets: null argument");
-    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED,
-                  "gnnpe_refine_sets: the whole graph must be on the device (gnnpe_load_csr)");
-    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "gnnpe_refine_sets: simple graphs only (gnnpe_set_multigraph_rows was called)");
+    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
+    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
     GNNPE_HIP_TRY(hipSetDevice(c->device));
     *answers = 0;
     if (device_ms) *device_ms = 0.0;
@@ -228,6 +255,9 @@ int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t
     }
     P.back_off[nq] = (uint16_t)mo.back_off[nq];
     for (size_t j = 0; j < mo.back.size(); j++) P.back[j] = (uint8_t)pos_of[mo.back[j]];
+    // the ordering constraints by position; a query without symmetry has none and runs the plain kernel
+    SetsOrder O = {};
+    const uint32_t n_pairs = distinct ? sets_order_from_pairs(gnnpe_host::query_symmetry(q).pairs, pos_of, c->sw.sets_trim, &O) : 0u;
     // start candidates; an empty set anywhere means no embedding
     for (uint32_t u = 0; u < nq; u++)
         if (cnt[u] == 0) return GNNPE_OK;
@@ -262,7 +292,10 @@ int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t
     const bool forced = c->sw.sets_first_shift >= 0 && c->nbr_used + c->n < (1ull << 32);
     const uint32_t w_shift = forced ? (uint32_t)c->sw.sets_first_shift
                                     : sets_first_level_shift(n_cand, c->nbr_used, c->n, c->num_cus, c->n_hub);
-    if (c->sw.debug)
+    if (c->sw.debug && distinct)
+        fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d pairs=%u\n", w_shift, (int)forced, n_cand, c->n_hub,
+                c->num_cus, n_pairs);
+    else if (c->sw.debug)
         fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d\n", w_shift, (int)forced, n_cand, c->n_hub, c->num_cus);
     if (he == hipSuccess && nq > 1) {
         hipLaunchKernelGGL(k_sets_cand_chunks, dim3((n_cand + 256) / 256), dim3(256), 0, c->stream, n_cand, d_cand,
@@ -276,10 +309,16 @@ int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t
         // a resident grid; a single-vertex query needs no more waves than it has items
         uint64_t blocks = (uint64_t)std::max(c->num_cus, 1) * kSetsBlocksPerCu;
         if (nq == 1) blocks = std::min<uint64_t>(blocks, ((uint64_t)(n_cand + 63) / 64 + kSetsWavesPerBlock - 1) / kSetsWavesPerBlock);
-        hipLaunchKernelGGL(k_refine_sets, dim3((uint32_t)blocks), dim3(kBlock), 0, c->stream, P, n_cand, d_cand, item_off, w_shift,
-                           c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),
-                           c->labels.as<uint32_t>(), d_bm, words, (unsigned long long)limit, d_ctr, d_rows,
-                           (unsigned long long)matches_cap);
+        if (n_pairs)
+            hipLaunchKernelGGL((k_refine_sets<true, SetsOrder>), dim3((uint32_t)blocks), dim3(kBlock), 0, c->stream, P, n_cand, d_cand, item_off,
+                               w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),
+                               c->labels.as<uint32_t>(), d_bm, words, (unsigned long long)limit, d_ctr, d_rows,
+                               (unsigned long long)matches_cap, O);
+        else
+            hipLaunchKernelGGL((k_refine_sets<false>), dim3((uint32_t)blocks), dim3(kBlock), 0, c->stream, P, n_cand, d_cand, item_off, w_shift,
+                               c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),
+                               c->labels.as<uint32_t>(), d_bm, words, (unsigned long long)limit, d_ctr, d_rows,
+                               (unsigned long long)matches_cap);
         he = hipGetLastError();
     }
     if (he == hipSuccess && !rc && device_ms) he = hipEventRecord(ev1, c->stream);
@@ -300,10 +339,26 @@ int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t
     if (ev1) (void)hipEventDestroy(ev1);
     (void)hipStreamSynchronize(c->stream);
     if (!rc && he != hipSuccess) {
-        set_error("gnnpe_refine_sets: %s", hipGetErrorString(he));
+        set_error("%s: %s", who, hipGetErrorString(he));
         rc = GNNPE_ERR_HIP;
     }
     return rc;
+}
+
+extern "C" {
+
+int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                      uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+{
+    return refine_sets_run("gnnpe_refine_sets", false, c, query_graph_path, candidate_bitmap, limit, answers, matches, matches_cap,
+                           device_ms);
+}
+
+int gnnpe_refine_sets_distinct(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                               uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+{
+    return refine_sets_run("gnnpe_refine_sets_distinct", true, c, query_graph_path, candidate_bitmap, limit, answers, matches,
+                           matches_cap, device_ms);
 }
 
 }  // extern "C"

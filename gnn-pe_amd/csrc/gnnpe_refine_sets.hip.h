@@ -46,6 +46,68 @@ __device__ __forceinline__ bool row_has(const uint32_t *__restrict__ nbrs, uint3
     return false;
 }
 
+// ---- the ORDERED searches (D(C, limit) of include/gnnpe_online.h: one embedding per distinct subgraph) ------------------------
+// The pairs (a, b) of host/query_symmetry.h ask for f(a) < f(b).  By position in the matching order every pair binds the LATER
+// of its two positions to the image of the earlier one: bit i of gt[d] = the image of position d must be greater than the image
+// of position i < d, bit i of lt[d] = smaller.  Position 0 has no bound.  The ordered kernels take this by value beside the plan.
+struct SetsOrder {
+    uint32_t gt[kSetsMaxQ], lt[kSetsMaxQ];
+    uint32_t trim;  // != 0: a pivot row longer than a chunk is cut to the ids inside the bounds when its depth is entered
+};
+
+// pos_of[query vertex] = position; returns the number of pairs
+template <class Pairs, class PosOf>
+static inline uint32_t sets_order_from_pairs(const Pairs &pairs, const PosOf &pos_of, bool trim, SetsOrder *O)
+{
+    *O = SetsOrder{};
+    O->trim = trim ? 1u : 0u;
+    for (const auto &ab : pairs) {
+        const uint32_t pa = pos_of[ab.first], pb = pos_of[ab.second];
+        if (pa < pb) O->gt[pb] |= 1u << pa; else O->lt[pa] |= 1u << pb;
+    }
+    return (uint32_t)pairs.size();
+}
+
+// the one argument of an ordered kernel's parameter pack
+__device__ __forceinline__ const SetsOrder &sets_order(const SetsOrder &o) { return o; }
+
+// the bounds of position d from the images of the earlier positions: an image v passes if lo <= v < hi.  Wave-uniform.
+__device__ __forceinline__ void order_bounds(const SetsOrder &O, const volatile SetsWave &S, uint32_t d, uint32_t &lo, uint32_t &hi)
+{
+    lo = 0u;
+    hi = 0xFFFFFFFFu;  // (no vertex has this id: a graph has fewer than 2^32 - 1 vertices)
+    for (uint32_t g = uni(O.gt[d]); g; g &= g - 1u) lo = max(lo, uni(S.image[__builtin_ctz(g)]) + 1u);
+    for (uint32_t l = uni(O.lt[d]); l; l &= l - 1u) hi = min(hi, uni(S.image[__builtin_ctz(l)]));
+}
+
+// first index in [b, e) of an ascending row whose entry is >= x, e if there is none.  The whole wave searches: 64 probes spread
+// over the range and one ballot leave a 64th of it, so a row of 4 096 entries takes two loads.  b, e, x and the result are
+// wave-uniform; no lane reads outside [b, e).
+__device__ __forceinline__ uint32_t row_lower_bound(const uint32_t *__restrict__ nbrs, uint32_t b, uint32_t e, uint32_t x, uint32_t lane)
+{
+    while (e - b > 64u) {
+        const uint32_t step = (e - b + 63u) >> 6;  // >= 2
+        const uint32_t idx = b + lane * step;
+        const bool below = idx < e && nbrs[idx] < x;
+        const uint32_t cnt = (uint32_t)__popcll(__ballot(below));  // the row ascends: the probes below x are the first cnt
+        if (cnt == 0) return b;
+        e = min(e, b + cnt * step);
+        b += (cnt - 1u) * step + 1u;
+    }
+    const uint32_t idx = b + lane;
+    const bool below = idx < e && nbrs[idx] < x;
+    return b + (uint32_t)__popcll(__ballot(below));
+}
+
+// the part [b, e) of a pivot row that can hold ids in [lo, hi); only a row longer than a chunk is searched -- a shorter one is one
+// chunk whatever is cut from it, and the lanes' own compare does the rest
+__device__ __forceinline__ void order_trim(const uint32_t *__restrict__ nbrs, uint32_t lo, uint32_t hi, uint32_t lane, uint32_t &b, uint32_t &e)
+{
+    if (e - b <= 64u) return;
+    if (lo != 0u) b = row_lower_bound(nbrs, b, e, lo, lane);
+    if (hi != 0xFFFFFFFFu && e - b > 0u) e = row_lower_bound(nbrs, b, e, hi, lane);
+}
+
 // first-level chunks (of 1 << w_shift entries) in every start candidate's row: the scan's input; entry n_cand = 0 so that the
 // scan's last output is the total
 static __global__ void k_sets_cand_chunks(uint32_t n_cand, const uint32_t *__restrict__ cand, const uint32_t *__restrict__ adj_deg,

@@ -42,6 +42,7 @@ struct Options {
     // --match-page ROWS (needs --all-matches): rows per page
     bool all_matches = false, match_page_given = false;
     uint64_t match_page = 1ull << 20;
+    bool distinct = false;  // --distinct (needs --refine sets): every matching subgraph once (gnnpe_refine_sets_distinct)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
     std::string transport = "rccl";  // --gpus N > 1: "rccl" (ncclSend/ncclRecv over xGMI) or "copy" (device-to-device copies)
@@ -118,9 +119,9 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             printf("%s -f <dataset dir/> -d <data.graph> -m offline -p <partitions> [-l 2] [-e 2]\n"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
-                   "           [--refine start|sets] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
+                   "           [--refine start|sets [--distinct]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
-                   "       in pages of ROWS embeddings (default 1048576)\n",
+                   "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once\n",
                    tool, tool);
             exit(0);
         }
@@ -153,6 +154,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             continue;
         }
         if (a == "--all-matches") { o.all_matches = true; continue; }
+        if (a == "--distinct") { o.distinct = true; continue; }
         if (a == "--allow-large") { o.allow_large = true; continue; }
         if (a == "--timing") { o.timing = true; continue; }
         if (a == "--sidecars") { o.sidecars = true; continue; }

@@ -166,7 +166,8 @@ struct Device {
 // ids -- the reference's candidate_set, ready for its refinement (main.cpp:176-179).  -m online goes on with the
 // refinement on the device (gnnpe_refine; with --refine sets, where the sets are complete, gnnpe_refine_sets, which can
 // also hand back the embeddings: --matches, at most 2^20 of them, or with --all-matches all of them page by page through
-// the match cursor, gnnpe_refine_pages_*) and prints the reference's answer line instead of writing the file.
+// the match cursor, gnnpe_refine_pages_*; with --distinct the _distinct forms, which count and write every matching subgraph
+// once, and a second line `Automorphisms: K`) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -258,7 +259,7 @@ int run_filter(const Options &o)
             typedef int (*open_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t, cursor_t **);
             typedef int (*next_fn)(cursor_t *, uint32_t *, uint64_t *, int *, double *);
             typedef void (*close_fn)(cursor_t *);
-            open_fn pages_open = (open_fn)dlsym(online, "gnnpe_refine_pages_open");
+            open_fn pages_open = (open_fn)dlsym(online, o.distinct ? "gnnpe_refine_pages_open_distinct" : "gnnpe_refine_pages_open");
             next_fn pages_next = (next_fn)dlsym(online, "gnnpe_refine_pages_next");
             close_fn pages_close = (close_fn)dlsym(online, "gnnpe_refine_pages_close");
             if (!pages_open || !pages_next || !pages_close) die("libgnnpe_online.so does not export gnnpe_refine_pages_*");
@@ -286,7 +287,7 @@ int run_filter(const Options &o)
             // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
             typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t *, uint32_t *, uint64_t,
                                           double *);
-            refine_sets_fn refine_sets = (refine_sets_fn)dlsym(online, "gnnpe_refine_sets");
+            refine_sets_fn refine_sets = (refine_sets_fn)dlsym(online, o.distinct ? "gnnpe_refine_sets_distinct" : "gnnpe_refine_sets");
             if (!refine_sets) die("libgnnpe_online.so does not export gnnpe_refine_sets");
             const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
             std::vector<uint32_t> rows((size_t)cap * n_qv);
@@ -306,6 +307,17 @@ int run_filter(const Options &o)
         }
         gnnpe_destroy(ctx);
         printf("Answer Number: %llu Query Time (ms): %g\n", (unsigned long long)answers, ms + refine_ms);
+        if (o.distinct) {
+            // the answer is the number of distinct subgraphs; times the automorphisms it is the number of embeddings
+            typedef int (*symmetry_fn)(const char *, uint64_t *, uint32_t *, uint32_t, uint32_t *);
+            symmetry_fn symmetry = (symmetry_fn)dlsym(online, "gnnpe_host_query_symmetry");
+            if (!symmetry) die("libgnnpe_online.so does not export gnnpe_host_query_symmetry");
+            uint64_t aut = 0;
+            std::vector<uint32_t> pairs((size_t)n_qv * n_qv);
+            uint32_t n_pairs = 0;
+            check(symmetry(o.query_graph.c_str(), &aut, pairs.data(), (uint32_t)(pairs.size() / 2), &n_pairs), "query_symmetry");
+            printf("Automorphisms: %llu\n", (unsigned long long)aut);
+        }
         if (o.timing && sets && o.all_matches)
             fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"match_pages\": %llu, \"paths\": %llu, "
                             "\"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
@@ -375,6 +387,7 @@ int main(int argc, char **argv)
     if (!o.matches_file.empty() && o.refine != "sets") die("--matches needs --refine sets");
     if (o.all_matches && o.matches_file.empty()) die("--all-matches needs --matches FILE");
     if (o.match_page_given && !o.all_matches) die("--match-page needs --all-matches");
+    if (o.distinct && o.refine != "sets") die("--distinct needs --refine sets");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "

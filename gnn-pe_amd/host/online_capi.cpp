@@ -7,6 +7,7 @@
 #include "../../include/gnnpe_online.h"
 #include "graph_loader.h"
 #include "refine.h"
+#include "query_symmetry.h"
 #include "refine_sets.h"
 
 namespace gnnpe {
@@ -46,11 +47,13 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
     return 0;
 }
 
-int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
-                           const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
+// gnnpe_host_refine_sets and gnnpe_host_refine_sets_distinct
+static int host_refine_sets(const char *who, bool distinct, uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
+                            const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                            uint64_t *answers)
 {
     if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers) {
-        gnnpe::set_error("gnnpe_host_refine_sets: null argument");
+        gnnpe::set_error("%s: null argument", who);
         return GNNPE_ERR_ARG;
     }
     gnnpe_host::StaticGraph q, g;
@@ -64,9 +67,53 @@ int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *
     g.offsets.assign(offsets, offsets + n + 1);
     g.neighbors.assign(nbrs, nbrs + offsets[n]);
     g.labels.assign(labels, labels + n);
-    if (gnnpe_host::refine_sets_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &err) != 0) {
+    gnnpe_host::QuerySymmetry sym;
+    if (distinct) sym = gnnpe_host::query_symmetry(q);
+    if (gnnpe_host::refine_sets_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &err,
+                                      distinct ? &sym.pairs : nullptr) != 0) {
         gnnpe::set_error("%s", err.c_str());
         return GNNPE_ERR_ARG;
+    }
+    return 0;
+}
+
+int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                           const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
+{
+    return host_refine_sets("gnnpe_host_refine_sets", false, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit, answers);
+}
+
+int gnnpe_host_refine_sets_distinct(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                    const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
+{
+    return host_refine_sets("gnnpe_host_refine_sets_distinct", true, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit,
+                            answers);
+}
+
+int gnnpe_host_query_symmetry(const char *query_graph_path, uint64_t *n_automorphisms, uint32_t *pairs, uint32_t pairs_cap,
+                              uint32_t *n_pairs)
+{
+    if (!query_graph_path || !n_automorphisms || !n_pairs || (!pairs && pairs_cap)) {
+        gnnpe::set_error("gnnpe_host_query_symmetry: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    int rc = q.load(query_graph_path, &err, true);
+    if (rc != 0) {
+        gnnpe::set_error("%s", err.c_str());
+        return rc;
+    }
+    const gnnpe_host::QuerySymmetry sym = gnnpe_host::query_symmetry(q);
+    *n_automorphisms = sym.n_automorphisms;
+    *n_pairs = (uint32_t)sym.pairs.size();
+    if (sym.pairs.size() > pairs_cap) {
+        gnnpe::set_error("gnnpe_host_query_symmetry: %zu pairs, room for %u", sym.pairs.size(), pairs_cap);
+        return GNNPE_ERR_ARG;
+    }
+    for (size_t k = 0; k < sym.pairs.size(); k++) {
+        pairs[2 * k] = sym.pairs[k].first;
+        pairs[2 * k + 1] = sym.pairs[k].second;
     }
     return 0;
 }

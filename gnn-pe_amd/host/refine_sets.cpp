@@ -16,6 +16,7 @@ struct SetSearch {
     uint64_t words;
     std::vector<uint32_t> order, pivot;       // matching order; an earlier neighbour of order[i] for i >= 1
     std::vector<std::vector<uint32_t>> back;  // the other earlier neighbours of order[i]
+    std::vector<std::vector<uint32_t>> above, below;  // earlier query vertices whose image order[i]'s must be greater / smaller than
     std::vector<uint32_t> image;              // query vertex -> data vertex
     std::vector<uint8_t> used;                // data vertex taken
     uint64_t count = 0, limit;
@@ -41,6 +42,9 @@ struct SetSearch {
             const uint32_t v = g.neighbors[i];
             if (!fits(u, v)) continue;
             bool ok = true;
+            for (uint32_t w : above[depth]) ok &= v > image[w];
+            for (uint32_t w : below[depth]) ok &= v < image[w];
+            if (!ok) continue;
             for (uint32_t w : back[depth])
                 if (!edge(v, image[w])) {
                     ok = false;
@@ -58,7 +62,7 @@ struct SetSearch {
 }  // namespace
 
 int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                      uint64_t limit, uint64_t *answers, std::string *err)
+                      uint64_t limit, uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs)
 {
     const uint32_t nq = query.n;
     if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
@@ -73,9 +77,22 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
     MatchOrder mo;
     if (build_match_order(query, cnt, &mo, err) != 0) return -2;  // (a disconnected query is refused whatever the limit)
     if (limit == 0) return 0;
-    SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<uint32_t>(nq, 0),
-                std::vector<uint8_t>(data.n, 0), 0, limit};
+    SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
+                std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0), std::vector<uint8_t>(data.n, 0), 0, limit};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
+    if (pairs) {
+        // f(a) < f(b) is tested where the later of the two in the order gets its image
+        std::vector<uint32_t> pos_of(nq, 0);
+        for (uint32_t i = 0; i < nq; i++) pos_of[mo.order[i]] = i;
+        for (const auto &ab : *pairs) {
+            if (ab.first >= nq || ab.second >= nq || ab.first == ab.second) {
+                if (err) *err = "refine_sets_count: an ordering pair names a vertex the query does not have";
+                return -2;
+            }
+            if (pos_of[ab.first] < pos_of[ab.second]) s.above[pos_of[ab.second]].push_back(ab.first);
+            else s.below[pos_of[ab.first]].push_back(ab.second);
+        }
+    }
     const uint32_t start = mo.order[0];
     for (uint64_t w = 0; w < words && s.count < limit; w++)
         for (uint32_t bits = bitmap[(size_t)start * words + w]; bits && s.count < limit; bits &= bits - 1) {

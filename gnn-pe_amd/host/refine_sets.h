@@ -9,6 +9,8 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "graph_loader.h"
 
@@ -16,7 +18,10 @@ namespace gnnpe_host {
 
 // bitmap: query.n rows of `words` = ceil(data.n / 32) uint32, bit v of row u set <=> v in C(u) (the layout
 // gnnpe_filter_candidates writes).  Returns 0 and *answers, or <0 with *err (disconnected query graph).
+// pairs (optional): only the maps with f(a) < f(b) for every pair (a, b) are counted -- with the pairs of query_symmetry.h this is
+// D(C, limit), one embedding per distinct subgraph.
 int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                      uint64_t limit, uint64_t *answers, std::string *err);
+                      uint64_t limit, uint64_t *answers, std::string *err,
+                      const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr);
 
 }  // namespace gnnpe_host

@@ -2,7 +2,8 @@
  *
  * gnnpe_host_refine / gnnpe_refine restate the reference (start vertex only) and are frozen: built in round 1 so that
  * `gnnpe_main -m online` can print the reference's answer line.  gnnpe_host_refine_sets / gnnpe_refine_sets (below) restrict
- * every query vertex to its set, for exact mode.  The library is kept out of libgnnpe_hip.so since round 6:
+ * every query vertex to its set, for exact mode; the _distinct forms (ABI version 11) count and list every matching subgraph
+ * once.  The library is kept out of libgnnpe_hip.so since round 6:
  * the offline hot path and its (f) rows link and load without it.  libgnnpe_online.so links against libgnnpe_hip.so (contexts, error text); `gnnpe_main` dlopen()s it for -m online
  * only.  Same conventions as gnnpe_hip.h: 0 = GNNPE_OK, gnnpe_last_error() for the text.
  */
@@ -88,6 +89,42 @@ int gnnpe_refine_pages_next(gnnpe_match_cursor *cursor, uint32_t *host_rows, uin
 int gnnpe_refine_pages_device_ptr(gnnpe_match_cursor *cursor, void **dev_rows, uint32_t *n_query_vertices);
 int gnnpe_refine_pages_info(gnnpe_match_cursor *cursor, uint64_t info[5]);
 void gnnpe_refine_pages_close(gnnpe_match_cursor *cursor);
+
+/* ---- ABI version 11: one embedding per distinct subgraph ---------------------------------------------------------------
+ * R counts EMBEDDINGS, so a query with symmetry reports every occurrence of the pattern |Aut(Q)| times (a triangle six
+ * times, K4 24 times), Aut(Q) being the permutations of the query vertices that keep labels and edges.  The functions
+ * below break the symmetry inside the search instead of leaving the duplicates to the caller.
+ *
+ * gnnpe_host_query_symmetry: |Aut(Q)| (saturated at 2^64 - 1) and the ordering pairs of the Grochow-Kellis construction:
+ *   walk the stabiliser chain in query-vertex id order; for u = 0, 1, ... with O_u the orbit of u under the automorphisms
+ *   that fix 0 .. u-1 pointwise, the pair (u, w) for every other w in O_u, ascending.  A pair (a, b) means "require
+ *   f(a) < f(b)".  For any injective f exactly one of the maps {f o alpha : alpha in Aut(Q)} satisfies every pair, and
+ *   |Aut(Q)| is the product of the |O_u|.  At most nq (nq - 1) / 2 pairs; pairs is pairs_cap x 2 uint32 and may be NULL
+ *   with pairs_cap == 0; *n_pairs is the number of pairs, and with pairs_cap below it the call returns GNNPE_ERR_ARG
+ *   (|Aut| and *n_pairs are still set).  No limit on the query's size; loader errors as from gnnpe_host_refine_sets.
+ *
+ * D(C, limit) = min(limit, number of maps counted by R(C, .) that also satisfy f(a) < f(b) for every such pair).
+ *   - If C is closed under the query's automorphisms -- exact-mode filter output, label/degree bitmaps, all-ones bitmaps
+ *     are -- the maps D counts are exactly one embedding per distinct image subgraph (the set of data edges the query
+ *     edges land on), and D(C, 2^64 - 1) * |Aut(Q)| = R(C, 2^64 - 1).
+ *   - For arbitrary C, D is the constrained count, nothing more: an occurrence whose one representative lies outside
+ *     the sets is not counted although another of its embeddings lies inside.
+ * A query without symmetry has no pairs: D = R, and the device forms run the kernels of the plain functions.
+ *
+ * gnnpe_host_refine_sets_distinct, gnnpe_refine_sets_distinct, gnnpe_refine_pages_open_distinct: arguments, requirements
+ * and refusals of gnnpe_host_refine_sets, gnnpe_refine_sets and gnnpe_refine_pages_open, with D in the place of R; the
+ * rows are the maps D counts.  On the device the compares run inside the search (an image outside its bounds is never
+ * descended into, and a long adjacency row is cut to its bounds by a search before it is walked), so the symmetric part
+ * of the search tree is not visited.  next, device_ptr, info and close serve both kinds of cursor. */
+int gnnpe_host_query_symmetry(const char *query_graph_path, uint64_t *n_automorphisms, uint32_t *pairs, uint32_t pairs_cap,
+                              uint32_t *n_pairs);
+int gnnpe_host_refine_sets_distinct(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                    const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                                    uint64_t *answers);
+int gnnpe_refine_sets_distinct(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                               uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
+int gnnpe_refine_pages_open_distinct(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                     uint64_t limit, uint64_t page_rows, gnnpe_match_cursor **cursor);
 
 #ifdef __cplusplus
 }
