@@ -1,10 +1,20 @@
 // gnnpe_refine_sets.hip.h -- what the two set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip)
-// and the paged k_refine_pages (gnnpe_refine_pages.hip).  The plan by position in the matching order, the per-wave search
-// state in LDS, the row search, the first-level items.
+// and the paged k_refine_pages (gnnpe_refine_pages.hip).  On the device the plan by position in the matching order, the
+// per-wave search state in LDS and every STEP of the search: a chunk's lane test, the descent into a survivor, the decode of a
+// first-level item, the single-vertex item.  Each kernel keeps its own loop, leaf and polling.  On the host the preparation
+// of a query (sets_prepare) and the staging of its first-level items on the device (sets_stage_items).
 #pragma once
 
-#include <algorithm>
+#include <hipcub/hipcub.hpp>
 
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../host/graph_loader.h"
+#include "../host/query_symmetry.h"
+#include "../host/refine.h"
+#include "../host/refine_sets.h"
 #include "gnnpe_common.h"
 
 namespace gnnpe {
@@ -108,6 +118,112 @@ __device__ __forceinline__ void order_trim(const uint32_t *__restrict__ nbrs, ui
     if (hi != 0xFFFFFFFFu && e - b > 0u) e = row_lower_bound(nbrs, b, e, hi, lane);
 }
 
+// ---- the steps of the search ---------------------------------------------------------------------------------------------------
+// Both kernels build a SetsGraph from their own parameters and keep the conventions of the state: S is read and written through
+// `volatile SetsWave &`, every word read from it goes through uni(), and no lane reads LDS that another lane alone wrote (every
+// lane writes every word).  The ordered instantiations pass their SetsOrder as the trailing pack, the plain ones nothing.
+struct SetsGraph {
+    const uint32_t *__restrict__ adj_start, *__restrict__ adj_deg, *__restrict__ nbrs, *__restrict__ labels, *__restrict__ bitmap;
+    uint64_t words;
+};
+
+// the lane's entry v of the chunk [cb, ce) of depth d's pivot row and its test: set bit, label, degree, the ordered bounds, not in
+// the image, every back edge by binary search in the SHORTER of the two rows
+template <bool kOrdered, class... Ord>
+__device__ __forceinline__ bool sets_lane_test(const SetsPlan &P, const volatile SetsWave &S, const SetsGraph &G, uint32_t d, uint32_t cb,
+                                               uint32_t ce, uint32_t lane, uint32_t &v, const Ord &...ord)
+{
+    const uint32_t idx = cb + lane;
+    bool ok = idx < ce;
+    v = ok ? G.nbrs[idx] : 0u;
+    const uint32_t word = G.bitmap[(uint64_t)P.qv[d] * G.words + (v >> 5)], lab = G.labels[v], dv = G.adj_deg[v];
+    ok = ok & (((word >> (v & 31u)) & 1u) != 0) & (lab == P.label[d]) & (dv >= P.degree[d]);
+    if constexpr (kOrdered) {
+        uint32_t lo, hi;
+        order_bounds(sets_order(ord...), S, d, lo, hi);
+        ok = ok & (v >= lo) & (v < hi);
+    }
+    for (uint32_t i = 0; i < d; i++) ok &= S.image[i] != v;
+    if (ok && P.back_off[d] < P.back_off[d + 1]) {
+        const uint32_t vs = G.adj_start[v];
+        for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1] && ok; j++) {
+            const uint32_t b = P.back[j], w = S.image[b], ws = S.istart[b], dw = S.ideg[b];
+            ok = dv <= dw ? row_has(G.nbrs, vs, dv, w) : row_has(G.nbrs, ws, dw, v);
+        }
+    }
+    return ok;
+}
+
+// descend into the lowest survivor of depth d's chunk: the others stay as its mask, the survivor becomes the image of d, and
+// d + 1 is entered over its pivot's row (in the ordered form cut to the bounds) with no survivors yet
+template <bool kOrdered, class... Ord>
+__device__ __forceinline__ void sets_descend(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G, uint32_t &d, unsigned long long m,
+                                             uint32_t lane, const Ord &...ord)
+{
+    const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1;
+    S.mask_lo[d] = (uint32_t)m;
+    S.mask_hi[d] = (uint32_t)(m >> 32);
+    const uint32_t v = uni(G.nbrs[uni(S.cbase[d]) + bit]);
+    S.image[d] = v;
+    S.istart[d] = uni(G.adj_start[v]);
+    S.ideg[d] = uni(G.adj_deg[v]);
+    d++;
+    const uint32_t p = P.pivot[d], ps = uni(S.istart[p]);
+    if constexpr (kOrdered) {
+        uint32_t rb = ps, re = ps + uni(S.ideg[p]);
+        if (sets_order(ord...).trim) {
+            uint32_t lo, hi;
+            order_bounds(sets_order(ord...), S, d, lo, hi);
+            order_trim(G.nbrs, lo, hi, lane, rb, re);
+        }
+        S.cbase[d] = rb - 64u;
+        S.end[d] = re;
+    } else {
+        S.cbase[d] = ps - 64u;
+        S.end[d] = ps + uni(S.ideg[p]);
+    }
+    S.mask_lo[d] = 0;
+    S.mask_hi[d] = 0;
+}
+
+// item q -> (start candidate, chunk of its row): the largest ci with item_off[ci] <= q.  A start candidate of the right label
+// and degree becomes the image of position 0 and depth 1 (its pivot is position 0) is held to the item's chunk; false otherwise.
+__device__ __forceinline__ bool sets_item_decode(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G, uint32_t n_cand,
+                                                 const uint32_t *__restrict__ cand, const uint32_t *__restrict__ item_off, uint32_t w_shift,
+                                                 uint32_t q)
+{
+    uint32_t lo = 0, hi = n_cand;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (item_off[mid] <= q) lo = mid; else hi = mid;
+    }
+    lo = uni(lo);
+    const uint32_t v0 = uni(cand[lo]);
+    const uint32_t s0 = uni(G.adj_start[v0]), d0 = uni(G.adj_deg[v0]);
+    if (uni(G.labels[v0]) != P.label[0] || d0 < P.degree[0]) return false;
+    S.image[0] = v0;
+    S.istart[0] = s0;
+    S.ideg[0] = d0;
+    const uint32_t c0 = s0 + ((q - uni(item_off[lo])) << w_shift);
+    S.cbase[1] = c0 - 64u;
+    S.end[1] = min(c0 + (1u << w_shift), s0 + d0);
+    S.mask_lo[1] = 0;
+    S.mask_hi[1] = 0;
+    return true;
+}
+
+// a single-vertex query: an item is 64 start candidates, lane's index i; its candidate, and the whole test of it
+__device__ __forceinline__ uint32_t sets_single_cand(uint32_t n_cand, const uint32_t *__restrict__ cand, uint32_t i)
+{
+    return i < n_cand ? cand[i] : 0u;
+}
+__device__ __forceinline__ bool sets_single_test(const SetsPlan &P, const SetsGraph &G, uint32_t n_cand, uint32_t i, uint32_t v)
+{
+    return i < n_cand && G.labels[v] == P.label[0] && G.adj_deg[v] >= P.degree[0];
+}
+
+// ---- the host's side of both calls -----------------------------------------------------------------------------------------
 // first-level chunks (of 1 << w_shift entries) in every start candidate's row: the scan's input; entry n_cand = 0 so that the
 // scan's last output is the total
 static __global__ void k_sets_cand_chunks(uint32_t n_cand, const uint32_t *__restrict__ cand, const uint32_t *__restrict__ adj_deg,
@@ -130,6 +246,118 @@ static inline uint32_t sets_first_level_shift(uint32_t n_cand, uint64_t entries,
     uint32_t shift = 6;
     while (shift > 0 && (est >> shift) < target) shift--;
     return shift;
+}
+
+// A query as both calls launch it: the plan and the ordering constraints by position, the start candidates.
+struct SetsQuery {
+    SetsPlan P = {};
+    SetsOrder O = {};      // of a distinct call
+    uint32_t n_pairs = 0;  // 0: the plain kernel (a call that is not distinct, or a query without symmetry)
+    uint32_t nq = 0, n_cand = 0;
+    uint64_t words = 0;
+    std::vector<uint32_t> cand;    // C(start vertex) below n, ascending; sets_stage_items uploads it
+    bool empty = false;            // limit 0 or an empty set: there is nothing to launch
+    uint32_t w_shift = 6;          // log2 of the first-level chunk width (sets_stage_items)
+    bool forced = false;           // ... taken from GNNPE_TESTING=sets_first_shift=K, not from the heuristic
+};
+
+// Everything between a call's own argument checks and the device: the state of the context, the query graph, the set sizes and the
+// matching order -- a disconnected query is refused whatever the limit -- then the plan, the pairs and the start candidates.
+static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *bitmap, bool distinct,
+                               uint64_t limit, SetsQuery *Q)
+{
+    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
+    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    const int rc = q.load(query_graph_path, &err);
+    if (rc != 0) {
+        set_error("%s", err.c_str());
+        return rc;
+    }
+    const uint32_t nq = Q->nq = q.n;
+    GNNPE_REQUIRE(nq >= 1 && nq <= (uint32_t)kSetsMaxQ, GNNPE_ERR_UNSUPPORTED, "query graphs of 1..%d vertices (got %u)", kSetsMaxQ, nq);
+    const uint64_t words = Q->words = ((uint64_t)c->n + 31) / 32;
+    const std::vector<uint64_t> cnt = gnnpe_host::set_sizes(bitmap, words, nq);
+    gnnpe_host::MatchOrder mo;
+    if (gnnpe_host::build_match_order(q, cnt, &mo, &err) != 0) {
+        set_error("%s", err.c_str());
+        return GNNPE_ERR_ARG;
+    }
+    Q->empty = limit == 0 || std::find(cnt.begin(), cnt.end(), 0u) != cnt.end();  // an empty set anywhere means no embedding
+    if (Q->empty) return GNNPE_OK;
+    // plan by position in the order.  P.back holds every query edge: 32 vertices have at most 496 edges, back leaves out the 31
+    // pivot edges, and sizeof(P.back) is 496
+    SetsPlan &P = Q->P;
+    static_assert(sizeof(P.back) == kSetsMaxQ * (kSetsMaxQ - 1) / 2, "one byte per possible query edge");
+    P.nq = nq;
+    std::vector<uint32_t> pos_of(nq, 0);
+    for (uint32_t i = 0; i < nq; i++) pos_of[mo.order[i]] = i;
+    for (uint32_t i = 0; i < nq; i++) {
+        P.label[i] = q.labels[mo.order[i]];
+        P.degree[i] = q.degree(mo.order[i]);
+        P.qv[i] = (uint8_t)mo.order[i];
+        P.pivot[i] = (uint8_t)pos_of[mo.pivot[i]];
+        P.back_off[i] = (uint16_t)mo.back_off[i];
+    }
+    P.back_off[nq] = (uint16_t)mo.back_off[nq];
+    for (size_t j = 0; j < mo.back.size(); j++) P.back[j] = (uint8_t)pos_of[mo.back[j]];
+    // the ordering constraints by position; a query without symmetry has none and runs the plain kernel
+    if (distinct) Q->n_pairs = sets_order_from_pairs(gnnpe_host::query_symmetry(q).pairs, pos_of, c->sw.sets_trim, &Q->O);
+    Q->cand = gnnpe_host::set_members(bitmap, words, mo.order[0], c->n);
+    Q->n_cand = (uint32_t)Q->cand.size();
+    Q->empty = Q->n_cand == 0;
+    return GNNPE_OK;
+}
+
+// the work buffer of a call or a cursor: [counters 32 B | item_off u32 x (n_cand + 1) | cand u32 x n_cand | chunks u32 x (n_cand + 1)]
+struct SetsWork {
+    void *ctr;
+    uint32_t *item_off, *cand, *chunks;
+    static constexpr size_t kCtrBytes = 32;
+    static size_t bytes(uint32_t n_cand) { return kCtrBytes + ((size_t)n_cand * 3 + 2) * 4 + 64; }
+    SetsWork(const DevBuf &b, uint32_t n_cand)
+        : ctr(b.p), item_off(reinterpret_cast<uint32_t *>(b.as<char>() + kCtrBytes)), cand(item_off + n_cand + 1), chunks(cand + n_cand)
+    {
+    }
+};
+
+// a resident grid; a single-vertex query needs no more waves than it has items
+static inline uint32_t sets_grid_blocks(const gnnpe_ctx *c, uint32_t nq, uint32_t n_cand)
+{
+    uint64_t blocks = (uint64_t)std::max(c->num_cus, 1) * kSetsBlocksPerCu;
+    if (nq == 1) blocks = std::min<uint64_t>(blocks, ((uint64_t)(n_cand + 63) / 64 + kSetsWavesPerBlock - 1) / kSetsWavesPerBlock);
+    return (uint32_t)blocks;
+}
+
+// Puts a prepared query on the device, on the context's stream, in the buffers it is handed (the context's for the one-shot call,
+// a cursor's own): the start candidates, the bitmap, zeroed counters, and for nq > 1 the offsets of the first-level items
+// (k_sets_cand_chunks and a scan; item_off[n_cand] is their number).  Chooses Q->w_shift first.  `uploaded`, if given, is recorded
+// between the copies and the kernels.  Waits for nothing.
+static inline int sets_stage_items(gnnpe_ctx *c, SetsQuery *Q, const uint32_t *bitmap, DevBuf &work, DevBuf &bm, DevBuf &tmp,
+                                   hipEvent_t uploaded = nullptr)
+{
+    // GNNPE_TESTING=sets_first_shift=K stands in for the heuristic; the 32-bit item offsets still come first
+    Q->forced = c->sw.sets_first_shift >= 0 && c->nbr_used + c->n < (1ull << 32);
+    Q->w_shift = Q->forced ? (uint32_t)c->sw.sets_first_shift : sets_first_level_shift(Q->n_cand, c->nbr_used, c->n, c->num_cus, c->n_hub);
+    const uint32_t n_cand = Q->n_cand;
+    const size_t bm_bytes = (size_t)Q->nq * Q->words * 4;
+    int rc;
+    if ((rc = work.reserve(SetsWork::bytes(n_cand))) || (rc = bm.reserve(bm_bytes))) return rc;
+    const SetsWork W(work, n_cand);
+    GNNPE_HIP_TRY(hipMemcpyAsync(W.cand, Q->cand.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, c->stream));
+    GNNPE_HIP_TRY(hipMemcpyAsync(bm.p, bitmap, bm_bytes, hipMemcpyHostToDevice, c->stream));
+    GNNPE_HIP_TRY(hipMemsetAsync(W.ctr, 0, SetsWork::kCtrBytes, c->stream));
+    if (uploaded) GNNPE_HIP_TRY(hipEventRecord(uploaded, c->stream));
+    if (Q->nq == 1) return GNNPE_OK;
+    hipLaunchKernelGGL(k_sets_cand_chunks, dim3((n_cand + 256) / 256), dim3(256), 0, c->stream, n_cand, W.cand, c->adj_deg.as<uint32_t>(),
+                       Q->w_shift, W.chunks);
+    size_t tb = 0;
+    GNNPE_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, W.chunks, W.item_off, (int)(n_cand + 1), c->stream));
+    if ((rc = tmp.reserve(tb))) return rc;
+    GNNPE_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, W.chunks, W.item_off, (int)(n_cand + 1), c->stream));
+    return GNNPE_OK;
 }
 
 }  // namespace gnnpe

@@ -14,6 +14,25 @@ namespace gnnpe {
 void set_error(const char *fmt, ...);
 }
 
+// load the query graph, or set the error text and return the loader's code
+static int load_query(const char *path, gnnpe_host::StaticGraph *q)
+{
+    std::string err;
+    const int rc = q->load(path, &err, true);
+    if (rc != 0) gnnpe::set_error("%s", err.c_str());
+    return rc;
+}
+
+static gnnpe_host::StaticGraph graph_from_csr(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels)
+{
+    gnnpe_host::StaticGraph g;
+    g.n = n;
+    g.offsets.assign(offsets, offsets + n + 1);
+    g.neighbors.assign(nbrs, nbrs + offsets[n]);
+    g.labels.assign(labels, labels + n);
+    return g;
+}
+
 extern "C" {
 
 int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
@@ -23,17 +42,10 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
         gnnpe::set_error("gnnpe_host_refine: null argument");
         return GNNPE_ERR_ARG;
     }
-    gnnpe_host::StaticGraph q, g;
+    gnnpe_host::StaticGraph q;
     std::string err;
-    int rc = q.load(query_graph_path, &err, true);
-    if (rc != 0) {
-        gnnpe::set_error("%s", err.c_str());
-        return rc;
-    }
-    g.n = n;
-    g.offsets.assign(offsets, offsets + n + 1);
-    g.neighbors.assign(nbrs, nbrs + offsets[n]);
-    g.labels.assign(labels, labels + n);
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
     const uint64_t words = ((uint64_t)n + 31) / 32;
     std::vector<std::vector<uint32_t>> cand(q.n);
     for (uint32_t u = 0; u < q.n; u++)
@@ -56,17 +68,10 @@ static int host_refine_sets(const char *who, bool distinct, uint32_t n, const ui
         gnnpe::set_error("%s: null argument", who);
         return GNNPE_ERR_ARG;
     }
-    gnnpe_host::StaticGraph q, g;
+    gnnpe_host::StaticGraph q;
     std::string err;
-    int rc = q.load(query_graph_path, &err, true);
-    if (rc != 0) {
-        gnnpe::set_error("%s", err.c_str());
-        return rc;
-    }
-    g.n = n;
-    g.offsets.assign(offsets, offsets + n + 1);
-    g.neighbors.assign(nbrs, nbrs + offsets[n]);
-    g.labels.assign(labels, labels + n);
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
     gnnpe_host::QuerySymmetry sym;
     if (distinct) sym = gnnpe_host::query_symmetry(q);
     if (gnnpe_host::refine_sets_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &err,
@@ -98,12 +103,7 @@ int gnnpe_host_query_symmetry(const char *query_graph_path, uint64_t *n_automorp
         return GNNPE_ERR_ARG;
     }
     gnnpe_host::StaticGraph q;
-    std::string err;
-    int rc = q.load(query_graph_path, &err, true);
-    if (rc != 0) {
-        gnnpe::set_error("%s", err.c_str());
-        return rc;
-    }
+    if (int rc = load_query(query_graph_path, &q)) return rc;
     const gnnpe_host::QuerySymmetry sym = gnnpe_host::query_symmetry(q);
     *n_automorphisms = sym.n_automorphisms;
     *n_pairs = (uint32_t)sym.pairs.size();

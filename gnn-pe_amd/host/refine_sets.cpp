@@ -71,11 +71,8 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
     }
     *answers = 0;
     if (nq == 0) return 0;
-    std::vector<uint64_t> cnt(nq, 0);
-    for (uint32_t u = 0; u < nq; u++)
-        for (uint64_t w = 0; w < words; w++) cnt[u] += (uint64_t)__builtin_popcount(bitmap[(size_t)u * words + w]);
     MatchOrder mo;
-    if (build_match_order(query, cnt, &mo, err) != 0) return -2;  // (a disconnected query is refused whatever the limit)
+    if (build_match_order(query, set_sizes(bitmap, words, nq), &mo, err) != 0) return -2;  // (a disconnected query is refused whatever the limit)
     if (limit == 0) return 0;
     SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
                 std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0), std::vector<uint8_t>(data.n, 0), 0, limit};
@@ -94,15 +91,14 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
         }
     }
     const uint32_t start = mo.order[0];
-    for (uint64_t w = 0; w < words && s.count < limit; w++)
-        for (uint32_t bits = bitmap[(size_t)start * words + w]; bits && s.count < limit; bits &= bits - 1) {
-            const uint32_t v = (uint32_t)(w * 32 + __builtin_ctz(bits));
-            if (v >= data.n || !s.fits(start, v)) continue;
-            s.image[start] = v;
-            s.used[v] = 1;
-            s.extend(1);
-            s.used[v] = 0;
-        }
+    for (uint32_t v : set_members(bitmap, words, start, data.n)) {
+        if (s.count >= limit) break;
+        if (!s.fits(start, v)) continue;
+        s.image[start] = v;
+        s.used[v] = 1;
+        s.extend(1);
+        s.used[v] = 0;
+    }
     *answers = std::min(s.count, limit);
     return 0;
 }

@@ -16,6 +16,27 @@
 
 namespace gnnpe_host {
 
+// cnt[u] = |C(u)|: the set bits of bitmap row u (rows of `words` uint32, as below)
+inline std::vector<uint64_t> set_sizes(const uint32_t *bitmap, uint64_t words, uint32_t nq)
+{
+    std::vector<uint64_t> cnt(nq, 0);
+    for (uint32_t u = 0; u < nq; u++)
+        for (uint64_t w = 0; w < words; w++) cnt[u] += (uint64_t)__builtin_popcount(bitmap[(size_t)u * words + w]);
+    return cnt;
+}
+
+// the members of C(u) below n, ascending (the last word of a row may carry bits past the graph)
+inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words, uint32_t u, uint32_t n)
+{
+    std::vector<uint32_t> out;
+    for (uint64_t w = 0; w < words; w++)
+        for (uint32_t bits = bitmap[(size_t)u * words + w]; bits; bits &= bits - 1) {
+            const uint64_t v = w * 32 + __builtin_ctz(bits);
+            if (v < n) out.push_back((uint32_t)v);
+        }
+    return out;
+}
+
 // bitmap: query.n rows of `words` = ceil(data.n / 32) uint32, bit v of row u set <=> v in C(u) (the layout
 // gnnpe_filter_candidates writes).  Returns 0 and *answers, or <0 with *err (disconnected query graph).
 // pairs (optional): only the maps with f(a) < f(b) for every pair (a, b) are counted -- with the pairs of query_symmetry.h this is
