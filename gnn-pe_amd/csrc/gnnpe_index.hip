@@ -2361,7 +2361,16 @@ static int build_triple_order(gnnpe_ctx *c)
         hipLaunchKernelGGL(k_tx_padj, dim3(grid_for(len)), dim3(kBlock), 0, c->stream, len, poffs, eoff,
                            p > 1 ? pbase : (const uint64_t *)nullptr, c->tx_padj.as<int64_t>());
     // 2. unit records + keys, sorted, gathered, scanned
-    const uint32_t lb = c->vkey_lb, zbits = c->vkey_zb * 3 * e, shift = 3 * lb + zbits, kbits = bits_for(p) + shift;
+    // ensure_vkey fills the vertex words' 3 lb + zb 3e bits up to 64 and knows nothing of the partition field on top (17 .. 32
+    // labels at e = 8: 63 bits).  The key is a packing order only -- any permutation of the units gives a valid tree -- so where the
+    // field does not fit the key leaves out Z-order levels (the low 3e bits) first, and low label bits only where 3 lb alone is too
+    // wide (more than 2^20 labels).  A key that fits is the vertex words' own: both drops 0.
+    const uint32_t pbits = bits_for(p);
+    uint32_t zb = c->vkey_zb, lb = c->vkey_lb;
+    while (zb > 0 && pbits + 3 * lb + zb * 3 * e > 64) zb--;
+    while (pbits + 3 * lb > 64) lb--;  // (pbits <= 33: ten label bits always stay)
+    const uint32_t zdrop = (c->vkey_zb - zb) * 3 * e, ldrop = c->vkey_lb - lb;
+    const uint32_t zbits = zb * 3 * e, shift = 3 * lb + zbits, kbits = pbits + shift;
     GNNPE_REQUIRE(kbits <= 64, GNNPE_ERR_UNSUPPORTED, "triple key needs %u bits", kbits);
     TripX *recs = c->px_recs.as<TripX>(), *sorted = c->px_sorted.as<TripX>();
     uint64_t *pref = c->px_pref.as<uint64_t>();
@@ -2373,7 +2382,7 @@ static int build_triple_order(gnnpe_ctx *c)
                            c->ufirst.as<uint64_t>(), c->uoff.as<uint64_t>(), c->erow.as<uint32_t>(), c->pnbr.as<uint32_t>(),  \
                            c->sorted.as<uint32_t>(), c->slab_begin, c->member.as<uint32_t>(), c->adj_start.as<uint32_t>(),     \
                            c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->nbr_rank.as<uint32_t>(), c->rank.as<uint32_t>(), \
-                           c->tx_cpre.as<uint32_t>(), toff, c->tx_padj.as<int64_t>(), c->vkey.as<uint64_t>(), e, lb, zbits, recs, k_in); \
+                           c->tx_cpre.as<uint32_t>(), toff, c->tx_padj.as<int64_t>(), c->vkey.as<uint64_t>(), e, lb, zbits, ldrop, zdrop, recs, k_in); \
         tb = 0;                                                                                                             \
         GNNPE_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k_in, k_out, v_in, v_out, (int)nu, 0, (int)kbits, c->stream)); \
         if ((rc = c->cub_tmp.reserve(tb))) return rc;                                                                       \

@@ -110,6 +110,9 @@ __global__ void k_tx_padj(uint32_t len, const uint32_t *__restrict__ poffs, cons
 // they fell into.  A c whose row is longer than 64 entries is left out of the walk and taken piece by piece by the whole wave.
 // Non-empty units get {record, key}; empty ones keep the fill's key.  The first path of a unit: the work unit's first output slot
 // (uoff, from the count) + the kept rows of the lanes in front.
+// lb / zbits are the key's label bits per vertex and Z-order bits; ldrop / zdrop (both 0 when the vertex words' own widths fit
+// under the partition field) are the low label bits and the low Z-order bits (whole levels of 3e) the key leaves out, see
+// build_triple_order.
 template <typename KeyT>
 __global__ __launch_bounds__(256) void k_tx_units(uint64_t n_wu, const uint32_t *__restrict__ upair, const uint64_t *__restrict__ ufirst,
                                                   const uint64_t *__restrict__ uoff, const uint32_t *__restrict__ erow,
@@ -119,7 +122,8 @@ __global__ __launch_bounds__(256) void k_tx_units(uint64_t n_wu, const uint32_t 
                                                   const uint32_t *__restrict__ nbr_rank, const uint32_t *__restrict__ rank,
                                                   const uint32_t *__restrict__ cpre, const uint64_t *__restrict__ toff,
                                                   const int64_t *__restrict__ padj, const uint64_t *__restrict__ vkey, uint32_t e, uint32_t lb,
-                                                  uint32_t zbits, TripX *__restrict__ recs, KeyT *__restrict__ keys)
+                                                  uint32_t zbits, uint32_t ldrop, uint32_t zdrop, TripX *__restrict__ recs,
+                                                  KeyT *__restrict__ keys)
 {
     __shared__ uint32_t s_off[4][65], s_st[4][64];
     __shared__ uint64_t s_step[4][64];
@@ -207,8 +211,9 @@ __global__ __launch_bounds__(256) void k_tx_units(uint64_t n_wu, const uint32_t 
     const uint64_t ubase = toff_w + cpre_q;
     // key: partition and the words of s and b are the wave's, c is the lane's
     const uint64_t lmask = (1ull << lb) - 1ull;
-    const uint64_t lab = ((((((uint64_t)part << lb) | ((ws >> 32) & lmask)) << lb) | ((wb >> 32) & lmask)) << lb) | ((wc >> 32) & lmask);
-    const uint64_t z = ((ws & 0xffffffffull) << (2u * e)) | ((wb & 0xffffffffull) << e) | (wc & 0xffffffffull);
+    const uint32_t lsh = 32u + ldrop;
+    const uint64_t lab = ((((((uint64_t)part << lb) | ((ws >> lsh) & lmask)) << lb) | ((wb >> lsh) & lmask)) << lb) | ((wc >> lsh) & lmask);
+    const uint64_t z = (((ws & 0xffffffffull) << (2u * e)) | ((wb & 0xffffffffull) << e) | (wc & 0xffffffffull)) >> zdrop;
     const KeyT key = (KeyT)((lab << zbits) | z);
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     if (valid && !hub && cnt) {
