@@ -1013,7 +1013,11 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
         // k_vde wrote the per-vertex records when it ran (run_vde) and the slab's pair offsets have not changed since
         const bool vinfo_current = c->vinfo_fused && c->vinfo_gen == c->slab_struct_gen && c->have_vde;
         c->vinfo_fused = false;  // (good for one count: the next gnnpe_vde decides again)
-        if (c->sw.debug) fprintf(stderr, "[count] vertex records: %s\n", vinfo_current ? "written by k_vde" : "k_pack_vinfo");
+        // a refresh gathers from the compact vde table: only k_hub_records reads the per-vertex records then (rank and vde), so where
+        // k_vde has not written them already (a vde unpack after it: every step at N > 1; a fill that refreshes) nobody packs them
+        const bool vinfo_needed = !reuse || c->n_hub != 0;
+        if (c->sw.debug)
+            fprintf(stderr, "[count] vertex records: %s\n", vinfo_current ? "written by k_vde" : vinfo_needed ? "k_pack_vinfo" : "not needed");
         // k_start_scan's status words + ticket are zeroed by the row kernel (count_paths passes them through the context)
         uint32_t *clear_words = c->clear_words;
         const uint32_t n_clear = c->n_clear;
@@ -1023,7 +1027,6 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
         const uint32_t n_heads_words = c->n_heads_words;
         if (reuse && launch && heads_words) c->heads_clean = true;
         const dim3 gridf((unsigned)std::min<uint64_t>(((uint64_t)c->n_held + 15) / 16, 1u << 30));
-        [[maybe_unused]] const bool refresh_from_blocks = diag_int("GNNPE_REFRESH_SHAPE", 0) == 1;
         int rows_ilp = (int)diag_int("GNNPE_ROWS_ILP", 4);  // (diagnostic builds: 1 | 2 | 8 for the A/B of DESIGN 3.2)
         if (rows_ilp != 1 && rows_ilp != 2 && rows_ilp != 8) rows_ilp = 4;
         const dim3 gridk((unsigned)std::min<uint64_t>(((uint64_t)c->n_held + 4 * rows_ilp - 1) / (4 * rows_ilp), 1u << 30));
@@ -1033,11 +1036,11 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
                        c->vinfo.as<double>(), c->revpos.as<uint32_t>(), c->rblock.as<uint32_t>(),                   \
                        c->rrecs.as<char>(), c->rpairs.as<RankedPair>(), c->rpos.as<uint8_t>(), clear_words, n_clear, \
                        (uint32_t)diag_int("GNNPE_ROWS_PAIR8", 0))
-#define GNNPE_RFS(EE, PK, FB)                                                                                       \
-    hipLaunchKernelGGL((k_rows_refresh<EE, PK, 4, FB>), gridf, block, 0, c->stream, c->n_held, held,                \
-                       c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(),              \
-                       c->vinfo.as<double>(), c->rpos.as<uint8_t>(), c->rblock.as<uint32_t>(), c->rrecs.as<char>(), \
-                       heads_words, n_heads_words)
+#define GNNPE_RF(EE, PK)                                                                                            \
+    hipLaunchKernelGGL((k_rows_refresh<EE, PK, 4>), gridf, block, 0, c->stream, c->n_held, held,                    \
+                       c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), vde,         \
+                       c->rpos.as<uint8_t>(), c->rblock.as<uint32_t>(), c->rrecs.as<char>(), heads_words,           \
+                       n_heads_words)
 #ifdef GNNPE_DIAG
 #define GNNPE_RRK(EE, PK)                                                                                           \
     do {                                                                                                            \
@@ -1052,17 +1055,12 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
                                c->rrecs.as<char>(), c->rpairs.as<RankedPair>(), c->rpos.as<uint8_t>());             \
         }                                                                                                           \
     } while (0)
-#define GNNPE_RF(EE, PK)                                                                                            \
-    do {                                                                                                            \
-        if (refresh_from_blocks) GNNPE_RFS(EE, PK, true); else GNNPE_RFS(EE, PK, false);                            \
-    } while (0)
 #else
 #define GNNPE_RRK(EE, PK) GNNPE_RRM(EE, PK, 4)
-#define GNNPE_RF(EE, PK) GNNPE_RFS(EE, PK, false)
 #endif
 #define GNNPE_RR(EE)                                                                                               \
     do {                                                                                                           \
-        if (!vinfo_current)                                                                                        \
+        if (vinfo_needed && !vinfo_current)                                                                        \
             hipLaunchKernelGGL((k_pack_vinfo<EE>), dim3(grid_for(c->n)), block, 0, c->stream, c->n, vde,            \
                                c->rank.as<uint32_t>(), c->slab_begin, c->slab_end, c->poffs.as<uint32_t>(),         \
                                c->vinfo.as<double>());                                                              \
@@ -1078,7 +1076,6 @@ static int build_ranked(gnnpe_ctx *c, uint64_t ne)
 #undef GNNPE_RR
 #undef GNNPE_RRK
 #undef GNNPE_RF
-#undef GNNPE_RFS
 #undef GNNPE_RRM
         // diagnostic launches beside the real one (GNNPE_ROWS_PROBE, scripts/count_ab.py): pieces of the kernel on their own,
         // into scratch copies of its outputs; whole graph on one device, e = 2, packed ids only

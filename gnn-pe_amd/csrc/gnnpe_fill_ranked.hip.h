@@ -12,6 +12,10 @@
 // Rows longer than 64 ("hub" rows; Test/data_graph.graph has one of degree 168) keep id order: their records are
 // {id, rank, vde}, their pair counts come from a per-row sort of the ranks (hipCUB segmented sort, hubs only) and the
 // emit kernel streams them with a ballot compaction -- in the same launch, pair by pair, so one graph may mix both.
+//
+// The blocks' STRUCTURE (which record sits where, with which id word) depends on the graph and the order only: the full count
+// (k_rows_rank_multi, from the per-vertex records {vde, rank, pair offset}) leaves a position byte per adjacency entry, and a later
+// count on the same structure only writes the embeddings again (k_rows_refresh, from the compact vde table).
 #pragma once
 
 #include "gnnpe_dpp.hip.h"
@@ -248,21 +252,24 @@ __global__ __launch_bounds__(256) void k_rows_rank_multi(uint32_t n_held, const 
 // k_rows_rank_multi (K rows per wave, the K rows' loads batched, no load under a lane mask, every gathered value waited for once):
 // the entry's id comes from the adjacency row, its record's position from rpos (a byte per entry, left by the full count), so the
 // WHOLE record {id | id-position, vde} is stored again -- the id word with the bits it had -- and the blocks' lines are written in
-// full as the full count writes them, never read.  One gather per entry from the per-vertex records (the vde half only).
-// FROM_BLOCKS (diagnostic builds, GNNPE_REFRESH_SHAPE=1: the shape this one was measured against): a lane per record in block
-// order reads the record's own id word and stores the E doubles in place -- no position array, but the blocks are read (as many
-// lines again as the gathers) and 16 of every 20 bytes of a line are written.
+// full as the full count writes them, never read.  One gather per entry from the COMPACT vde table (n x E doubles), not from the
+// per-vertex records that the full count gathers: half the bytes at E = 2, so twice the share of the table that an L2 holds, and
+// nobody has to write those records for a refresh (profiles/refresh_entries.txt: 0.417 -> 0.370 ms at config 3).
+// Two other shapes were measured against this one and lost: block-driven (a lane per record in block order, the id read from the
+// record itself: profiles/count_reuse_ab.txt) and entry-driven (a lane per item of an 8-byte-per-entry list {id word, record
+// offset} left by the full count, flat over the entries, the headers by a lane-per-row prologue: profiles/refresh_entries.txt --
+// fewer waves and one round trip less, but the list is more bytes to read than the rows it replaces and the headers arrive as
+// partial lines from another wave).
 // (clear_words: the emit kernel's ticket heads, which k_start_scan zeroes in a full count.)
-template <int E, bool PACKED, int K, bool FROM_BLOCKS>
+template <int E, bool PACKED, int K>
 __global__ __launch_bounds__(256) void k_rows_refresh(uint32_t n_held, const uint32_t *__restrict__ held,
                                                       const uint32_t *__restrict__ adj_start,
                                                       const uint32_t *__restrict__ adj_deg,
-                                                      const uint32_t *__restrict__ nbrs, const double *__restrict__ vinfo,
+                                                      const uint32_t *__restrict__ nbrs, const double *__restrict__ vde,
                                                       const uint8_t *__restrict__ rpos, const uint32_t *__restrict__ rblock,
                                                       char *__restrict__ recs, uint32_t *__restrict__ clear_words, uint32_t n_clear)
 {
     typedef typename RecOf<E, PACKED>::type Rec;
-    constexpr int S = GNNPE_VINFO_STRIDE(E);
     const unsigned lane = lane_id();
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_clear; i += gridDim.x * blockDim.x) clear_words[i] = 0u;
     const uint64_t w = (uint64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -281,26 +288,17 @@ __global__ __launch_bounds__(256) void k_rows_refresh(uint32_t n_held, const uin
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const uint32_t j = d[k] ? min(lane, d[k] - 1u) : 0u;  // (idle lanes re-read the row's last entry)
-        if constexpr (FROM_BLOCKS) {
-            // (a row without entries has no block: it reads the first word of the buffer)
-            const char *src = d[k] ? recs + (uint64_t)blk[k] * kRowAlign + 8 * E + (uint64_t)j * sizeof(Rec) : recs;
-            const uint32_t first = *reinterpret_cast<const uint32_t *>(src);
-            u[k] = d[k] ? (PACKED ? first & ((1u << kPackedIdBits) - 1u) : first) : 0u;
-            pos[k] = j;
-        } else {
-            const uint32_t q = d[k] ? st[k] + j : 0u;
-            const uint32_t uq = nbrs[q];
-            u[k] = d[k] ? uq : 0u;  // (a row without entries gathers vertex 0's record: entry 0 may not exist)
-            pos[k] = min((uint32_t)rpos[q], d[k] ? d[k] - 1u : 0u);  // (a position never leaves its block, whatever the byte holds)
-        }
+        const uint32_t q = d[k] ? st[k] + j : 0u;
+        const uint32_t uq = nbrs[q];
+        u[k] = d[k] ? uq : 0u;  // (a row without entries gathers vertex 0's embedding: entry 0 may not exist)
+        pos[k] = min((uint32_t)rpos[q], d[k] ? d[k] - 1u : 0u);  // (a position never leaves its block, whatever the byte holds)
     }
     double vu[K][E], hb[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        const double *vi = vinfo + (uint64_t)u[k] * S;
 #pragma unroll
-        for (int j = 0; j < E; j++) vu[k][j] = vi[j];
-        hb[k] = vinfo[(uint64_t)b[k] * S + min(lane, (unsigned)(E - 1))];  // header: vde of the row's vertex
+        for (int j = 0; j < E; j++) vu[k][j] = vde[(uint64_t)u[k] * E + j];
+        hb[k] = vde[(uint64_t)b[k] * E + min(lane, (unsigned)(E - 1))];  // header: vde of the row's vertex
     }
     // every gathered value is waited for HERE, once (k_rows_rank_multi's comment)
 #pragma unroll
@@ -316,22 +314,16 @@ __global__ __launch_bounds__(256) void k_rows_refresh(uint32_t n_held, const uin
         char *const base = recs + (uint64_t)blk[k] * kRowAlign;
         if (lane < (unsigned)E) reinterpret_cast<double *>(base)[lane] = hb[k];
         if (lane < du) {
-            Rec *const dst = reinterpret_cast<Rec *>(base + 8 * E) + pos[k];
-            if constexpr (FROM_BLOCKS) {
-#pragma unroll
-                for (int j = 0; j < E; j++) dst->vde[j] = vu[k][j];
+            Rec rec;
+            if constexpr (PACKED) {
+                rec.idp = u[k] | (lane << kPackedIdBits);
             } else {
-                Rec rec;
-                if constexpr (PACKED) {
-                    rec.idp = u[k] | (lane << kPackedIdBits);
-                } else {
-                    rec.id = u[k];
-                    rec.aux = lane;
-                }
-#pragma unroll
-                for (int j = 0; j < E; j++) rec.vde[j] = vu[k][j];
-                *dst = rec;
+                rec.id = u[k];
+                rec.aux = lane;
             }
+#pragma unroll
+            for (int j = 0; j < E; j++) rec.vde[j] = vu[k][j];
+            reinterpret_cast<Rec *>(base + 8 * E)[pos[k]] = rec;
         }
     }
 }

@@ -3,10 +3,10 @@ G(1M, 10M), e = 2, one context, one pair of output buffers, the cases alternatin
     off     GNNPE_COUNT_REUSE=0: every count builds pair records, record order, start records and the total (the code path of the
             releases before the reuse: k_rows_rank_multi + k_start_scan)
     on      the default: counts after the first refresh the embeddings (k_rows_refresh), nothing else
-    blocks  GNNPE_REFRESH_SHAPE=1: the refresh in its block-driven shape (a lane per record in block order, the id read from the record)
+(The block-driven refresh that profiles/count_reuse_ab.txt compares -- a lane per record in block order -- lost and is gone with its knob.)
 Per round and case: device time (events) of vde + count alone and of whole enqueued steps (vde, enqueue-only count, capped fill), ten
 each.  Diagnostic build (scripts/_diag.py).
-    python scripts/count_reuse_ab.py [off on blocks]"""
+    python scripts/count_reuse_ab.py [off on]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -15,9 +15,9 @@ import numpy as np, torch
 import gnnpe_amd  # noqa: F401
 from gnnpe_amd import binding, synth
 
-CASES = {"off": {"GNNPE_COUNT_REUSE": "0"}, "on": {}, "blocks": {"GNNPE_REFRESH_SHAPE": "1"}}
-KEYS = ["GNNPE_COUNT_REUSE", "GNNPE_REFRESH_SHAPE"]
-cases = sys.argv[1:] or ["off", "on", "blocks"]
+CASES = {"off": {"GNNPE_COUNT_REUSE": "0"}, "on": {}}
+KEYS = ["GNNPE_COUNT_REUSE"]
+cases = sys.argv[1:] or ["off", "on"]
 ROUNDS, ITERS = int(os.environ.get("GNNPE_AB_ROUNDS", "3")), int(os.environ.get("GNNPE_AB_ITERS", "10"))  # keep both small under --pmc
 
 g = synth.gnm_graph(1_000_000, 10_000_000)
