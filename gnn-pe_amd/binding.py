@@ -124,7 +124,8 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 11  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 12  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
 
@@ -149,6 +150,9 @@ ONLINE_SIGNATURES = {
     "gnnpe_host_refine_sets_distinct": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
     "gnnpe_refine_sets_distinct": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _u32p, C.c_uint64, _f64p]),
     "gnnpe_refine_pages_open_distinct": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
+    "gnnpe_host_refine_sets_mode": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p]),
+    "gnnpe_refine_sets_mode": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_refine_pages_open_mode": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
 }
 _online = None
 
@@ -373,16 +377,26 @@ def host_refine(g, query_path, bitmap, limit=0xFFFFFFFF):
     return out.value
 
 
-def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF, distinct=False):
+def match_mode(distinct=False, induced=False):
+    """the mode word of the gnnpe_*_mode functions"""
+    return (MATCH_DISTINCT if distinct else 0) | (MATCH_INDUCED if induced else 0)
+
+
+def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF, distinct=False, induced=False):
     """Set-restricted refinement on the host (include/gnnpe_online.h, R(C, limit)): the embeddings whose every image lies in its
-    query vertex's set, counted up to `limit`.  distinct=True: D(C, limit), one embedding per distinct subgraph."""
+    query vertex's set, counted up to `limit`.  distinct=True: D(C, limit), one embedding per distinct subgraph.  induced=True:
+    I(C, limit) (with distinct ID): only the maps that send non-adjacent query vertices to non-adjacent data vertices."""
     lib = load()
     out = C.c_uint64()
     o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
     bm = _np(bitmap, np.uint32)
-    fn = load_online().gnnpe_host_refine_sets_distinct if distinct else load_online().gnnpe_host_refine_sets
-    rc = fn(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(), _ptr(bm, _u32p), int(limit),
-            C.byref(out))
+    if induced:
+        rc = load_online().gnnpe_host_refine_sets_mode(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
+                                                       _ptr(bm, _u32p), int(limit), match_mode(distinct, induced), C.byref(out))
+    else:
+        fn = load_online().gnnpe_host_refine_sets_distinct if distinct else load_online().gnnpe_host_refine_sets
+        rc = fn(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(), _ptr(bm, _u32p), int(limit),
+                C.byref(out))
     if rc:
         raise GnnpeError(lib.gnnpe_last_error().decode())
     return out.value
@@ -555,19 +569,23 @@ class MatchCursor:
     device=False rows is a fresh np.uint32 array of n_rows x n_query_vertices; with device=True it is a zero-copy view of the
     cursor's device page (`torch.as_tensor(rows, device=...)` shares it: int32 words holding the uint32 ids, like
     OutputPool.ids_tensor), valid until the next next() or close().  distinct=True: one embedding per distinct subgraph
-    (gnnpe_refine_pages_open_distinct).  Loading another graph into the engine invalidates the
+    (gnnpe_refine_pages_open_distinct); induced=True: induced matches only (gnnpe_refine_pages_open_mode).  Loading another graph into the engine invalidates the
     cursor: next() raises.  Engine.close() closes the engine's open cursors."""
 
     INFO_FIELDS = ("pages", "rows", "suspended_waves", "items_left", "slots")
 
-    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False):
+    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
         self.eng, self.lib, self.h = eng, load_online(), None
         bm = _np(bitmap, np.uint32)
         self.page_rows, self.device = int(page_rows), bool(device)
         self.done = False
         h = C.c_void_p()
-        open_fn = self.lib.gnnpe_refine_pages_open_distinct if distinct else self.lib.gnnpe_refine_pages_open
-        eng._ck(open_fn(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows, C.byref(h)))
+        if induced:
+            eng._ck(self.lib.gnnpe_refine_pages_open_mode(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows,
+                                                          match_mode(distinct, induced), C.byref(h)))
+        else:
+            open_fn = self.lib.gnnpe_refine_pages_open_distinct if distinct else self.lib.gnnpe_refine_pages_open
+            eng._ck(open_fn(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows, C.byref(h)))
         self.h = h
         ptr, nq = C.c_void_p(), C.c_uint32()
         eng._ck(self.lib.gnnpe_refine_pages_device_ptr(self.h, C.byref(ptr), C.byref(nq)))
@@ -833,10 +851,11 @@ class Engine:
         self._ck(load_online().gnnpe_refine(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out), C.byref(ms)))
         return out.value, ms.value
 
-    def refine_sets(self, query_path, bitmap, limit=0xFFFFFFFF, matches_cap=0, distinct=False):
+    def refine_sets(self, query_path, bitmap, limit=0xFFFFFFFF, matches_cap=0, distinct=False, induced=False):
         """Set-restricted refinement on the device (gnnpe_refine_sets): (answers, device ms), or with matches_cap > 0
         (answers, device ms, matches) -- matches[k, u] = image of query vertex u in the k-th embedding kept,
-        min(answers, matches_cap) rows.  distinct=True: gnnpe_refine_sets_distinct, one embedding per distinct subgraph."""
+        min(answers, matches_cap) rows.  distinct=True: gnnpe_refine_sets_distinct, one embedding per distinct subgraph.
+        induced=True: gnnpe_refine_sets_mode with GNNPE_MATCH_INDUCED, induced matches only."""
         out, ms = C.c_uint64(), C.c_double()
         bm = _np(bitmap, np.uint32)
         cap = min(int(matches_cap), int(limit))
@@ -844,22 +863,27 @@ class Engine:
         if matches_cap > 0:
             nq = bm.shape[0] if bm.ndim == 2 else bm.size // ((self.n + 31) // 32)
             rows = np.zeros((max(cap, 1), nq), np.uint32)
-        fn = load_online().gnnpe_refine_sets_distinct if distinct else load_online().gnnpe_refine_sets
-        self._ck(fn(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out),
-                    _ptr(rows, _u32p) if rows is not None else None, cap, C.byref(ms)))
+        if induced:
+            self._ck(load_online().gnnpe_refine_sets_mode(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit),
+                                                          match_mode(distinct, induced), C.byref(out),
+                                                          _ptr(rows, _u32p) if rows is not None else None, cap, C.byref(ms)))
+        else:
+            fn = load_online().gnnpe_refine_sets_distinct if distinct else load_online().gnnpe_refine_sets
+            self._ck(fn(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), C.byref(out),
+                        _ptr(rows, _u32p) if rows is not None else None, cap, C.byref(ms)))
         if rows is None:
             return out.value, ms.value
         return out.value, ms.value, rows[:min(out.value, cap)]
 
-    def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False):
+    def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
         """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open), or with distinct=True over the ones
-        gnnpe_refine_sets_distinct counts."""
-        return MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct)
+        gnnpe_refine_sets_distinct counts; induced=True keeps the induced matches only (gnnpe_refine_pages_open_mode)."""
+        return MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct, induced=induced)
 
-    def match_pages(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False):
+    def match_pages(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
         """Generator over the pages of a MatchCursor: every embedding inside the sets exactly once, up to `limit`, at most
         page_rows per page (an empty last page is not yielded).  The cursor is closed when the generator ends or is dropped."""
-        cur = MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct)
+        cur = MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct, induced=induced)
         try:
             done = False
             while not done:

@@ -26,7 +26,8 @@
 //
 // Resources (gfx950, -O3): 53 VGPRs (k_refine_sets: 30), no scratch, 896 B of LDS per wave (3 584 B per workgroup) as
 // k_refine_sets; a suspend slot is 912 B of global memory per resident wave (3.6 MiB on 256 CUs).  The ordered instantiation
-// (gnnpe_refine_pages_open_distinct) has 58 VGPRs and no scratch; slot and LDS are the same.
+// (gnnpe_refine_pages_open_distinct) has 58 VGPRs and no scratch; slot and LDS are the same.  The two induced instantiations
+// (gnnpe_refine_pages_open_mode with GNNPE_MATCH_INDUCED): profiles/online_induced.txt.
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_refine_sets.hip.h"
 
@@ -47,11 +48,14 @@ struct PagesSlot {  // saved state of one wave
     uint32_t w[kWaveWords];  // the SetsWave words of depths 0 .. depth
 };
 
-// One kernel, two instantiations.  k_refine_pages<false> is the plain search: the parameter pack is empty, nothing below that is
+// One kernel, four instantiations.  k_refine_pages<false> is the plain search: the parameter pack is empty, nothing below that is
 // `if constexpr (kOrdered)` exists (here and in the shared steps), and the code is what it was before the ordered form existed.
 // k_refine_pages<true, SetsOrder> is the ordered search (D(C, limit): one embedding per distinct subgraph): one more by-value
 // argument, the bounds of SetsOrder in every chunk's test, and the long pivot rows trimmed to them.  The bounds are
 // derived from the images, which a suspended wave saves and restores: the slot holds nothing new.
+// k_refine_pages<false, SetsNon> and k_refine_pages<true, SetsOrder, SetsNon> add the induced test of sets_lane_test (SetsNon, the
+// last by-value argument).  It reads the images too, so the slot is the same again, and the leftover leaf mask of a resumed wave
+// holds lanes that passed it: they are emitted without a test, as ever.
 template <bool kOrdered, class... Ord>
 __global__ __launch_bounds__(kBlock) void k_refine_pages(SetsPlan P, uint32_t n_cand, const uint32_t *__restrict__ cand,
                                                         const uint32_t *__restrict__ item_off, uint32_t n_items, uint32_t w_shift,
@@ -224,15 +228,15 @@ void gnnpe_refine_pages_close(gnnpe_match_cursor *cur)
 
 }  // extern "C"
 
-// gnnpe_refine_pages_open (distinct = false) and gnnpe_refine_pages_open_distinct
-static int refine_pages_open(const char *who, bool distinct, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+// gnnpe_refine_pages_open (mode 0), gnnpe_refine_pages_open_distinct (GNNPE_MATCH_DISTINCT) and gnnpe_refine_pages_open_mode
+static int refine_pages_open(const char *who, uint32_t mode, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
                              uint64_t limit, uint64_t page_rows, gnnpe_match_cursor **out)
 {
     GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && out, GNNPE_ERR_ARG, "%s: null argument", who);
     *out = nullptr;
     GNNPE_REQUIRE(page_rows > 0, GNNPE_ERR_ARG, "%s: page_rows must be at least 1", who);
     SetsQuery Q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, distinct, limit, &Q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q);
     if (rc) return rc;
     gnnpe_match_cursor *cur = new gnnpe_match_cursor();
     struct Guard {  // every early return below closes the cursor unless it was handed out
@@ -282,13 +286,20 @@ extern "C" {
 int gnnpe_refine_pages_open(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                             uint64_t page_rows, gnnpe_match_cursor **out)
 {
-    return refine_pages_open("gnnpe_refine_pages_open", false, c, query_graph_path, candidate_bitmap, limit, page_rows, out);
+    return refine_pages_open("gnnpe_refine_pages_open", 0u, c, query_graph_path, candidate_bitmap, limit, page_rows, out);
 }
 
 int gnnpe_refine_pages_open_distinct(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                                      uint64_t page_rows, gnnpe_match_cursor **out)
 {
-    return refine_pages_open("gnnpe_refine_pages_open_distinct", true, c, query_graph_path, candidate_bitmap, limit, page_rows, out);
+    return refine_pages_open("gnnpe_refine_pages_open_distinct", GNNPE_MATCH_DISTINCT, c, query_graph_path, candidate_bitmap, limit,
+                             page_rows, out);
+}
+
+int gnnpe_refine_pages_open_mode(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                                 uint64_t page_rows, uint32_t mode, gnnpe_match_cursor **out)
+{
+    return refine_pages_open("gnnpe_refine_pages_open_mode", mode, c, query_graph_path, candidate_bitmap, limit, page_rows, out);
 }
 
 int gnnpe_refine_pages_next(gnnpe_match_cursor *cur, uint32_t *host_rows, uint64_t *n_rows, int *done, double *device_ms)
@@ -309,12 +320,15 @@ int gnnpe_refine_pages_next(gnnpe_match_cursor *cur, uint32_t *host_rows, uint64
     GNNPE_HIP_TRY(hipMemsetAsync(d_ctr, 0, kPagesPerLaunchBytes, c->stream));
     GNNPE_HIP_TRY(hipEventRecord(cur->ev0, c->stream));
     auto launch = [&](auto... ord) {
-        hipLaunchKernelGGL((k_refine_pages<sizeof...(ord) != 0, decltype(ord)...>), dim3(cur->blocks), dim3(kBlock), 0, c->stream, Q.P, Q.n_cand,
+        hipLaunchKernelGGL((k_refine_pages<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(cur->blocks), dim3(kBlock), 0, c->stream, Q.P, Q.n_cand,
                            W.cand, W.item_off, cur->n_items, Q.w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(),
                            c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), cur->bitmap.as<uint32_t>(), Q.words, d_ctr,
                            cur->slots.as<PagesSlot>(), cur->page.as<uint32_t>(), (unsigned long long)rows_now, ord...);
     };
-    Q.n_pairs ? launch(Q.O) : launch();
+    if (Q.n_non)
+        Q.n_pairs ? launch(Q.O, Q.N) : launch(Q.N);
+    else
+        Q.n_pairs ? launch(Q.O) : launch();
     GNNPE_HIP_TRY(hipGetLastError());
     GNNPE_HIP_TRY(hipEventRecord(cur->ev1, c->stream));
     GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned, d_ctr, sizeof(PagesCounters), hipMemcpyDeviceToHost, c->stream));

@@ -26,6 +26,10 @@
 //     lo <= v < hi to its test; when a depth is entered over a pivot row longer than a chunk, the row is first cut to the
 //     part that can hold such ids by a wave-wide search (row_lower_bound: 64 probes and a ballot per step).  31 VGPRs, no
 //     scratch; the plain instantiation has none of it (30 VGPRs).
+//   * induced form (gnnpe_refine_sets_mode with GNNPE_MATCH_INDUCED: I(C, limit) and ID(C, limit)): per position a mask of the
+//     earlier positions that are no query neighbours (SetsNon).  A lane that passed every other test searches each of their
+//     images' rows, or its own, whichever is shorter, and fails if the edge is there: a subtree is cut at its first wrong vertex.
+//     Two more instantiations, plain and ordered; the two above hold none of it.  Figures: profiles/online_induced.txt.
 // host/refine_sets.cpp is the host form.  The paged form of this search (gnnpe_refine_pages.hip) takes the same steps, and every
 // step exists once, in gnnpe_refine_sets.hip.h: the lane test of a chunk, the descent, the item decode and the single-vertex item
 // on the device; the preparation of a query and the staging of its items on the host.  This file keeps what is the one-shot
@@ -42,10 +46,12 @@ struct SetsCounters {  // one 32-byte block, zeroed before every launch
 };
 static_assert(sizeof(SetsCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
 
-// One kernel, two instantiations.  k_refine_sets<false> is the plain search: the parameter pack is empty, nothing below that is
+// One kernel, four instantiations.  k_refine_sets<false> is the plain search: the parameter pack is empty, nothing below that is
 // `if constexpr (kOrdered)` exists (here and in the shared steps), and the code is what it was before the ordered form existed.
 // k_refine_sets<true, SetsOrder> is the ordered search (D(C, limit): one embedding per distinct subgraph): one more by-value
 // argument, the bounds of SetsOrder in every chunk's test, and the long pivot rows trimmed to them.
+// k_refine_sets<false, SetsNon> and k_refine_sets<true, SetsOrder, SetsNon> are the two with the induced test: SetsNon is the last
+// by-value argument, and all it adds is inside sets_lane_test.
 template <bool kOrdered, class... Ord>
 __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_cand, const uint32_t *__restrict__ cand,
                                                        const uint32_t *__restrict__ item_off, uint32_t w_shift,
@@ -141,15 +147,16 @@ __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_c
 
 using namespace gnnpe;
 
-// gnnpe_refine_sets (distinct = false: R) and gnnpe_refine_sets_distinct (D: the ordered kernel, unless the query has no symmetry)
-static int refine_sets_run(const char *who, bool distinct, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+// gnnpe_refine_sets (mode 0: R), gnnpe_refine_sets_distinct (GNNPE_MATCH_DISTINCT: D, the ordered kernel unless the query has no
+// symmetry) and gnnpe_refine_sets_mode (any mode; GNNPE_MATCH_INDUCED: I or ID, an induced kernel unless the query has no non-edge)
+static int refine_sets_run(const char *who, uint32_t mode, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
                            uint64_t limit, uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
 {
     GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers, GNNPE_ERR_ARG, "%s: null argument", who);
     *answers = 0;
     if (device_ms) *device_ms = 0.0;
     SetsQuery Q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, distinct, limit, &Q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q);
     if (rc || Q.empty) return rc;  // limit 0 or an empty set: no answers
     const uint32_t nq = Q.nq, n_cand = Q.n_cand;
     if (!matches) matches_cap = 0;
@@ -162,22 +169,27 @@ static int refine_sets_run(const char *who, bool distinct, gnnpe_ctx *c, const c
     if (device_ms) he = hipEventCreate(&ev0);
     if (he == hipSuccess && device_ms) he = hipEventCreate(&ev1);
     if (he == hipSuccess) rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, ev0);
-    if (c->sw.debug && distinct)
-        fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d pairs=%u\n", Q.w_shift, (int)Q.forced, n_cand, c->n_hub,
-                c->num_cus, Q.n_pairs);
-    else if (c->sw.debug)
-        fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d\n", Q.w_shift, (int)Q.forced, n_cand, c->n_hub, c->num_cus);
+    if (c->sw.debug) {
+        char pairs[32] = "", non[32] = "";  // a distinct call appends pairs=K, an induced one nonedges=K
+        if (mode & GNNPE_MATCH_DISTINCT) snprintf(pairs, sizeof pairs, " pairs=%u", Q.n_pairs);
+        if (mode & GNNPE_MATCH_INDUCED) snprintf(non, sizeof non, " nonedges=%u", Q.n_non);
+        fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d%s%s\n", Q.w_shift, (int)Q.forced, n_cand, c->n_hub,
+                c->num_cus, pairs, non);
+    }
     uint32_t *d_rows = matches_cap ? c->q_matches.as<uint32_t>() : nullptr;
     if (he == hipSuccess && !rc) {
         const SetsWork W(c->q_work, n_cand);
         auto launch = [&](auto... ord) {
-            hipLaunchKernelGGL((k_refine_sets<sizeof...(ord) != 0, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)), dim3(kBlock), 0,
+            hipLaunchKernelGGL((k_refine_sets<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)), dim3(kBlock), 0,
                                c->stream, Q.P, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(),
                                c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), Q.words,
                                (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr), d_rows, (unsigned long long)matches_cap,
                                ord...);
         };
-        Q.n_pairs ? launch(Q.O) : launch();
+        if (Q.n_non)
+            Q.n_pairs ? launch(Q.O, Q.N) : launch(Q.N);
+        else
+            Q.n_pairs ? launch(Q.O) : launch();
         he = hipGetLastError();
         if (he == hipSuccess && device_ms) he = hipEventRecord(ev1, c->stream);
         if (he == hipSuccess) he = hipMemcpyAsync(c->h_pinned, W.ctr, 16, hipMemcpyDeviceToHost, c->stream);
@@ -209,15 +221,22 @@ extern "C" {
 int gnnpe_refine_sets(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                       uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
 {
-    return refine_sets_run("gnnpe_refine_sets", false, c, query_graph_path, candidate_bitmap, limit, answers, matches, matches_cap,
+    return refine_sets_run("gnnpe_refine_sets", 0u, c, query_graph_path, candidate_bitmap, limit, answers, matches, matches_cap,
                            device_ms);
 }
 
 int gnnpe_refine_sets_distinct(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                                uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
 {
-    return refine_sets_run("gnnpe_refine_sets_distinct", true, c, query_graph_path, candidate_bitmap, limit, answers, matches,
-                           matches_cap, device_ms);
+    return refine_sets_run("gnnpe_refine_sets_distinct", GNNPE_MATCH_DISTINCT, c, query_graph_path, candidate_bitmap, limit, answers,
+                           matches, matches_cap, device_ms);
+}
+
+int gnnpe_refine_sets_mode(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
+                           uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+{
+    return refine_sets_run("gnnpe_refine_sets_mode", mode, c, query_graph_path, candidate_bitmap, limit, answers, matches, matches_cap,
+                           device_ms);
 }
 
 }  // extern "C"

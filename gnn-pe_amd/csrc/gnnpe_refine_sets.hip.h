@@ -9,12 +9,14 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../host/graph_loader.h"
 #include "../host/query_symmetry.h"
 #include "../host/refine.h"
 #include "../host/refine_sets.h"
+#include "../../include/gnnpe_online.h"
 #include "gnnpe_common.h"
 
 namespace gnnpe {
@@ -78,8 +80,25 @@ static inline uint32_t sets_order_from_pairs(const Pairs &pairs, const PosOf &po
     return (uint32_t)pairs.size();
 }
 
-// the one argument of an ordered kernel's parameter pack
+// ---- the INDUCED searches (I(C, limit) and ID(C, limit) of include/gnnpe_online.h: query non-edges land on data non-edges) ------
+// By position in the matching order: bit i < d of non[d] = positions i and d are NOT adjacent in the query, i.e. i is neither the
+// pivot of d nor one of its back neighbours.  The induced kernels take this by value beside the plan, after the SetsOrder of an
+// ordered one: 128 bytes.
+struct SetsNon {
+    uint32_t non[kSetsMaxQ];
+};
+
+// what a kernel's parameter pack holds: nothing (plain), SetsOrder (ordered), SetsNon (induced), or SetsOrder and SetsNon
+template <class... Ext>
+constexpr bool kSetsOrdered = (std::is_same_v<Ext, SetsOrder> || ...);
+template <class... Ext>
+constexpr bool kSetsInduced = (std::is_same_v<Ext, SetsNon> || ...);
+
+// the SetsOrder of an ordered kernel's parameter pack, the SetsNon of an induced one's
 __device__ __forceinline__ const SetsOrder &sets_order(const SetsOrder &o) { return o; }
+__device__ __forceinline__ const SetsOrder &sets_order(const SetsOrder &o, const SetsNon &) { return o; }
+__device__ __forceinline__ const SetsNon &sets_non(const SetsNon &n) { return n; }
+__device__ __forceinline__ const SetsNon &sets_non(const SetsOrder &, const SetsNon &n) { return n; }
 
 // the bounds of position d from the images of the earlier positions: an image v passes if lo <= v < hi.  Wave-uniform.
 __device__ __forceinline__ void order_bounds(const SetsOrder &O, const volatile SetsWave &S, uint32_t d, uint32_t &lo, uint32_t &hi)
@@ -121,14 +140,16 @@ __device__ __forceinline__ void order_trim(const uint32_t *__restrict__ nbrs, ui
 // ---- the steps of the search ---------------------------------------------------------------------------------------------------
 // Both kernels build a SetsGraph from their own parameters and keep the conventions of the state: S is read and written through
 // `volatile SetsWave &`, every word read from it goes through uni(), and no lane reads LDS that another lane alone wrote (every
-// lane writes every word).  The ordered instantiations pass their SetsOrder as the trailing pack, the plain ones nothing.
+// lane writes every word).  The ordered instantiations pass their SetsOrder as the trailing pack, the induced ones their SetsNon
+// (after the SetsOrder, if both), the plain ones nothing.
 struct SetsGraph {
     const uint32_t *__restrict__ adj_start, *__restrict__ adj_deg, *__restrict__ nbrs, *__restrict__ labels, *__restrict__ bitmap;
     uint64_t words;
 };
 
 // the lane's entry v of the chunk [cb, ce) of depth d's pivot row and its test: set bit, label, degree, the ordered bounds, not in
-// the image, every back edge by binary search in the SHORTER of the two rows
+// the image, every back edge by binary search in the SHORTER of the two rows; in the induced form, for the lanes still standing,
+// every earlier image that is no query neighbour by the same search, which must NOT find it
 template <bool kOrdered, class... Ord>
 __device__ __forceinline__ bool sets_lane_test(const SetsPlan &P, const volatile SetsWave &S, const SetsGraph &G, uint32_t d, uint32_t cb,
                                                uint32_t ce, uint32_t lane, uint32_t &v, const Ord &...ord)
@@ -149,6 +170,16 @@ __device__ __forceinline__ bool sets_lane_test(const SetsPlan &P, const volatile
         for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1] && ok; j++) {
             const uint32_t b = P.back[j], w = S.image[b], ws = S.istart[b], dw = S.ideg[b];
             ok = dv <= dw ? row_has(G.nbrs, vs, dv, w) : row_has(G.nbrs, ws, dw, v);
+        }
+    }
+    if constexpr (kSetsInduced<Ord...>) {
+        if (ok) {
+            const uint32_t vs = G.adj_start[v];
+            for (uint32_t m = uni(sets_non(ord...).non[d]); m && ok; m &= m - 1u) {
+                const uint32_t i = (uint32_t)__builtin_ctz(m);
+                const uint32_t w = uni(S.image[i]), ws = uni(S.istart[i]), dw = uni(S.ideg[i]);
+                ok = !(dv <= dw ? row_has(G.nbrs, vs, dv, w) : row_has(G.nbrs, ws, dw, v));
+            }
         }
     }
     return ok;
@@ -252,7 +283,9 @@ static inline uint32_t sets_first_level_shift(uint32_t n_cand, uint64_t entries,
 struct SetsQuery {
     SetsPlan P = {};
     SetsOrder O = {};      // of a distinct call
-    uint32_t n_pairs = 0;  // 0: the plain kernel (a call that is not distinct, or a query without symmetry)
+    uint32_t n_pairs = 0;  // 0: no ordered kernel (a call that is not distinct, or a query without symmetry)
+    SetsNon N = {};        // of an induced call
+    uint32_t n_non = 0;    // non-adjacent pairs; 0: no induced kernel (a call that is not induced, or a query without a non-edge)
     uint32_t nq = 0, n_cand = 0;
     uint64_t words = 0;
     std::vector<uint32_t> cand;    // C(start vertex) below n, ascending; sets_stage_items uploads it
@@ -263,9 +296,11 @@ struct SetsQuery {
 
 // Everything between a call's own argument checks and the device: the state of the context, the query graph, the set sizes and the
 // matching order -- a disconnected query is refused whatever the limit -- then the plan, the pairs and the start candidates.
-static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *bitmap, bool distinct,
+static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *bitmap, uint32_t mode,
                                uint64_t limit, SetsQuery *Q)
 {
+    GNNPE_REQUIRE((mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) == 0, GNNPE_ERR_ARG, "%s: unknown mode bits 0x%x", who, mode);
+    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0, induced = (mode & GNNPE_MATCH_INDUCED) != 0;
     GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
     GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
     GNNPE_HIP_TRY(hipSetDevice(c->device));
@@ -305,6 +340,14 @@ static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_
     for (size_t j = 0; j < mo.back.size(); j++) P.back[j] = (uint8_t)pos_of[mo.back[j]];
     // the ordering constraints by position; a query without symmetry has none and runs the plain kernel
     if (distinct) Q->n_pairs = sets_order_from_pairs(gnnpe_host::query_symmetry(q).pairs, pos_of, c->sw.sets_trim, &Q->O);
+    // the non-edges by position: every earlier position but the pivot and the back neighbours; a query without one (1 or 2
+    // vertices, K_n) runs the kernel it would run without the flag
+    for (uint32_t d = 1; induced && d < nq; d++) {
+        uint32_t m = ((1u << d) - 1u) & ~(1u << P.pivot[d]);
+        for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1]; j++) m &= ~(1u << P.back[j]);
+        Q->N.non[d] = m;
+        Q->n_non += (uint32_t)__builtin_popcount(m);
+    }
     Q->cand = gnnpe_host::set_members(bitmap, words, mo.order[0], c->n);
     Q->n_cand = (uint32_t)Q->cand.size();
     Q->empty = Q->n_cand == 0;

@@ -43,6 +43,7 @@ struct Options {
     bool all_matches = false, match_page_given = false;
     uint64_t match_page = 1ull << 20;
     bool distinct = false;  // --distinct (needs --refine sets): every matching subgraph once (gnnpe_refine_sets_distinct)
+    bool induced = false;   // --induced (needs --refine sets): induced matching, query non-edges on data non-edges (GNNPE_MATCH_INDUCED)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
     std::string transport = "rccl";  // --gpus N > 1: "rccl" (ncclSend/ncclRecv over xGMI) or "copy" (device-to-device copies)
@@ -119,9 +120,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             printf("%s -f <dataset dir/> -d <data.graph> -m offline -p <partitions> [-l 2] [-e 2]\n"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
-                   "           [--refine start|sets [--distinct]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
+                   "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
-                   "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once\n",
+                   "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
+                   "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices\n",
                    tool, tool);
             exit(0);
         }
@@ -155,6 +157,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         }
         if (a == "--all-matches") { o.all_matches = true; continue; }
         if (a == "--distinct") { o.distinct = true; continue; }
+        if (a == "--induced") { o.induced = true; continue; }
         if (a == "--allow-large") { o.allow_large = true; continue; }
         if (a == "--timing") { o.timing = true; continue; }
         if (a == "--sidecars") { o.sidecars = true; continue; }

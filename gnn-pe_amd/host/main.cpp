@@ -167,7 +167,8 @@ struct Device {
 // refinement on the device (gnnpe_refine; with --refine sets, where the sets are complete, gnnpe_refine_sets, which can
 // also hand back the embeddings: --matches, at most 2^20 of them, or with --all-matches all of them page by page through
 // the match cursor, gnnpe_refine_pages_*; with --distinct the _distinct forms, which count and write every matching subgraph
-// once, and a second line `Automorphisms: K`) and prints the reference's answer line instead of writing the file.
+// once, and a second line `Automorphisms: K`; with --induced the _mode forms with GNNPE_MATCH_INDUCED, which count and write induced
+// matches only, so that the answer is I or ID) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -251,21 +252,22 @@ int run_filter(const Options &o)
         refine_fn refine = (refine_fn)dlsym(online, "gnnpe_refine");
         if (!refine) die("libgnnpe_online.so does not export gnnpe_refine");
         const bool sets = o.refine == "sets";
+        const uint32_t match_mode = (o.distinct ? 1u /* GNNPE_MATCH_DISTINCT */ : 0u) | (o.induced ? 2u /* GNNPE_MATCH_INDUCED */ : 0u);
         uint64_t n_written = 0;
         uint64_t n_pages = 0;
         if (sets && o.all_matches) {
             // every embedding up to -n through the match cursor (gnnpe_refine_pages_*): one page on the host at a time
             typedef struct gnnpe_match_cursor cursor_t;
-            typedef int (*open_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t, cursor_t **);
+            typedef int (*open_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t, uint32_t, cursor_t **);
             typedef int (*next_fn)(cursor_t *, uint32_t *, uint64_t *, int *, double *);
             typedef void (*close_fn)(cursor_t *);
-            open_fn pages_open = (open_fn)dlsym(online, o.distinct ? "gnnpe_refine_pages_open_distinct" : "gnnpe_refine_pages_open");
+            open_fn pages_open = (open_fn)dlsym(online, "gnnpe_refine_pages_open_mode");
             next_fn pages_next = (next_fn)dlsym(online, "gnnpe_refine_pages_next");
             close_fn pages_close = (close_fn)dlsym(online, "gnnpe_refine_pages_close");
             if (!pages_open || !pages_next || !pages_close) die("libgnnpe_online.so does not export gnnpe_refine_pages_*");
             const uint64_t page = std::min<uint64_t>(o.match_page, std::max<uint64_t>(limit, 1));
             cursor_t *cur = nullptr;
-            check(pages_open(ctx, o.query_graph.c_str(), bitmap.data(), limit, page, &cur), "refine_pages_open");
+            check(pages_open(ctx, o.query_graph.c_str(), bitmap.data(), limit, page, match_mode, &cur), "refine_pages_open");
             FILE *mf = fopen(o.matches_file.c_str(), "w");
             if (!mf) die("cannot write " + o.matches_file);
             std::vector<uint32_t> rows((size_t)page * n_qv);
@@ -285,13 +287,13 @@ int run_filter(const Options &o)
             n_written = answers;
         } else if (sets) {
             // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
-            typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t *, uint32_t *, uint64_t,
-                                          double *);
-            refine_sets_fn refine_sets = (refine_sets_fn)dlsym(online, o.distinct ? "gnnpe_refine_sets_distinct" : "gnnpe_refine_sets");
-            if (!refine_sets) die("libgnnpe_online.so does not export gnnpe_refine_sets");
+            typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, uint32_t *,
+                                          uint64_t, double *);
+            refine_sets_fn refine_sets = (refine_sets_fn)dlsym(online, "gnnpe_refine_sets_mode");
+            if (!refine_sets) die("libgnnpe_online.so does not export gnnpe_refine_sets_mode");
             const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
             std::vector<uint32_t> rows((size_t)cap * n_qv);
-            check(refine_sets(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, cap ? rows.data() : nullptr, cap,
+            check(refine_sets(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, cap ? rows.data() : nullptr, cap,
                               &refine_ms), "refine_sets");
             if (!o.matches_file.empty()) {
                 FILE *mf = fopen(o.matches_file.c_str(), "w");
@@ -318,6 +320,7 @@ int run_filter(const Options &o)
             check(symmetry(o.query_graph.c_str(), &aut, pairs.data(), (uint32_t)(pairs.size() / 2), &n_pairs), "query_symmetry");
             printf("Automorphisms: %llu\n", (unsigned long long)aut);
         }
+        if (o.induced) exact_json += "\"induced\": true, ";
         if (o.timing && sets && o.all_matches)
             fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"match_pages\": %llu, \"paths\": %llu, "
                             "\"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
@@ -388,6 +391,7 @@ int main(int argc, char **argv)
     if (o.all_matches && o.matches_file.empty()) die("--all-matches needs --matches FILE");
     if (o.match_page_given && !o.all_matches) die("--match-page needs --all-matches");
     if (o.distinct && o.refine != "sets") die("--distinct needs --refine sets");
+    if (o.induced && o.refine != "sets") die("--induced needs --refine sets");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "

@@ -59,8 +59,8 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
     return 0;
 }
 
-// gnnpe_host_refine_sets and gnnpe_host_refine_sets_distinct
-static int host_refine_sets(const char *who, bool distinct, uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
+// gnnpe_host_refine_sets (mode 0), gnnpe_host_refine_sets_distinct (GNNPE_MATCH_DISTINCT) and gnnpe_host_refine_sets_mode
+static int host_refine_sets(const char *who, uint32_t mode, uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
                             const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
                             uint64_t *answers)
 {
@@ -68,6 +68,11 @@ static int host_refine_sets(const char *who, bool distinct, uint32_t n, const ui
         gnnpe::set_error("%s: null argument", who);
         return GNNPE_ERR_ARG;
     }
+    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
+        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
+        return GNNPE_ERR_ARG;
+    }
+    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
     gnnpe_host::StaticGraph q;
     std::string err;
     if (int rc = load_query(query_graph_path, &q)) return rc;
@@ -75,7 +80,7 @@ static int host_refine_sets(const char *who, bool distinct, uint32_t n, const ui
     gnnpe_host::QuerySymmetry sym;
     if (distinct) sym = gnnpe_host::query_symmetry(q);
     if (gnnpe_host::refine_sets_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &err,
-                                      distinct ? &sym.pairs : nullptr) != 0) {
+                                      distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
         gnnpe::set_error("%s", err.c_str());
         return GNNPE_ERR_ARG;
     }
@@ -85,13 +90,21 @@ static int host_refine_sets(const char *who, bool distinct, uint32_t n, const ui
 int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                            const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
 {
-    return host_refine_sets("gnnpe_host_refine_sets", false, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit, answers);
+    return host_refine_sets("gnnpe_host_refine_sets", 0u, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit, answers);
 }
 
 int gnnpe_host_refine_sets_distinct(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                     const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
 {
-    return host_refine_sets("gnnpe_host_refine_sets_distinct", true, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit,
+    return host_refine_sets("gnnpe_host_refine_sets_distinct", GNNPE_MATCH_DISTINCT, n, offsets, nbrs, labels, query_graph_path,
+                            candidate_bitmap, limit, answers);
+}
+
+int gnnpe_host_refine_sets_mode(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
+                                uint64_t *answers)
+{
+    return host_refine_sets("gnnpe_host_refine_sets_mode", mode, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit,
                             answers);
 }
 

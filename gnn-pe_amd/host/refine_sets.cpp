@@ -17,6 +17,7 @@ struct SetSearch {
     std::vector<uint32_t> order, pivot;       // matching order; an earlier neighbour of order[i] for i >= 1
     std::vector<std::vector<uint32_t>> back;  // the other earlier neighbours of order[i]
     std::vector<std::vector<uint32_t>> above, below;  // earlier query vertices whose image order[i]'s must be greater / smaller than
+    std::vector<std::vector<uint32_t>> non;   // induced: the earlier query vertices order[i] is not adjacent to
     std::vector<uint32_t> image;              // query vertex -> data vertex
     std::vector<uint8_t> used;                // data vertex taken
     uint64_t count = 0, limit;
@@ -51,6 +52,12 @@ struct SetSearch {
                     break;
                 }
             if (!ok) continue;
+            for (uint32_t w : non[depth])
+                if (edge(v, image[w])) {
+                    ok = false;
+                    break;
+                }
+            if (!ok) continue;
             image[u] = v;
             used[v] = 1;
             extend(depth + 1);
@@ -62,7 +69,8 @@ struct SetSearch {
 }  // namespace
 
 int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                      uint64_t limit, uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs)
+                      uint64_t limit, uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
+                      bool induced)
 {
     const uint32_t nq = query.n;
     if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
@@ -75,8 +83,15 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
     if (build_match_order(query, set_sizes(bitmap, words, nq), &mo, err) != 0) return -2;  // (a disconnected query is refused whatever the limit)
     if (limit == 0) return 0;
     SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
-                std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0), std::vector<uint8_t>(data.n, 0), 0, limit};
+                std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0),
+                std::vector<uint8_t>(data.n, 0), 0, limit};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
+    // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
+    for (uint32_t i = 1; induced && i < nq; i++)
+        for (uint32_t j = 0; j < i; j++) {
+            const uint32_t w = mo.order[j];
+            if (w != mo.pivot[i] && std::find(s.back[i].begin(), s.back[i].end(), w) == s.back[i].end()) s.non[i].push_back(w);
+        }
     if (pairs) {
         // f(a) < f(b) is tested where the later of the two in the order gets its image
         std::vector<uint32_t> pos_of(nq, 0);

@@ -41,8 +41,10 @@ inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words,
 // gnnpe_filter_candidates writes).  Returns 0 and *answers, or <0 with *err (disconnected query graph).
 // pairs (optional): only the maps with f(a) < f(b) for every pair (a, b) are counted -- with the pairs of query_symmetry.h this is
 // D(C, limit), one embedding per distinct subgraph.
+// induced: only the maps that also send every two distinct, non-adjacent query vertices to non-adjacent data vertices are counted
+// -- I(C, limit), or with the pairs ID(C, limit).
 int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
                       uint64_t limit, uint64_t *answers, std::string *err,
-                      const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr);
+                      const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
 
 }  // namespace gnnpe_host

@@ -3,7 +3,7 @@
  * gnnpe_host_refine / gnnpe_refine restate the reference (start vertex only) and are frozen: built in round 1 so that
  * `gnnpe_main -m online` can print the reference's answer line.  gnnpe_host_refine_sets / gnnpe_refine_sets (below) restrict
  * every query vertex to its set, for exact mode; the _distinct forms (ABI version 11) count and list every matching subgraph
- * once.  The library is kept out of libgnnpe_hip.so since round 6:
+ * once; the _mode forms (ABI version 12) add induced matching.  The library is kept out of libgnnpe_hip.so since round 6:
  * the offline hot path and its (f) rows link and load without it.  libgnnpe_online.so links against libgnnpe_hip.so (contexts, error text); `gnnpe_main` dlopen()s it for -m online
  * only.  Same conventions as gnnpe_hip.h: 0 = GNNPE_OK, gnnpe_last_error() for the text.
  */
@@ -125,6 +125,37 @@ int gnnpe_refine_sets_distinct(gnnpe_ctx *ctx, const char *query_graph_path, con
                                uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
 int gnnpe_refine_pages_open_distinct(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
                                      uint64_t limit, uint64_t page_rows, gnnpe_match_cursor **cursor);
+
+/* ---- ABI version 12: induced matching ---------------------------------------------------------------------------------
+ * R and D count MONOMORPHISMS: query edges land on data edges and nothing is asked of query non-edges.  Induced
+ * (vertex-induced) matching -- "subgraph isomorphism" in VF2's sense, the notion of motif and graphlet counting -- also
+ * sends every two non-adjacent query vertices to two non-adjacent data vertices.
+ *
+ * I(C, limit) = min(limit, number of maps counted by R(C, .) that also send every pair of distinct, non-adjacent query
+ *   vertices to non-adjacent data vertices).  ID(C, limit) is the same with D in the place of R: the ordering pairs of
+ *   gnnpe_host_query_symmetry also hold.
+ *   - The degree test (query degree <= data degree) stays.
+ *   - Automorphisms keep non-edges: for C closed under them ID counts one map per distinct induced occurrence, and
+ *     ID(C, 2^64 - 1) * |Aut(Q)| = I(C, 2^64 - 1).  For arbitrary C both are the constrained counts, nothing more.
+ *   - A query with no non-adjacent pair (1 or 2 vertices, K_n) has I = R and ID = D, and the device forms run the kernels
+ *     of the functions above.
+ *
+ * The three functions below take a mode word: 0 is R, GNNPE_MATCH_DISTINCT is D, GNNPE_MATCH_INDUCED is I, both bits are
+ * ID; any other bit returns GNNPE_ERR_ARG.  Arguments, requirements, refusals, row layout and cursor lifetime are those of
+ * gnnpe_host_refine_sets, gnnpe_refine_sets and gnnpe_refine_pages_open, which are their mode-0 cases as the _distinct
+ * functions are their GNNPE_MATCH_DISTINCT cases; the rows are the maps the mode counts.  On the device the non-edge test
+ * runs inside the search, after the back-edge test and by the same binary search in the shorter of the two rows: an image
+ * adjacent to an earlier image it must not be adjacent to is never descended into.  next, device_ptr, info and close
+ * serve every kind of cursor. */
+#define GNNPE_MATCH_DISTINCT 1u
+#define GNNPE_MATCH_INDUCED 2u
+int gnnpe_host_refine_sets_mode(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
+                                uint64_t *answers);
+int gnnpe_refine_sets_mode(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                           uint32_t mode, uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
+int gnnpe_refine_pages_open_mode(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                 uint64_t limit, uint64_t page_rows, uint32_t mode, gnnpe_match_cursor **cursor);
 
 #ifdef __cplusplus
 }
