@@ -124,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 12  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 13  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -153,6 +153,10 @@ ONLINE_SIGNATURES = {
     "gnnpe_host_refine_sets_mode": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p]),
     "gnnpe_refine_sets_mode": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, _u32p, C.c_uint64, _f64p]),
     "gnnpe_refine_pages_open_mode": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "gnnpe_host_refine_sets_vertex_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, C.c_uint32,
+                                                       _u64p, C.POINTER(C.c_int), _u64p]),
+    "gnnpe_refine_sets_vertex_counts": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p,
+                                                  C.POINTER(_vp), _f64p]),
 }
 _online = None
 
@@ -400,6 +404,29 @@ def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF, distinct=False, in
     if rc:
         raise GnnpeError(lib.gnnpe_last_error().decode())
     return out.value
+
+
+def _bitmap_rows(bm, n):
+    """query vertices of a bitmap: its rows, or for a flat one its words over ceil(n / 32)"""
+    return bm.shape[0] if bm.ndim == 2 else bm.size // max((n + 31) // 32, 1)
+
+
+def host_refine_sets_vertex_counts(g, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """Per-vertex match counts on the host (include/gnnpe_online.h, V_m(C)): (answers, complete, counts) with counts[u, v] = the
+    matches of the mode that send query vertex u to data vertex v, an (nq, n) uint64 array; nq is taken from the bitmap's rows.
+    `limit` is a guard: answers = min(matches, limit), complete = matches < limit, and counts is exact only where complete."""
+    lib = load()
+    out, done = C.c_uint64(), C.c_int()
+    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm = _np(bitmap, np.uint32)
+    n = len(o) - 1
+    counts = np.zeros((_bitmap_rows(bm, n), n), np.uint64)
+    rc = load_online().gnnpe_host_refine_sets_vertex_counts(n, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
+                                                            _ptr(bm, _u32p), int(limit), match_mode(distinct, induced),
+                                                            C.byref(out), C.byref(done), _ptr(counts, _u64p))
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return out.value, bool(done.value), counts
 
 
 def host_query_symmetry(query_path, pairs_cap=None):
@@ -874,6 +901,23 @@ class Engine:
         if rows is None:
             return out.value, ms.value
         return out.value, ms.value, rows[:min(out.value, cap)]
+
+    def refine_sets_vertex_counts(self, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False, device=False):
+        """Per-vertex match counts on the device (gnnpe_refine_sets_vertex_counts): (answers, complete, counts, device ms) with
+        counts[u, v] = the matches of the mode that send query vertex u to data vertex v, (nq, n) uint64.  `limit` is a guard:
+        complete = matches < limit, and counts is exact only where complete.  device=True: counts is a view of the context's
+        device table (`torch.as_tensor(counts, device=...)` shares it: int64 words holding the uint64 counts), with no host copy,
+        valid until the next call of this method or until another graph is loaded."""
+        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
+        bm = _np(bitmap, np.uint32)
+        nq = _bitmap_rows(bm, self.n)
+        counts = None if device else np.zeros((nq, self.n), np.uint64)
+        self._ck(load_online().gnnpe_refine_sets_vertex_counts(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit),
+                                                               match_mode(distinct, induced), C.byref(out), C.byref(done),
+                                                               _ptr(counts, _u64p), C.byref(ptr), C.byref(ms)))
+        if device:
+            counts = _DevArray(int(ptr.value or 0), (nq, self.n), "<i8", owner=self)
+        return out.value, bool(done.value), counts, ms.value
 
     def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
         """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open), or with distinct=True over the ones

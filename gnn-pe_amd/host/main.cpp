@@ -168,7 +168,8 @@ struct Device {
 // also hand back the embeddings: --matches, at most 2^20 of them, or with --all-matches all of them page by page through
 // the match cursor, gnnpe_refine_pages_*; with --distinct the _distinct forms, which count and write every matching subgraph
 // once, and a second line `Automorphisms: K`; with --induced the _mode forms with GNNPE_MATCH_INDUCED, which count and write induced
-// matches only, so that the answer is I or ID) and prints the reference's answer line instead of writing the file.
+// matches only, so that the answer is I or ID; with --vertex-counts gnnpe_refine_sets_vertex_counts, which writes per data vertex
+// the matches it takes part in by query vertex) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -285,6 +286,30 @@ int run_filter(const Options &o)
             pages_close(cur);
             if (fclose(mf) != 0) die("write failed on " + o.matches_file);
             n_written = answers;
+        } else if (sets && !o.vertex_counts_file.empty()) {
+            // per-vertex match counts (gnnpe_refine_sets_vertex_counts): -n is a guard, the table is exact only below it
+            typedef int (*vcounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, int *, uint64_t *,
+                                      void **, double *);
+            vcounts_fn vcounts = (vcounts_fn)dlsym(online, "gnnpe_refine_sets_vertex_counts");
+            if (!vcounts) die("libgnnpe_online.so does not export gnnpe_refine_sets_vertex_counts");
+            std::vector<uint64_t> table((size_t)n_qv * g.n);
+            int complete = 0;
+            check(vcounts(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, &complete, table.data(), nullptr,
+                          &refine_ms), "refine_sets_vertex_counts");
+            if (!complete)
+                die("--vertex-counts: the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " +
+                    o.vertex_counts_file + " was not written; raise -n");
+            FILE *vf = fopen(o.vertex_counts_file.c_str(), "w");
+            if (!vf) die("cannot write " + o.vertex_counts_file);
+            for (uint32_t v = 0; v < g.n; v++) {
+                bool any = false;
+                for (uint32_t u = 0; u < n_qv && !any; u++) any = table[(size_t)u * g.n + v] != 0;
+                if (!any) continue;
+                fprintf(vf, "%u", v);
+                for (uint32_t u = 0; u < n_qv; u++) fprintf(vf, " %llu", (unsigned long long)table[(size_t)u * g.n + v]);
+                fputc('\n', vf);
+            }
+            if (fclose(vf) != 0) die("write failed on " + o.vertex_counts_file);
         } else if (sets) {
             // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
             typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, uint32_t *,
@@ -392,6 +417,8 @@ int main(int argc, char **argv)
     if (o.match_page_given && !o.all_matches) die("--match-page needs --all-matches");
     if (o.distinct && o.refine != "sets") die("--distinct needs --refine sets");
     if (o.induced && o.refine != "sets") die("--induced needs --refine sets");
+    if (!o.vertex_counts_file.empty() && o.refine != "sets") die("--vertex-counts needs --refine sets");
+    if (!o.vertex_counts_file.empty() && !o.matches_file.empty()) die("--vertex-counts and --matches exclude each other");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "

@@ -21,6 +21,7 @@ struct SetSearch {
     std::vector<uint32_t> image;              // query vertex -> data vertex
     std::vector<uint8_t> used;                // data vertex taken
     uint64_t count = 0, limit;
+    uint64_t *vcounts = nullptr;              // vertex counts: nq x g.n cells, every find adds 1 to the cell of each of its images
 
     bool in_set(uint32_t u, uint32_t v) const { return (bitmap[(size_t)u * words + (v >> 5)] >> (v & 31)) & 1u; }
     bool fits(uint32_t u, uint32_t v) const
@@ -36,6 +37,8 @@ struct SetSearch {
     {
         if (depth == order.size()) {
             count++;
+            if (vcounts)
+                for (uint32_t u = 0; u < q.n; u++) vcounts[(size_t)u * g.n + image[u]]++;
             return;
         }
         const uint32_t u = order[depth], p = image[pivot[depth]];
@@ -68,9 +71,10 @@ struct SetSearch {
 
 }  // namespace
 
-int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                      uint64_t limit, uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
-                      bool induced)
+// refine_sets_count (vcounts == nullptr) and refine_sets_vertex_counts: one search, the table is filled at the finds
+static int refine_sets_search(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
+                              uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced,
+                              uint64_t *vcounts)
 {
     const uint32_t nq = query.n;
     if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
@@ -84,7 +88,7 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
     if (limit == 0) return 0;
     SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
                 std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0),
-                std::vector<uint8_t>(data.n, 0), 0, limit};
+                std::vector<uint8_t>(data.n, 0), 0, limit, vcounts};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
     // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
     for (uint32_t i = 1; induced && i < nq; i++)
@@ -116,6 +120,29 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
     }
     *answers = std::min(s.count, limit);
     return 0;
+}
+
+int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                      uint64_t limit, uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
+                      bool induced)
+{
+    return refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, nullptr);
+}
+
+int refine_sets_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                              uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
+                              const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+{
+    if (!complete || !counts) {
+        if (err) *err = "refine_sets_vertex_counts: null argument";
+        return -2;
+    }
+    *complete = false;
+    std::fill(counts, counts + (size_t)query.n * data.n, 0ull);
+    const int rc = refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, counts);
+    // the search stops at `limit` finds: below it, it walked everything (limit 0 walks nothing, and 0 < 0 is false)
+    if (rc == 0) *complete = *answers < limit;
+    return rc;
 }
 
 }  // namespace gnnpe_host

@@ -47,4 +47,11 @@ int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const u
                       uint64_t limit, uint64_t *answers, std::string *err,
                       const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
 
+// V_m(C) of include/gnnpe_online.h: counts[u * data.n + v] = the number of the maps refine_sets_count counts (same pairs, same
+// induced) that send query vertex u to data vertex v.  limit is a guard: *answers = min(|M|, limit), *complete = |M| < limit, and
+// the table is exact only where *complete (all zeros and complete where a set is empty).
+int refine_sets_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                              uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
+                              const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+
 }  // namespace gnnpe_host

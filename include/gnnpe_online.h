@@ -157,6 +157,56 @@ int gnnpe_refine_sets_mode(gnnpe_ctx *ctx, const char *query_graph_path, const u
 int gnnpe_refine_pages_open_mode(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
                                  uint64_t limit, uint64_t page_rows, uint32_t mode, gnnpe_match_cursor **cursor);
 
+/* ---- ABI version 13: per-vertex match counts ---------------------------------------------------------------------------
+ * What a motif or graphlet counter asks of the matches is rarely the rows: it is how many matches every data vertex takes
+ * part in, and in which role -- graphlet degree vectors, local triangle and clique counts, per-vertex motif features.  The
+ * search visits every match anyway; the two functions below build that table inside it and write no rows.
+ *
+ * For a mode word m (0, GNNPE_MATCH_DISTINCT, GNNPE_MATCH_INDUCED, or both) let M_m(C) be the set of maps that
+ * gnnpe_refine_sets_mode counts with limit 2^64 - 1.
+ *
+ *   V_m(C)[u][v] = |{ f in M_m(C) : f(u) = v }|     u < nq, v < n, uint64, row-major nq x n
+ *
+ * u is the query vertex id as in the query file (nq is the file's vertex count).  Every row of the table sums to |M_m(C)|.
+ * v can be the image of u in some match iff V[u][v] > 0: the rows' supports are the exact candidate sets.
+ *
+ * Reading the table.  For C closed under Aut(Q) (exact-mode filter output, label/degree bitmaps, all-ones bitmaps), with
+ * O(u) the orbit of u under the FULL automorphism group:
+ *   - modes 0 and INDUCED: V[u][v] * |O(u)| / |Aut(Q)| is the number of distinct occurrences in which v plays a role of
+ *     u's orbit (a triangle: V[u][v] / 2 triangles at v; a wedge: V[centre][v] / 2 wedges centred at v, V[end][v] wedges
+ *     ending at v).
+ *   - the DISTINCT modes: the same number is the sum of V[u'][v] over u' in O(u).  A single column of a symmetric query
+ *     splits by the ordering pairs (the smallest image of a triangle always sits at vertex 0) and means nothing on its own.
+ *   - for arbitrary C the table holds the constrained counts, nothing more.
+ *
+ * limit is a GUARD, not a cut: the table is exact only if the whole search ran.
+ *   - *answers = min(|M|, limit), as for every other call.
+ *   - *complete = 1 iff |M| < limit; limit = 2^64 - 1 always completes.
+ *   - with *complete = 0 the table's contents are unspecified (and the device form copies nothing to host_counts).
+ *   - with limit 0 the call launches nothing and returns *complete = 0.
+ *   - if some C(u) is empty, or there are no start candidates, the table is all zeros and *complete = 1.
+ *
+ * gnnpe_host_refine_sets_vertex_counts: the host form, the backtracking of gnnpe_host_refine_sets_mode adding 1 to the nq
+ *   cells of every find.  counts is nq x n uint64 of the caller's.  No limit on the query's size.  Unknown mode bits and a
+ *   disconnected query return GNNPE_ERR_ARG.
+ * gnnpe_refine_sets_vertex_counts: the device form (csrc/gnnpe_refine_vcount.hip).  Requirements and refusals are exactly
+ *   those of gnnpe_refine_sets_mode: the whole simple graph on the device, a connected query graph of 1..32 vertices, no
+ *   multigraph state, unknown mode bits GNNPE_ERR_ARG.
+ *   - The search is gnnpe_refine_sets_mode's.  Every wave tallies its finds per depth and adds a tally to the table when it
+ *     leaves the image it belongs to: one 64-bit atomic add per find (the last position) and one per visited image with at
+ *     least one find below it, not nq per find.
+ *   - host_counts (nq x n uint64) may be NULL: then nothing but the 16-byte counter block comes back to the host.
+ *   - *dev_counts (dev_counts may be NULL) is the table on the device: a context-owned, grow-only buffer of nq * n * 8
+ *     bytes, valid until the next call of this function on the context or until the context's rows are loaded or changed.
+ *     An allocation the device refuses returns its error and leaves the context usable.
+ *   - *device_ms (may be NULL) covers the zeroing of the table and the kernel. */
+int gnnpe_host_refine_sets_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                         const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                                         uint32_t mode, uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_refine_sets_vertex_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                    uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
+                                    void **dev_counts, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
