@@ -124,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 13  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 14  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -157,6 +157,11 @@ ONLINE_SIGNATURES = {
                                                        _u64p, C.POINTER(C.c_int), _u64p]),
     "gnnpe_refine_sets_vertex_counts": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p,
                                                   C.POINTER(_vp), _f64p]),
+    "gnnpe_host_query_edges": (C.c_int, [C.c_char_p, _u32p, C.c_uint32, _u32p]),
+    "gnnpe_host_refine_sets_edge_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, C.c_uint32,
+                                                     _u64p, C.POINTER(C.c_int), _u64p]),
+    "gnnpe_refine_sets_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p,
+                                                C.POINTER(_vp), _f64p]),
 }
 _online = None
 
@@ -429,6 +434,36 @@ def host_refine_sets_vertex_counts(g, query_path, bitmap, limit=2 ** 64 - 1, dis
     return out.value, bool(done.value), counts
 
 
+def host_query_edges(query_path):
+    """gnnpe_host_query_edges: the query edges as the edge-count tables number them, an (nqe, 2) uint32 array of (a_k, b_k) with
+    a_k < b_k, lexicographically ascending."""
+    lib, online = load(), load_online()
+    k = C.c_uint32()
+    online.gnnpe_host_query_edges(query_path.encode(), None, 0, C.byref(k))  # (a file that does not load fails again below)
+    edges = np.zeros((max(k.value, 1), 2), np.uint32)
+    if online.gnnpe_host_query_edges(query_path.encode(), _ptr(edges, _u32p), k.value, C.byref(k)):
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return edges[:k.value].copy()
+
+
+def host_refine_sets_edge_counts(g, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """Per-edge match counts on the host (include/gnnpe_online.h, E_m(C)): (answers, complete, counts) with counts[k, j] = the
+    matches of the mode that send query edge k = host_query_edges(query_path)[k] = (a, b) onto adjacency entry j of g: a to the
+    vertex whose row holds j, b to g["nbrs"][j]; an (nqe, len(g["nbrs"])) uint64 array.  `limit` is a guard: answers =
+    min(matches, limit), complete = matches < limit, and counts is exact only where complete."""
+    lib = load()
+    out, done = C.c_uint64(), C.c_int()
+    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm = _np(bitmap, np.uint32)
+    counts = np.zeros((len(host_query_edges(query_path)), int(o[-1])), np.uint64)
+    rc = load_online().gnnpe_host_refine_sets_edge_counts(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p),
+                                                          query_path.encode(), _ptr(bm, _u32p), int(limit), match_mode(distinct, induced),
+                                                          C.byref(out), C.byref(done), _ptr(counts, _u64p))
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return out.value, bool(done.value), counts
+
+
 def host_query_symmetry(query_path, pairs_cap=None):
     """gnnpe_host_query_symmetry: (|Aut(Q)| saturated at 2^64 - 1, pairs ndarray [k, 2]); a pair (a, b) asks for f(a) < f(b), and of
     the |Aut(Q)| embeddings of one subgraph exactly one satisfies every pair.  pairs_cap (default: whatever is needed) is the room
@@ -670,6 +705,8 @@ class Engine:
             raise GnnpeError("gnnpe_create: " + self.lib.gnnpe_last_error().decode())
         self.n = 0
         self.e = 0
+        self.entries = 0  # adjacency entries of the CSR given to load_csr: the width of the edge-count tables
+        self._rows_gen = self._ecounts_call = 0  # what an edge-count device view is valid for
         self.slab = (0, 0)
         self.total = None
         self._pools = []
@@ -710,8 +747,10 @@ class Engine:
         offsets, nbrs, labels = _np(offsets, np.uint32), _np(nbrs, np.uint32), _np(labels, np.uint32)
         n = len(offsets) - 1
         assert len(labels) == n and len(nbrs) == offsets[-1]
+        self._rows_gen += 1
         self._ck(self.lib.gnnpe_load_csr(self.ctx, n, _ptr(offsets, _u32p), _ptr(nbrs, _u32p), _ptr(labels, _u32p)))
         self.n = n
+        self.entries = int(offsets[-1])
         self.slab = (0, n)
 
     def load_multigraph(self, offsets, nbrs, labels):
@@ -724,11 +763,14 @@ class Engine:
 
     def set_multigraph_rows(self, row_offsets, row_nbrs):
         row_offsets, row_nbrs = _np(row_offsets, np.uint64), _np(row_nbrs, np.uint32)
+        self._rows_gen += 1
         self._ck(self.lib.gnnpe_set_multigraph_rows(self.ctx, len(row_offsets) - 1, _ptr(row_offsets, _u64p), _ptr(row_nbrs, _u32p)))
 
     def load_rows(self, n, labels, rows, row_offsets, row_nbrs, nbr_capacity=0):
         labels, rows = _np(labels, np.uint32), _np(rows, np.uint32)
         row_offsets, row_nbrs = _np(row_offsets, np.uint64), _np(row_nbrs, np.uint32)
+        self._rows_gen += 1
+        self.entries = 0
         self._ck(self.lib.gnnpe_load_rows(self.ctx, n, _ptr(labels, _u32p), len(rows), _ptr(rows, _u32p),
                                           _ptr(row_offsets, _u64p), _ptr(row_nbrs, _u32p), int(nbr_capacity)))
         self.n = n
@@ -918,6 +960,36 @@ class Engine:
         if device:
             counts = _DevArray(int(ptr.value or 0), (nq, self.n), "<i8", owner=self)
         return out.value, bool(done.value), counts, ms.value
+
+    def refine_sets_edge_counts(self, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False, device=False):
+        """Per-edge match counts on the device (gnnpe_refine_sets_edge_counts): (answers, complete, counts, device ms) with
+        counts[k, j] = the matches of the mode that send query edge k = host_query_edges(query_path)[k] onto adjacency entry j of
+        the CSR given to load_csr, (nqe, entries) uint64.  `limit` is a guard: complete = matches < limit, and counts is exact only
+        where complete.  device=True: counts is a view of the context's device table (`torch.as_tensor(counts, device=...)`
+        shares it: int64 words holding the uint64 counts), with no host copy, valid until the next call of this method or until
+        another graph is loaded; edge_counts_to_host(counts) copies it back and refuses a view that is no longer valid."""
+        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
+        bm = _np(bitmap, np.uint32)
+        shape = (len(host_query_edges(query_path)), self.entries)
+        counts = None if device else np.zeros(shape, np.uint64)
+        self._ecounts_call += 1
+        self._ck(load_online().gnnpe_refine_sets_edge_counts(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit),
+                                                             match_mode(distinct, induced), C.byref(out), C.byref(done),
+                                                             _ptr(counts, _u64p), C.byref(ptr), C.byref(ms)))
+        if device:
+            counts = _DevArray(int(ptr.value or 0), shape, "<i8", owner=self)
+            counts.valid_for = (self._rows_gen, self._ecounts_call)
+        return out.value, bool(done.value), counts, ms.value
+
+    def edge_counts_to_host(self, view):
+        """the device table a refine_sets_edge_counts(..., device=True) call returned, copied to the host as uint64; a view from
+        before the latest such call or from before the rows were loaded again is refused: the buffer holds something else by now"""
+        if getattr(view, "owner", None) is not self or getattr(view, "valid_for", None) != (self._rows_gen, self._ecounts_call):
+            raise GnnpeError("stale edge-count view: the table was replaced by a later refine_sets_edge_counts call or the graph was loaded again")
+        nbytes = view.shape[0] * view.shape[1] * 8
+        if nbytes == 0:
+            return np.zeros(view.shape, np.uint64)
+        return self.copy_to_host(view.__cuda_array_interface__["data"][0], nbytes).view(np.uint64).reshape(view.shape)
 
     def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
         """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open), or with distinct=True over the ones

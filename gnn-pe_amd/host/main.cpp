@@ -169,7 +169,8 @@ struct Device {
 // the match cursor, gnnpe_refine_pages_*; with --distinct the _distinct forms, which count and write every matching subgraph
 // once, and a second line `Automorphisms: K`; with --induced the _mode forms with GNNPE_MATCH_INDUCED, which count and write induced
 // matches only, so that the answer is I or ID; with --vertex-counts gnnpe_refine_sets_vertex_counts, which writes per data vertex
-// the matches it takes part in by query vertex) and prints the reference's answer line instead of writing the file.
+// the matches it takes part in by query vertex; with --edge-counts gnnpe_refine_sets_edge_counts, the same per adjacency entry and
+// query edge) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -310,6 +311,41 @@ int run_filter(const Options &o)
                 fputc('\n', vf);
             }
             if (fclose(vf) != 0) die("write failed on " + o.vertex_counts_file);
+        } else if (sets && !o.edge_counts_file.empty()) {
+            // per-edge match counts (gnnpe_refine_sets_edge_counts): -n is a guard, the table is exact only below it
+            typedef int (*ecounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, int *, uint64_t *,
+                                      void **, double *);
+            typedef int (*qedges_fn)(const char *, uint32_t *, uint32_t, uint32_t *);
+            ecounts_fn ecounts = (ecounts_fn)dlsym(online, "gnnpe_refine_sets_edge_counts");
+            qedges_fn qedges = (qedges_fn)dlsym(online, "gnnpe_host_query_edges");
+            if (!ecounts || !qedges) die("libgnnpe_online.so does not export gnnpe_refine_sets_edge_counts");
+            uint32_t nqe = 0;
+            std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
+            check(qedges(o.query_graph.c_str(), qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
+            const size_t entries = g.offsets[g.n];
+            std::vector<uint64_t> table((size_t)nqe * entries);
+            int complete = 0;
+            check(ecounts(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, &complete, table.data(), nullptr,
+                          &refine_ms), "refine_sets_edge_counts");
+            if (!complete)
+                die("--edge-counts: the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " +
+                    o.edge_counts_file + " was not written; raise -n");
+            FILE *ef = fopen(o.edge_counts_file.c_str(), "w");
+            if (!ef) die("cannot write " + o.edge_counts_file);
+            fputc('#', ef);
+            for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %u-%u", qe[2 * k], qe[2 * k + 1]);
+            fputc('\n', ef);
+            // the rows ascend, so the entries in CSR order are ascending by (x, y)
+            for (uint32_t x = 0; x < g.n; x++)
+                for (size_t j = g.offsets[x]; j < g.offsets[x + 1]; j++) {
+                    bool any = false;
+                    for (uint32_t k = 0; k < nqe && !any; k++) any = table[(size_t)k * entries + j] != 0;
+                    if (!any) continue;
+                    fprintf(ef, "%u %u", x, g.neighbors[j]);
+                    for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %llu", (unsigned long long)table[(size_t)k * entries + j]);
+                    fputc('\n', ef);
+                }
+            if (fclose(ef) != 0) die("write failed on " + o.edge_counts_file);
         } else if (sets) {
             // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
             typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, uint32_t *,
@@ -419,6 +455,9 @@ int main(int argc, char **argv)
     if (o.induced && o.refine != "sets") die("--induced needs --refine sets");
     if (!o.vertex_counts_file.empty() && o.refine != "sets") die("--vertex-counts needs --refine sets");
     if (!o.vertex_counts_file.empty() && !o.matches_file.empty()) die("--vertex-counts and --matches exclude each other");
+    if (!o.edge_counts_file.empty() && o.refine != "sets") die("--edge-counts needs --refine sets");
+    if (!o.edge_counts_file.empty() && !o.matches_file.empty()) die("--edge-counts and --matches exclude each other");
+    if (!o.edge_counts_file.empty() && !o.vertex_counts_file.empty()) die("--edge-counts and --vertex-counts exclude each other");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "

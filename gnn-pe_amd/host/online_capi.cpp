@@ -140,6 +140,60 @@ int gnnpe_host_refine_sets_vertex_counts(uint32_t n, const uint32_t *offsets, co
     return 0;
 }
 
+int gnnpe_host_refine_sets_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                       const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
+                                       uint64_t *answers, int *complete, uint64_t *counts)
+{
+    const char *who = "gnnpe_host_refine_sets_edge_counts";
+    // (counts may be null where the table is empty: refine_sets_edge_counts looks at it once the query is known)
+    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || !complete) {
+        gnnpe::set_error("%s: null argument", who);
+        return GNNPE_ERR_ARG;
+    }
+    *answers = 0;
+    *complete = 0;
+    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
+        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
+        return GNNPE_ERR_ARG;
+    }
+    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
+    gnnpe_host::QuerySymmetry sym;
+    if (distinct) sym = gnnpe_host::query_symmetry(q);
+    bool done = false;
+    if (gnnpe_host::refine_sets_edge_counts(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &done, counts, &err,
+                                            distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
+        gnnpe::set_error("%s", err.c_str());
+        return GNNPE_ERR_ARG;
+    }
+    *complete = done ? 1 : 0;
+    return 0;
+}
+
+int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
+{
+    if (!query_graph_path || !n_edges || (!edges && cap)) {
+        gnnpe::set_error("gnnpe_host_query_edges: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    gnnpe_host::StaticGraph q;
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const std::vector<std::pair<uint32_t, uint32_t>> qe = gnnpe_host::query_edges(q);
+    *n_edges = (uint32_t)qe.size();
+    if (qe.size() > cap) {
+        gnnpe::set_error("gnnpe_host_query_edges: %zu edges, room for %u", qe.size(), cap);
+        return GNNPE_ERR_ARG;
+    }
+    for (size_t k = 0; k < qe.size(); k++) {
+        edges[2 * k] = qe[k].first;
+        edges[2 * k + 1] = qe[k].second;
+    }
+    return 0;
+}
+
 int gnnpe_host_query_symmetry(const char *query_graph_path, uint64_t *n_automorphisms, uint32_t *pairs, uint32_t pairs_cap,
                               uint32_t *n_pairs)
 {

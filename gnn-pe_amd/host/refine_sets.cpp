@@ -22,6 +22,8 @@ struct SetSearch {
     std::vector<uint8_t> used;                // data vertex taken
     uint64_t count = 0, limit;
     uint64_t *vcounts = nullptr;              // vertex counts: nq x g.n cells, every find adds 1 to the cell of each of its images
+    uint64_t *ecounts = nullptr;              // edge counts: qedges.size() x g.offsets[g.n] cells, every find adds 1 per query edge
+    std::vector<std::pair<uint32_t, uint32_t>> qedges;  // query_edges(q), for ecounts
 
     bool in_set(uint32_t u, uint32_t v) const { return (bitmap[(size_t)u * words + (v >> 5)] >> (v & 31)) & 1u; }
     bool fits(uint32_t u, uint32_t v) const
@@ -39,6 +41,13 @@ struct SetSearch {
             count++;
             if (vcounts)
                 for (uint32_t u = 0; u < q.n; u++) vcounts[(size_t)u * g.n + image[u]]++;
+            for (size_t k = 0; ecounts && k < qedges.size(); k++) {
+                // the entry f(a_k) -> f(b_k): its index in the CSR, by binary search in the row of f(a_k)
+                const uint32_t x = image[qedges[k].first], y = image[qedges[k].second];
+                const auto row = g.neighbors.begin() + g.offsets[x], end = g.neighbors.begin() + g.offsets[x + 1];
+                const auto it = std::lower_bound(row, end, y);
+                if (it != end && *it == y) ecounts[k * (size_t)g.offsets[g.n] + (size_t)(it - g.neighbors.begin())]++;
+            }
             return;
         }
         const uint32_t u = order[depth], p = image[pivot[depth]];
@@ -71,10 +80,10 @@ struct SetSearch {
 
 }  // namespace
 
-// refine_sets_count (vcounts == nullptr) and refine_sets_vertex_counts: one search, the table is filled at the finds
+// refine_sets_count (no table), refine_sets_vertex_counts and refine_sets_edge_counts: one search, a table is filled at the finds
 static int refine_sets_search(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
                               uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced,
-                              uint64_t *vcounts)
+                              uint64_t *vcounts, uint64_t *ecounts = nullptr)
 {
     const uint32_t nq = query.n;
     if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
@@ -88,7 +97,8 @@ static int refine_sets_search(const StaticGraph &data, const StaticGraph &query,
     if (limit == 0) return 0;
     SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
                 std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0),
-                std::vector<uint8_t>(data.n, 0), 0, limit, vcounts};
+                std::vector<uint8_t>(data.n, 0), 0, limit, vcounts, ecounts,
+                ecounts ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>()};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
     // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
     for (uint32_t i = 1; induced && i < nq; i++)
@@ -142,6 +152,33 @@ int refine_sets_vertex_counts(const StaticGraph &data, const StaticGraph &query,
     const int rc = refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, counts);
     // the search stops at `limit` finds: below it, it walked everything (limit 0 walks nothing, and 0 < 0 is false)
     if (rc == 0) *complete = *answers < limit;
+    return rc;
+}
+
+std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query)
+{
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    for (uint32_t a = 0; a < query.n; a++)
+        for (uint32_t i = query.offsets[a]; i < query.offsets[a + 1]; i++) {
+            const uint32_t b = query.neighbors[i];
+            if (a < b && (out.empty() || out.back() != std::make_pair(a, b))) out.emplace_back(a, b);  // (a repeated `e` line: once)
+        }
+    return out;
+}
+
+int refine_sets_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                            uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
+                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+{
+    const size_t cells = query_edges(query).size() * (size_t)(data.n ? data.offsets[data.n] : 0);
+    if (!complete || (!counts && cells)) {
+        if (err) *err = "refine_sets_edge_counts: null argument";
+        return -2;
+    }
+    *complete = false;
+    if (cells) std::fill(counts, counts + cells, 0ull);
+    const int rc = refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, nullptr, cells ? counts : nullptr);
+    if (rc == 0) *complete = *answers < limit;  // as in refine_sets_vertex_counts
     return rc;
 }
 

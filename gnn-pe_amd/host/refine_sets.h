@@ -54,4 +54,15 @@ int refine_sets_vertex_counts(const StaticGraph &data, const StaticGraph &query,
                               uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
                               const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
 
+// The query edges as include/gnnpe_online.h numbers them: (a_k, b_k) with a_k < b_k, lexicographically ascending, each once.
+std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query);
+
+// E_m(C) of include/gnnpe_online.h: counts[k * data.offsets[data.n] + j] = the number of the maps refine_sets_count counts (same
+// pairs, same induced) that send query edge k = (a_k, b_k) onto the adjacency entry j = (f(a_k) -> f(b_k)) of the data CSR; j is
+// found by binary search in the row of f(a_k).  limit and *complete as in refine_sets_vertex_counts.  A query without an edge has
+// no table: counts may then be null.
+int refine_sets_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                            uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
+                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+
 }  // namespace gnnpe_host

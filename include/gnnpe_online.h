@@ -207,6 +207,62 @@ int gnnpe_refine_sets_vertex_counts(gnnpe_ctx *ctx, const char *query_graph_path
                                     uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
                                     void **dev_counts, double *device_ms);
 
+/* ---- ABI version 14: per-edge match counts -----------------------------------------------------------------------------
+ * The other half of what motif and graphlet consumers ask for is per EDGE: the triangle support of every edge (the input of a
+ * k-truss decomposition), edge-orbit graphlet degree vectors, per-edge motif features.  None of it follows from V_m(C): two
+ * vertices can each sit in many matches without sharing one.  The functions below build the table inside the search.
+ *
+ * Query edges.  The edges of the loaded simple query graph are written (a_k, b_k) with a_k < b_k and sorted lexicographically,
+ * k = 0 .. nqe - 1.  gnnpe_host_query_edges hands that list out (edges: cap x 2 uint32; conventions as
+ * gnnpe_host_query_symmetry: *n_edges is always set, and a cap below it returns GNNPE_ERR_ARG).
+ *
+ * Data entries.  j is an index into the CSR the caller handed over: offsets / nbrs of the host form, the arrays of
+ * gnnpe_load_csr for the device form -- the context keeps them entry for entry (row x starts at offsets[x], nbrs is copied as
+ * it is).  Entry j in row x with nbrs[j] = y is the directed entry x -> y.  The graph is undirected: y -> x is an entry too.
+ *
+ *   E_m(C)[k][j] = |{ f in M_m(C) : f(a_k) = x and f(b_k) = y }|   for j = (x -> y), uint64, row-major nqe x offsets[n]
+ *
+ * with M_m(C) as in the ABI 13 text.  Every row sums to |M_m(C)|.  Summing row k over the entries of data row x gives
+ * V[a_k][x]; summing row k over the entries with nbrs[j] = y gives V[b_k][y].
+ *
+ * Reading the table.
+ *   - the undirected support of {x, y} under query edge k is E[k][x->y] + E[k][y->x].
+ *   - triangle, mode 0: every E[k][x->y] is the number of triangles on {x, y} -- the truss support.
+ *   - wedge 0 - 1 - 2, mode 0: E[0][x->y] = deg(y) - 1 and E[1][x->y] = deg(x) - 1.
+ *   - for C closed under Aut(Q), in the DISTINCT modes a single row of a symmetric query splits by the ordering pairs, and
+ *     so does a single direction of it (the smaller image of a triangle's edge 0 always sits at vertex 0).  A row and a
+ *     direction mean nothing on their own there: what means something is the sum over the rows of the edge's orbit under
+ *     Aut(Q), and over both directions -- the number of distinct occurrences in which {x, y} plays a role of that orbit.
+ *   - for arbitrary C the table holds the constrained counts, nothing more.
+ *
+ * limit and *complete are exactly those of gnnpe_refine_sets_vertex_counts: limit is a guard, *answers = min(|M|, limit),
+ * *complete = 1 iff |M| < limit; with *complete = 0 the table is unspecified and nothing is copied to the host; with limit 0
+ * nothing is launched; an empty set gives a zero table and *complete = 1.
+ * A single-vertex query has nqe = 0: the call succeeds with an empty table (counts / host_counts are not touched and may be
+ * NULL, *dev_counts = NULL, nothing is allocated) and the usual *answers and *complete.
+ *
+ * gnnpe_host_refine_sets_edge_counts: the host form, the backtracking of gnnpe_host_refine_sets_mode adding 1 to the nqe cells
+ *   of every find; the entry is found by binary search in the data row.  No limit on the query's size.  Unknown mode bits and a
+ *   disconnected query return GNNPE_ERR_ARG.
+ * gnnpe_refine_sets_edge_counts: the device form (csrc/gnnpe_refine_ecount.hip).  Requirements and refusals are exactly those
+ *   of gnnpe_refine_sets_mode.
+ *   - Every wave tallies its finds per depth, remembers the entry it stands on per depth, and adds a tally to the entries of a
+ *     position's query edges when it leaves the image: deg_Q(last position) atomic adds per find, and for every visited image
+ *     with a find below it one per query edge to its earlier positions.
+ *   - host_counts (nqe x offsets[n] uint64) may be NULL.
+ *   - *dev_counts (dev_counts may be NULL) is the table on the device: a context-owned, grow-only buffer of its own, valid
+ *     until the next call of THIS function on the context or until the context's rows are loaded or changed; a
+ *     gnnpe_refine_sets_vertex_counts call in between does not disturb it.  An allocation the device refuses returns its
+ *     error and leaves the context usable.
+ *   - *device_ms (may be NULL) covers the zeroing of the table and the kernel. */
+int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges);
+int gnnpe_host_refine_sets_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                       const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
+                                       uint32_t mode, uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_refine_sets_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                  uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
+                                  void **dev_counts, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
