@@ -124,7 +124,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 14  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 15  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -162,6 +162,10 @@ ONLINE_SIGNATURES = {
                                                      _u64p, C.POINTER(C.c_int), _u64p]),
     "gnnpe_refine_sets_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p,
                                                 C.POINTER(_vp), _f64p]),
+    "gnnpe_host_refine_sets_delta": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64,
+                                               C.c_uint32, _u64p]),
+    "gnnpe_refine_sets_delta": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p, C.c_uint64,
+                                          _f64p]),
 }
 _online = None
 
@@ -462,6 +466,30 @@ def host_refine_sets_edge_counts(g, query_path, bitmap, limit=2 ** 64 - 1, disti
     if rc:
         raise GnnpeError(lib.gnnpe_last_error().decode())
     return out.value, bool(done.value), counts
+
+
+def _delta_pairs(edges):
+    """F of the delta calls as a contiguous (n_delta, 2) uint32 array; ids that do not fit 32 bits are refused here"""
+    e = np.asarray(edges, np.int64).reshape(-1, 2)
+    if e.size and (e.min() < 0 or e.max() > 0xFFFFFFFF):
+        raise GnnpeError("delta edges: vertex ids are uint32")
+    return np.ascontiguousarray(e, np.uint32)
+
+
+def host_refine_sets_delta(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """The matches through a set of data edges on the host (include/gnnpe_online.h, Delta_m(C, F, limit)): the number of matches
+    of the mode that put at least one query edge on one of `edges` (pairs (x, y), either orientation, repeats tolerated), each
+    match once, up to `limit`.  A pair that is no edge of g, a loop or an id outside g raises GnnpeError."""
+    lib = load()
+    out = C.c_uint64()
+    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
+    rc = load_online().gnnpe_host_refine_sets_delta(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
+                                                    _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
+                                                    match_mode(distinct, induced), C.byref(out))
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return out.value
 
 
 def host_query_symmetry(query_path, pairs_cap=None):
@@ -980,6 +1008,21 @@ class Engine:
             counts = _DevArray(int(ptr.value or 0), shape, "<i8", owner=self)
             counts.valid_for = (self._rows_gen, self._ecounts_call)
         return out.value, bool(done.value), counts, ms.value
+
+    def refine_sets_delta(self, query_path, bitmap, edges, limit=2 ** 64 - 1, matches_cap=0, distinct=False, induced=False):
+        """The matches through a set of data edges on the device (gnnpe_refine_sets_delta): (answers, rows, device ms).  answers =
+        min(limit, the matches of the mode that put at least one query edge on one of `edges`), each match once; rows[k, u] = the
+        image of query vertex u in the k-th match kept, min(answers, matches_cap) rows (none with matches_cap 0).  `edges`: pairs
+        (x, y) of the loaded graph, either orientation, repeats tolerated; a pair that is no edge is refused."""
+        out, ms = C.c_uint64(), C.c_double()
+        bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
+        cap = min(int(matches_cap), int(limit))
+        nq = _bitmap_rows(bm, self.n)
+        rows = np.zeros((cap, nq), np.uint32)
+        self._ck(load_online().gnnpe_refine_sets_delta(self.ctx, query_path.encode(), _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None,
+                                                       len(e), int(limit), match_mode(distinct, induced), C.byref(out),
+                                                       _ptr(rows, _u32p) if cap else None, cap, C.byref(ms)))
+        return out.value, rows[:min(out.value, cap)], ms.value
 
     def edge_counts_to_host(self, view):
         """the device table a refine_sets_edge_counts(..., device=True) call returned, copied to the host as uint64; a view from

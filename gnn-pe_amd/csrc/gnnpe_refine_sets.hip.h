@@ -294,17 +294,59 @@ struct SetsQuery {
     bool forced = false;           // ... taken from GNNPE_TESTING=sets_first_shift=K, not from the heuristic
 };
 
+// The plan of a matching order by position, with the ordering constraints of a distinct call and the non-edges of an induced one:
+// what sets_prepare launches for the order of build_match_order, and gnnpe_refine_sets_delta for the order anchored at each query
+// edge.  Fills Q->P, Q->O, Q->n_pairs, Q->N and Q->n_non; returns pos_of[query vertex] = position.
+static inline std::vector<uint32_t> sets_plan_from_order(const gnnpe_host::StaticGraph &q, const gnnpe_host::MatchOrder &mo, bool distinct,
+                                                         bool induced, bool trim, SetsQuery *Q)
+{
+    const uint32_t nq = q.n;
+    // plan by position in the order.  P.back holds every query edge: 32 vertices have at most 496 edges, back leaves out the 31
+    // pivot edges, and sizeof(P.back) is 496
+    SetsPlan &P = Q->P;
+    static_assert(sizeof(P.back) == kSetsMaxQ * (kSetsMaxQ - 1) / 2, "one byte per possible query edge");
+    P = SetsPlan{};
+    P.nq = nq;
+    std::vector<uint32_t> pos_of(nq, 0);
+    for (uint32_t i = 0; i < nq; i++) pos_of[mo.order[i]] = i;
+    for (uint32_t i = 0; i < nq; i++) {
+        P.label[i] = q.labels[mo.order[i]];
+        P.degree[i] = q.degree(mo.order[i]);
+        P.qv[i] = (uint8_t)mo.order[i];
+        P.pivot[i] = (uint8_t)pos_of[mo.pivot[i]];
+        P.back_off[i] = (uint16_t)mo.back_off[i];
+    }
+    P.back_off[nq] = (uint16_t)mo.back_off[nq];
+    for (size_t j = 0; j < mo.back.size(); j++) P.back[j] = (uint8_t)pos_of[mo.back[j]];
+    // the ordering constraints by position; a query without symmetry has none and runs the plain kernel
+    Q->O = SetsOrder{};
+    Q->n_pairs = distinct ? sets_order_from_pairs(gnnpe_host::query_symmetry(q).pairs, pos_of, trim, &Q->O) : 0u;
+    // the non-edges by position: every earlier position but the pivot and the back neighbours; a query without one (1 or 2
+    // vertices, K_n) runs the kernel it would run without the flag
+    Q->N = SetsNon{};
+    Q->n_non = 0;
+    for (uint32_t d = 1; induced && d < nq; d++) {
+        uint32_t m = ((1u << d) - 1u) & ~(1u << P.pivot[d]);
+        for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1]; j++) m &= ~(1u << P.back[j]);
+        Q->N.non[d] = m;
+        Q->n_non += (uint32_t)__builtin_popcount(m);
+    }
+    return pos_of;
+}
+
 // Everything between a call's own argument checks and the device: the state of the context, the query graph, the set sizes and the
 // matching order -- a disconnected query is refused whatever the limit -- then the plan, the pairs and the start candidates.
+// `query`, if given, receives the loaded query graph (gnnpe_refine_sets_delta builds its own orders from it).
 static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *bitmap, uint32_t mode,
-                               uint64_t limit, SetsQuery *Q)
+                               uint64_t limit, SetsQuery *Q, gnnpe_host::StaticGraph *query = nullptr)
 {
     GNNPE_REQUIRE((mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) == 0, GNNPE_ERR_ARG, "%s: unknown mode bits 0x%x", who, mode);
     const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0, induced = (mode & GNNPE_MATCH_INDUCED) != 0;
     GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
     GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
     GNNPE_HIP_TRY(hipSetDevice(c->device));
-    gnnpe_host::StaticGraph q;
+    gnnpe_host::StaticGraph q_own;
+    gnnpe_host::StaticGraph &q = query ? *query : q_own;
     std::string err;
     const int rc = q.load(query_graph_path, &err);
     if (rc != 0) {
@@ -322,32 +364,7 @@ static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_
     }
     Q->empty = limit == 0 || std::find(cnt.begin(), cnt.end(), 0u) != cnt.end();  // an empty set anywhere means no embedding
     if (Q->empty) return GNNPE_OK;
-    // plan by position in the order.  P.back holds every query edge: 32 vertices have at most 496 edges, back leaves out the 31
-    // pivot edges, and sizeof(P.back) is 496
-    SetsPlan &P = Q->P;
-    static_assert(sizeof(P.back) == kSetsMaxQ * (kSetsMaxQ - 1) / 2, "one byte per possible query edge");
-    P.nq = nq;
-    std::vector<uint32_t> pos_of(nq, 0);
-    for (uint32_t i = 0; i < nq; i++) pos_of[mo.order[i]] = i;
-    for (uint32_t i = 0; i < nq; i++) {
-        P.label[i] = q.labels[mo.order[i]];
-        P.degree[i] = q.degree(mo.order[i]);
-        P.qv[i] = (uint8_t)mo.order[i];
-        P.pivot[i] = (uint8_t)pos_of[mo.pivot[i]];
-        P.back_off[i] = (uint16_t)mo.back_off[i];
-    }
-    P.back_off[nq] = (uint16_t)mo.back_off[nq];
-    for (size_t j = 0; j < mo.back.size(); j++) P.back[j] = (uint8_t)pos_of[mo.back[j]];
-    // the ordering constraints by position; a query without symmetry has none and runs the plain kernel
-    if (distinct) Q->n_pairs = sets_order_from_pairs(gnnpe_host::query_symmetry(q).pairs, pos_of, c->sw.sets_trim, &Q->O);
-    // the non-edges by position: every earlier position but the pivot and the back neighbours; a query without one (1 or 2
-    // vertices, K_n) runs the kernel it would run without the flag
-    for (uint32_t d = 1; induced && d < nq; d++) {
-        uint32_t m = ((1u << d) - 1u) & ~(1u << P.pivot[d]);
-        for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1]; j++) m &= ~(1u << P.back[j]);
-        Q->N.non[d] = m;
-        Q->n_non += (uint32_t)__builtin_popcount(m);
-    }
+    sets_plan_from_order(q, mo, distinct, induced, c->sw.sets_trim, Q);
     Q->cand = gnnpe_host::set_members(bitmap, words, mo.order[0], c->n);
     Q->n_cand = (uint32_t)Q->cand.size();
     Q->empty = Q->n_cand == 0;

@@ -49,6 +49,9 @@ struct Options {
     // --edge-counts FILE (needs --refine sets, not with --matches or --vertex-counts): per adjacency entry, in how many matches it
     // carries each query edge (gnnpe_refine_sets_edge_counts); -n is a guard as for --vertex-counts
     std::string edge_counts_file;
+    // --delta-edges FILE (needs --refine sets; with --matches but not --all-matches, not with the count tables): one data edge
+    // `x y` per line; the answer is the matches through at least one of them, each once (gnnpe_refine_sets_delta)
+    std::string delta_edges_file;
     bool induced = false;   // --induced (needs --refine sets): induced matching, query non-edges on data non-edges (GNNPE_MATCH_INDUCED)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
@@ -127,7 +130,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
-                   "           [--vertex-counts FILE | --edge-counts FILE]\n"
+                   "           [--vertex-counts FILE | --edge-counts FILE | --delta-edges FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -137,7 +140,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --edge-counts FILE (needs --refine sets, not with --matches or --vertex-counts; combines with --distinct and\n"
                    "       --induced) writes a first line `# a_0-b_0 a_1-b_1 ...`, the query edges with a_k < b_k, and one line\n"
                    "       `x y c_0 ... c_{nqe-1}` per directed adjacency entry x -> y in a match, ascending by (x, y): c_k = the matches that\n"
-                   "       send a_k to x and b_k to y.  -n is a guard as for --vertex-counts\n",
+                   "       send a_k to x and b_k to y.  -n is a guard as for --vertex-counts;\n"
+                   "       --delta-edges FILE (needs --refine sets; combines with --distinct, --induced and --matches, not with\n"
+                   "       --all-matches or the count tables): FILE has one data edge `x y` per line; the answer is the number of matches\n"
+                   "       that put a query edge on at least one of them, each match once, and --matches writes those\n",
                    tool, tool);
             exit(0);
         }
@@ -154,11 +160,12 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             o.transport_explicit = true;
             continue;
         }
-        if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts") {
+        if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges") {
             if (i + 1 >= argc) die(a + " needs a value");
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }
             if (a == "--vertex-counts") { o.vertex_counts_file = argv[++i]; continue; }
             if (a == "--edge-counts") { o.edge_counts_file = argv[++i]; continue; }
+            if (a == "--delta-edges") { o.delta_edges_file = argv[++i]; continue; }
             o.refine = argv[++i];
             if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;

@@ -170,7 +170,8 @@ struct Device {
 // once, and a second line `Automorphisms: K`; with --induced the _mode forms with GNNPE_MATCH_INDUCED, which count and write induced
 // matches only, so that the answer is I or ID; with --vertex-counts gnnpe_refine_sets_vertex_counts, which writes per data vertex
 // the matches it takes part in by query vertex; with --edge-counts gnnpe_refine_sets_edge_counts, the same per adjacency entry and
-// query edge) and prints the reference's answer line instead of writing the file.
+// query edge; with --delta-edges gnnpe_refine_sets_delta, which counts and writes the matches through the listed data edges, each
+// once) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -346,6 +347,36 @@ int run_filter(const Options &o)
                     fputc('\n', ef);
                 }
             if (fclose(ef) != 0) die("write failed on " + o.edge_counts_file);
+        } else if (sets && !o.delta_edges_file.empty()) {
+            // the matches through the data edges of FILE, each once (gnnpe_refine_sets_delta); --matches as below
+            typedef int (*delta_fn)(gnnpe_ctx *, const char *, const uint32_t *, const uint32_t *, uint64_t, uint64_t, uint32_t, uint64_t *,
+                                    uint32_t *, uint64_t, double *);
+            delta_fn delta = (delta_fn)dlsym(online, "gnnpe_refine_sets_delta");
+            if (!delta) die("libgnnpe_online.so does not export gnnpe_refine_sets_delta");
+            std::vector<uint32_t> edges;
+            FILE *df = fopen(o.delta_edges_file.c_str(), "r");
+            if (!df) die("cannot read " + o.delta_edges_file);
+            for (unsigned long long x, y;;) {
+                const int got = fscanf(df, "%llu %llu", &x, &y);
+                if (got == EOF) break;
+                if (got != 2 || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull) die(o.delta_edges_file + ": one `x y` per line expected");
+                edges.push_back((uint32_t)x);
+                edges.push_back((uint32_t)y);
+            }
+            fclose(df);
+            const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
+            std::vector<uint32_t> rows((size_t)cap * n_qv);
+            check(delta(ctx, o.query_graph.c_str(), bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &answers,
+                        cap ? rows.data() : nullptr, cap, &refine_ms), "refine_sets_delta");
+            if (!o.matches_file.empty()) {
+                FILE *mf = fopen(o.matches_file.c_str(), "w");
+                if (!mf) die("cannot write " + o.matches_file);
+                n_written = std::min(answers, cap);
+                for (uint64_t k = 0; k < n_written; k++)
+                    for (uint32_t u = 0; u < n_qv; u++)
+                        fprintf(mf, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
+                if (fclose(mf) != 0) die("write failed on " + o.matches_file);
+            }
         } else if (sets) {
             // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
             typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, uint32_t *,
@@ -458,6 +489,9 @@ int main(int argc, char **argv)
     if (!o.edge_counts_file.empty() && o.refine != "sets") die("--edge-counts needs --refine sets");
     if (!o.edge_counts_file.empty() && !o.matches_file.empty()) die("--edge-counts and --matches exclude each other");
     if (!o.edge_counts_file.empty() && !o.vertex_counts_file.empty()) die("--edge-counts and --vertex-counts exclude each other");
+    if (!o.delta_edges_file.empty() && o.refine != "sets") die("--delta-edges needs --refine sets");
+    if (!o.delta_edges_file.empty() && (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty()))
+        die("--delta-edges excludes --all-matches, --vertex-counts and --edge-counts");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "

@@ -173,6 +173,36 @@ int gnnpe_host_refine_sets_edge_counts(uint32_t n, const uint32_t *offsets, cons
     return 0;
 }
 
+int gnnpe_host_refine_sets_delta(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                 const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *delta_edges,
+                                 uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers)
+{
+    const char *who = "gnnpe_host_refine_sets_delta";
+    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || (!delta_edges && n_delta)) {
+        gnnpe::set_error("%s: null argument", who);
+        return GNNPE_ERR_ARG;
+    }
+    *answers = 0;
+    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
+        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
+        return GNNPE_ERR_ARG;
+    }
+    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
+    gnnpe_host::QuerySymmetry sym;
+    if (distinct) sym = gnnpe_host::query_symmetry(q);
+    if (gnnpe_host::refine_sets_delta_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, delta_edges, n_delta, limit, answers, &err,
+                                            distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
+        *answers = 0;
+        gnnpe::set_error("%s: %s", who, err.c_str());
+        return GNNPE_ERR_ARG;
+    }
+    return 0;
+}
+
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
 {
     if (!query_graph_path || !n_edges || (!edges && cap)) {

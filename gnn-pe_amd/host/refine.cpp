@@ -47,24 +47,12 @@ struct Search {
 
 }  // namespace
 
-int build_match_order(const StaticGraph &query, const std::vector<uint64_t> &cnt, MatchOrder *out, std::string *err)
+// the rule after the first positions: always the unvisited vertex with the most visited neighbours (the smaller id on a tie); its
+// pivot is its first earlier neighbour in the order, the others are its back neighbours
+static int grow_match_order(const StaticGraph &query, std::vector<uint8_t> &seen, MatchOrder *out, std::string *err)
 {
     const uint32_t nq = query.n;
-    if (!out || cnt.size() != nq || nq == 0) {
-        if (err) *err = "build_match_order: one candidate count per query vertex expected";
-        return -2;
-    }
-    // start vertex: fewest candidates, then larger degree, then smaller id (custom.h:634-654)
-    uint32_t start = 0;
-    for (uint32_t u = 1; u < nq; u++)
-        if (cnt[u] < cnt[start] || (cnt[u] == cnt[start] && query.degree(u) > query.degree(start))) start = u;
-    out->order.assign(1, start);
-    out->pivot.assign(1, start);
-    out->back.clear();
-    out->back_off.assign(2, 0);
-    std::vector<uint8_t> seen(nq, 0);
-    seen[start] = 1;
-    for (uint32_t step = 1; step < nq; step++) {
+    for (uint32_t step = (uint32_t)out->order.size(); step < nq; step++) {
         uint32_t best = nq, best_links = 0;
         for (uint32_t u = 0; u < nq; u++) {
             if (seen[u]) continue;
@@ -90,6 +78,43 @@ int build_match_order(const StaticGraph &query, const std::vector<uint64_t> &cnt
         seen[best] = 1;
     }
     return 0;
+}
+
+int build_match_order(const StaticGraph &query, const std::vector<uint64_t> &cnt, MatchOrder *out, std::string *err)
+{
+    const uint32_t nq = query.n;
+    if (!out || cnt.size() != nq || nq == 0) {
+        if (err) *err = "build_match_order: one candidate count per query vertex expected";
+        return -2;
+    }
+    // start vertex: fewest candidates, then larger degree, then smaller id (custom.h:634-654)
+    uint32_t start = 0;
+    for (uint32_t u = 1; u < nq; u++)
+        if (cnt[u] < cnt[start] || (cnt[u] == cnt[start] && query.degree(u) > query.degree(start))) start = u;
+    out->order.assign(1, start);
+    out->pivot.assign(1, start);
+    out->back.clear();
+    out->back_off.assign(2, 0);
+    std::vector<uint8_t> seen(nq, 0);
+    seen[start] = 1;
+    return grow_match_order(query, seen, out, err);
+}
+
+int build_match_order_from_edge(const StaticGraph &query, uint32_t a, uint32_t b, MatchOrder *out, std::string *err)
+{
+    const uint32_t nq = query.n;
+    if (!out || a >= nq || b >= nq || a == b ||
+        !std::binary_search(query.neighbors.begin() + query.offsets[a], query.neighbors.begin() + query.offsets[a + 1], b)) {
+        if (err) *err = "build_match_order_from_edge: (a, b) must be an edge of the query";
+        return -2;
+    }
+    out->order = {a, b};
+    out->pivot = {a, a};
+    out->back.clear();
+    out->back_off.assign(3, 0);  // neither position has a back neighbour
+    std::vector<uint8_t> seen(nq, 0);
+    seen[a] = seen[b] = 1;
+    return grow_match_order(query, seen, out, err);
 }
 
 int refine_count(const StaticGraph &data, const StaticGraph &query, const std::vector<std::vector<uint32_t>> &cand,

@@ -29,6 +29,10 @@ struct MatchOrder {
 };
 int build_match_order(const StaticGraph &query, const std::vector<uint64_t> &candidate_counts, MatchOrder *out, std::string *err);
 
+// The same order anchored at a query edge: order[0] = a, order[1] = b with pivot a, then the rule above with its ties, pivots and
+// back lists.  (a, b) must be an edge of the query; a disconnected query is refused.
+int build_match_order_from_edge(const StaticGraph &query, uint32_t a, uint32_t b, MatchOrder *out, std::string *err);
+
 // candidates[u] = ascending data vertex ids of query vertex u.  Returns 0 and *answers, or <0 with *err
 // (disconnected query graph, size mismatch).
 int refine_count(const StaticGraph &data, const StaticGraph &query, const std::vector<std::vector<uint32_t>> &candidates,

@@ -23,7 +23,8 @@ struct SetSearch {
     uint64_t count = 0, limit;
     uint64_t *vcounts = nullptr;              // vertex counts: nq x g.n cells, every find adds 1 to the cell of each of its images
     uint64_t *ecounts = nullptr;              // edge counts: qedges.size() x g.offsets[g.n] cells, every find adds 1 per query edge
-    std::vector<std::pair<uint32_t, uint32_t>> qedges;  // query_edges(q), for ecounts
+    std::vector<std::pair<uint32_t, uint32_t>> qedges;  // query_edges(q), for ecounts and delta
+    const std::vector<uint64_t> *delta = nullptr;       // delta: ascending keys (min << 32) | max; a find with no query edge on one is dropped
 
     bool in_set(uint32_t u, uint32_t v) const { return (bitmap[(size_t)u * words + (v >> 5)] >> (v & 31)) & 1u; }
     bool fits(uint32_t u, uint32_t v) const
@@ -38,6 +39,12 @@ struct SetSearch {
     void extend(size_t depth)
     {
         if (depth == order.size()) {
+            if (delta) {
+                bool touches = false;
+                for (size_t k = 0; k < qedges.size() && !touches; k++)
+                    touches = std::binary_search(delta->begin(), delta->end(), delta_key(image[qedges[k].first], image[qedges[k].second]));
+                if (!touches) return;
+            }
             count++;
             if (vcounts)
                 for (uint32_t u = 0; u < q.n; u++) vcounts[(size_t)u * g.n + image[u]]++;
@@ -80,10 +87,11 @@ struct SetSearch {
 
 }  // namespace
 
-// refine_sets_count (no table), refine_sets_vertex_counts and refine_sets_edge_counts: one search, a table is filled at the finds
+// refine_sets_count (no table), refine_sets_vertex_counts and refine_sets_edge_counts: one search, a table is filled at the finds;
+// refine_sets_delta_count: the same search, a find that touches no edge of `delta` is dropped
 static int refine_sets_search(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
                               uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced,
-                              uint64_t *vcounts, uint64_t *ecounts = nullptr)
+                              uint64_t *vcounts, uint64_t *ecounts = nullptr, const std::vector<uint64_t> *delta = nullptr)
 {
     const uint32_t nq = query.n;
     if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
@@ -98,7 +106,7 @@ static int refine_sets_search(const StaticGraph &data, const StaticGraph &query,
     SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
                 std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0),
                 std::vector<uint8_t>(data.n, 0), 0, limit, vcounts, ecounts,
-                ecounts ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>()};
+                ecounts || delta ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>(), delta};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
     // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
     for (uint32_t i = 1; induced && i < nq; i++)
@@ -180,6 +188,45 @@ int refine_sets_edge_counts(const StaticGraph &data, const StaticGraph &query, c
     const int rc = refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, nullptr, cells ? counts : nullptr);
     if (rc == 0) *complete = *answers < limit;  // as in refine_sets_vertex_counts
     return rc;
+}
+
+int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys, std::string *err)
+{
+    keys->clear();
+    if (n_delta && !delta_edges) {
+        if (err) *err = "delta edges: null argument";
+        return -2;
+    }
+    for (uint64_t i = 0; i < n_delta; i++) {
+        const uint32_t x = delta_edges[2 * i], y = delta_edges[2 * i + 1];
+        if (x == y || x >= n || y >= n) {
+            if (err) *err = "delta edge " + std::to_string(i) + " (" + std::to_string(x) + ", " + std::to_string(y) + "): " +
+                            (x == y ? "a loop" : "a vertex id the graph does not have");
+            return -2;
+        }
+        keys->push_back(delta_key(x, y));
+    }
+    std::sort(keys->begin(), keys->end());
+    keys->erase(std::unique(keys->begin(), keys->end()), keys->end());
+    return 0;
+}
+
+int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
+                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+{
+    if (answers) *answers = 0;
+    std::vector<uint64_t> keys;
+    if (delta_edge_keys(data.n, delta_edges, n_delta, &keys, err) != 0) return -2;
+    for (uint64_t key : keys) {
+        const uint32_t x = (uint32_t)(key >> 32), y = (uint32_t)key;
+        if (!std::binary_search(data.neighbors.begin() + data.offsets[x], data.neighbors.begin() + data.offsets[x + 1], y)) {
+            if (err) *err = "delta edge (" + std::to_string(x) + ", " + std::to_string(y) + ") is not an edge of the graph";
+            return -2;
+        }
+    }
+    // (an empty F drops every find; the walk still refuses what refine_sets_count refuses)
+    return refine_sets_search(data, query, bitmap, words, keys.empty() ? 0 : limit, answers, err, pairs, induced, nullptr, nullptr, &keys);
 }
 
 }  // namespace gnnpe_host

@@ -7,6 +7,7 @@
 // build_match_order (refine.h); the count does not depend on the order.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <utility>
@@ -63,6 +64,21 @@ std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query)
 // no table: counts may then be null.
 int refine_sets_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
                             uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
+                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+
+// An undirected data edge {x, y} as one word: (min << 32) | max.
+inline uint64_t delta_key(uint32_t x, uint32_t y) { return ((uint64_t)std::min(x, y) << 32) | std::max(x, y); }
+
+// F of the delta calls as ascending keys, each edge once: delta_edges holds n_delta pairs (x, y), either orientation, repeats
+// tolerated.  A loop or an id >= n returns <0 with *err; whether a pair is an edge of the graph is not looked at here.
+int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys, std::string *err);
+
+// Delta_m(C, F, limit) of include/gnnpe_online.h: min(limit, the maps refine_sets_count counts (same pairs, same induced) that put
+// at least one query edge on an edge of F), each once.  The backtracking of refine_sets_count, unchanged, with one test at every
+// find: it walks all of M and shares nothing with the edge-anchored search of csrc/gnnpe_refine_delta.hip, whose yardstick it is.
+// A pair that is no edge of the graph is refused (<0 with *err) by a binary search in the data row.
+int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
                             const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
 
 }  // namespace gnnpe_host

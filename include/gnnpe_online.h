@@ -263,6 +263,58 @@ int gnnpe_refine_sets_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, 
                                   uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
                                   void **dev_counts, double *device_ms);
 
+/* ---- ABI version 15: the matches through a given set of data edges, each once ----------------------------------------------
+ * "Which matches use one of these data edges?" is the primitive of incremental (continuous) subgraph matching:
+ *   - edges were added to G: load the new graph and ask for the matches through the added edges -- exactly the new matches;
+ *   - edges are about to be removed: ask on the current graph for the matches through them -- exactly the ones that vanish.
+ * Re-running the query pays for |M| where it needs the difference; pinning endpoints through the bitmap takes 2 nqe calls per
+ * edge and reports a match through several of the edges several times; E_m(C) has the counts per edge, which do not add up to a
+ * count for a SET of edges, and no rows.
+ *
+ * M_m(C) is as in the ABI 13 text, the query edges (a_k, b_k), k = 0 .. nqe - 1, as gnnpe_host_query_edges numbers them.
+ * F is a set of undirected data edges, handed over as delta_edges: n_delta x 2 uint32 pairs (x, y), either orientation; repeats
+ * and both orientations of one edge are tolerated and mean the edge once.
+ *
+ *   Delta_m(C, F, limit) = min(limit, |{ f in M_m(C) : {f(a_k), f(b_k)} in F for at least one k }|)
+ *
+ * Every such map is counted and listed ONCE, however many of its query edges land in F.
+ *   - modes 0 and DISTINCT, G' = G plus F with F disjoint from E(G), the same C: |M(G')| = |M(G)| + Delta(G', F).  The degree
+ *     test does not disturb this: a match that avoids F already has deg_Q(u) distinct neighbours of f(u) in G.
+ *   - the INDUCED modes: Delta is still exactly "the matches on the loaded graph that touch F", but adding an edge can also
+ *     DESTROY induced matches, and those are not Delta of the new graph.
+ *   - F = E(G) and nq >= 2: Delta = |M|.
+ *   - F = {{x, y}}: Delta = the sum over k of E[k][x->y] + E[k][y->x].
+ *   - a single-vertex query has no edge: Delta = 0.  n_delta == 0: Delta = 0.  Nothing is launched in either case.
+ *
+ * Refusals, all GNNPE_ERR_ARG with *answers = 0:
+ *   - x == y, or an id >= n: checked on the host before anything is launched.
+ *   - a pair that is not an edge of the graph.  The device form finds it on the device and reports it with the counter block, in
+ *     the call's single wait; the context stays usable afterwards.  (Where nothing is launched -- limit 0, an empty set, a
+ *     single-vertex query -- the device form does not look the pairs up.)
+ *   - everything else exactly as gnnpe_refine_sets_mode: the whole simple graph on the device, a connected query of 1..32
+ *     vertices, no multigraph state, no unknown mode bits.
+ *
+ * gnnpe_host_refine_sets_delta: the host form.  The backtracking of gnnpe_host_refine_sets_mode, unchanged, with one test at
+ *   every find (is a query edge's image in F: a binary search among the sorted keys (min << 32) | max).  It walks all of M, not
+ *   only Delta: it is the yardstick and shares nothing with the device form's search.
+ * gnnpe_refine_sets_delta: the device form (csrc/gnnpe_refine_delta.hip): one launch per query edge k over one item per directed
+ *   entry of F, in a matching order that starts at (a_k, b_k); a map is kept in the launch of its lowest-numbered query edge
+ *   in F only.  Its cost follows Delta and nqe, not |M|.
+ *   - matches, matches_cap and the row layout are as gnnpe_refine_sets_mode: the first min(*answers, matches_cap) rows are
+ *     pairwise different maps of the set above.  Which maps come out when limit or the cap cuts, and their order, are
+ *     unspecified.
+ *   - *device_ms (may be NULL) covers the kernels, not the uploads.
+ *   - the buffers are context-owned and grow-only; an allocation the device refuses returns its error and leaves the context
+ *     usable.
+ *   - there is no paged (cursor) form of this call. */
+int gnnpe_host_refine_sets_delta(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                 const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                 const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                 uint64_t *answers);
+int gnnpe_refine_sets_delta(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                            uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
