@@ -1,9 +1,10 @@
 // gnnpe_refine_delta.hip -- THE MATCHES THROUGH A SET OF DATA EDGES, each once: Delta_m(C, F, limit) of include/gnnpe_online.h,
 // the primitive of incremental subgraph matching (the new matches after an insertion, the vanishing ones before a deletion).
 //
-// The search is k_refine_sets' (gnnpe_refine_sets.hip): the same resident grid and tickets, the same loop over the shared steps
-// of gnnpe_refine_sets.hip.h (sets_lane_test, sets_descend), the same leaf (total, rows through the cursor, the flush every 1024
-// finds) and the same polling.  What is this file's own:
+// The search is k_refine_sets' (gnnpe_refine_sets.hip): the same resident grid and tickets, and from gnnpe_refine_sets.hip.h the
+// ticket take (sets_limit_reached, sets_take_ticket), the loop over the shared steps (sets_walk), the leaf (sets_leaf_rows: total, rows through the
+// cursor, the flush every 1024 finds) and the polling; on the host the events, the wait and the error translation (SetsCall).
+// What is this file's own:
 //
 //   * ONE LAUNCH PER QUERY EDGE k = (a_k, b_k), all on the context's stream against one counter block (total, cursor, ticket;
 //     the ticket is cleared by a 4-byte memset between launches), and one wait at the end.  The plan of launch k comes from
@@ -22,18 +23,13 @@
 //     the set of the definition, every map once, and a subtree that belongs to an earlier launch is cut at its first vertex.
 //   * one item per entry is all the balancing there is: a single delta edge between two hubs under a large query runs on one
 //     wave.
-// The shared device code is used as it is; the test above is ANDed onto its result here.
+// The shared device code is used as it is; the test above is this kernel's `test` hook of the walk, ANDed onto the lane test's
+// result.
 // Resources of the four instantiations and the measurement: profiles/online_delta.txt.
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_refine_sets.hip.h"
 
 namespace gnnpe {
-
-struct DeltaCounters {  // one 32-byte block, zeroed once per call; the ticket alone is cleared between the launches
-    unsigned long long total, cursor;
-    uint32_t ticket, bad, pad[2];  // bad != 0: a pair of F is no edge of the graph
-};
-static_assert(sizeof(DeltaCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
 
 struct SetsDelta {  // by position: bit i < d of older[d] = positions i and d are joined by a query edge numbered below the launch's
     uint32_t older[kSetsMaxQ];
@@ -57,7 +53,7 @@ __device__ __forceinline__ bool delta_has(const unsigned long long *__restrict__
 // one lane per directed pair (x, y), both below n: the index of y in x's row, or kDeltaNoEntry and the error flag
 static __global__ void k_delta_entries(uint32_t n_pairs, const uint32_t *__restrict__ pairs, const uint32_t *__restrict__ adj_start,
                                        const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
-                                       uint32_t *__restrict__ ent, DeltaCounters *ctr)
+                                       uint32_t *__restrict__ ent, SetsCounters *ctr)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pairs) return;
@@ -85,23 +81,20 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta(SetsPlan P, SetsDelta D
                                                         const uint32_t *__restrict__ adj_start,
                                                         const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
                                                         const uint32_t *__restrict__ labels, const uint32_t *__restrict__ bitmap,
-                                                        uint64_t words, unsigned long long limit, DeltaCounters *ctr,
+                                                        uint64_t words, unsigned long long limit, SetsCounters *ctr,
                                                         uint32_t *__restrict__ matches, unsigned long long matches_cap, Ord... ord)
 {
     __shared__ SetsWave s_wave[kSetsWavesPerBlock];
     volatile SetsWave &S = s_wave[threadIdx.x >> 6];
     const SetsGraph G = {adj_start, adj_deg, nbrs, labels, bitmap, words};
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nq = P.nq, last = nq - 1;
+    const uint32_t last = P.nq - 1;
     bool rows_full = matches == nullptr;  // no row left to reserve
 
     for (;;) {
-        if (__hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) return;
-        uint32_t q = 0;
-        if (lane == 0) q = atomicAdd(&ctr->ticket, 1u);
-        q = uni(q);
+        if (sets_limit_reached(ctr, limit)) return;
+        const uint32_t q = sets_take_ticket(ctr, lane);
         if (q >= n_items) return;
-
         // item q -> the directed entry x -> y at index j of the CSR; x is tested as position 0, depth 1 is held to [j, j + 1)
         const uint32_t j = uni(ent[q]);
         if (j == kDeltaNoEntry) continue;  // no edge of the graph: the call is refused
@@ -120,67 +113,23 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta(SetsPlan P, SetsDelta D
         unsigned long long pending = 0;  // finds not yet added to the total
         bool stop = false;
 
-        // the chunk of survivors at the last depth: count them, store their rows
-        auto leaf = [&](uint32_t d, bool ok, uint32_t v) {
-            const unsigned long long m = __ballot(ok);
-            const uint32_t cnt = (uint32_t)__popcll(m);
-            if (cnt == 0) return;
-            if (!rows_full) {
-                unsigned long long slot = 0;
-                if (lane == 0) slot = atomicAdd(&ctr->cursor, (unsigned long long)cnt);
-                slot = uni64(slot);
-                if (slot >= matches_cap) rows_full = true;
-                slot += (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-                if (ok && slot < matches_cap) {
-                    uint32_t *row = matches + slot * nq;
-                    for (uint32_t i = 0; i < d; i++) row[P.qv[i]] = S.image[i];
-                    row[P.qv[d]] = v;
+        sets_walk<kOrdered>(
+            P, S, G, ctr, limit, lane, pending, stop, last,
+            // the charging rule: a query edge numbered below this launch's must not land in F
+            [&](uint32_t d, uint32_t v) {
+                bool ok = true;
+                for (uint32_t o = uni(D.older[d]); o && ok; o &= o - 1u) {
+                    const uint32_t w = uni(S.image[__builtin_ctz(o)]);
+                    ok = !delta_has(keys, n_keys, ((unsigned long long)min(v, w) << 32) | max(v, w));
                 }
-            }
-            pending += cnt;
-            if (pending >= 1024ull) {
-                unsigned long long before = 0;
-                if (lane == 0) before = atomicAdd(&ctr->total, pending);
-                before = uni64(before);
-                stop = before + pending >= limit;
-                pending = 0;
-            }
-        };
-
-        uint32_t d = 1, steps = 0;
-        while (d >= 1 && !stop) {
-            // a subtree that finds little still hears of the limit: a look at the total every 1024 chunks
-            if ((++steps & 1023u) == 0 &&
-                __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + pending >= limit)
-                break;
-            unsigned long long m = ((unsigned long long)uni(S.mask_hi[d]) << 32) | uni(S.mask_lo[d]);
-            if (m == 0) {
-                // next chunk of the pivot row
-                const uint32_t cb = uni(S.cbase[d]) + 64u, ce = uni(S.end[d]);
-                if ((int32_t)(ce - cb) <= 0) {
-                    d--;
-                    continue;
-                }
-                S.cbase[d] = cb;
-                uint32_t v;
-                bool ok = sets_lane_test<kOrdered>(P, S, G, d, cb, ce, lane, v, ord...);
-                // the charging rule: a query edge numbered below this launch's must not land in F
-                if (ok) {
-                    for (uint32_t o = uni(D.older[d]); o && ok; o &= o - 1u) {
-                        const uint32_t w = uni(S.image[__builtin_ctz(o)]);
-                        ok = !delta_has(keys, n_keys, ((unsigned long long)min(v, w) << 32) | max(v, w));
-                    }
-                }
-                if (d == last) {
-                    leaf(d, ok, v);
-                    continue;
-                }
-                m = __ballot(ok);
-                if (m == 0) continue;
-            }
-            sets_descend<kOrdered>(P, S, G, d, m, lane, ord...);
-        }
-        if (pending && lane == 0) atomicAdd(&ctr->total, pending);
+                return ok;
+            },
+            // the chunk of survivors at the last depth: count them, store their rows
+            [&](uint32_t d, uint32_t, bool ok, uint32_t v) {
+                sets_leaf_rows(P, S, ctr, limit, matches, matches_cap, rows_full, lane, d, ok, v, pending, stop);
+            },
+            SetsNoHook{}, SetsNoHook{}, ord...);
+        sets_item_end(ctr, lane, pending);
         if (stop) return;
     }
 }
@@ -255,71 +204,48 @@ extern "C" int gnnpe_refine_sets_delta(gnnpe_ctx *c, const char *query_graph_pat
     if ((rc = c->q_work.reserve(SetsWork::kCtrBytes)) || (rc = c->q_bitmap.reserve(bm_bytes)) ||
         (rc = c->q_delta.reserve(DeltaBuf::bytes(n_keys))) || (matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))))
         return rc;
-    DeltaCounters *ctr = c->q_work.as<DeltaCounters>();
+    SetsCounters *ctr = c->q_work.as<SetsCounters>();
     const DeltaBuf F(c->q_delta, n_keys);
     uint32_t *d_rows = matches_cap ? c->q_matches.as<uint32_t>() : nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t he = hipSuccess;
-    if (device_ms) he = hipEventCreate(&ev0);
-    if (he == hipSuccess && device_ms) he = hipEventCreate(&ev1);
-    if (he == hipSuccess) he = hipMemcpyAsync(F.keys, keys.data(), n_keys * 8, hipMemcpyHostToDevice, c->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(F.pairs, pairs.data(), n_keys * 16, hipMemcpyHostToDevice, c->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(c->q_bitmap.p, candidate_bitmap, bm_bytes, hipMemcpyHostToDevice, c->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(ctr, 0, SetsWork::kCtrBytes, c->stream);
-    if (he == hipSuccess && device_ms) he = hipEventRecord(ev0, c->stream);
+    SetsCall call(who, c, device_ms != nullptr);
+    if (call.ok()) call.he = hipMemcpyAsync(F.keys, keys.data(), n_keys * 8, hipMemcpyHostToDevice, c->stream);
+    if (call.ok()) call.he = hipMemcpyAsync(F.pairs, pairs.data(), n_keys * 16, hipMemcpyHostToDevice, c->stream);
+    if (call.ok()) call.he = hipMemcpyAsync(c->q_bitmap.p, candidate_bitmap, bm_bytes, hipMemcpyHostToDevice, c->stream);
+    if (call.ok()) call.he = hipMemsetAsync(ctr, 0, SetsWork::kCtrBytes, c->stream);
+    if (call.ok() && call.ev0) call.he = hipEventRecord(call.ev0, c->stream);
     // a resident grid, or as many waves as there are items
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(sets_grid_blocks(c, nq, n_items), (n_items + kSetsWavesPerBlock - 1) / kSetsWavesPerBlock);
     if (c->sw.debug)
         fprintf(stderr, "[refine_delta] edges=%zu items=%u launches=%zu blocks=%u pairs=%u nonedges=%u\n", n_keys, n_items, qe.size(), blocks,
                 plans[0].n_pairs, plans[0].n_non);
-    if (he == hipSuccess) {
+    call.launch([&] {
         hipLaunchKernelGGL(k_delta_entries, dim3((n_items + 255) / 256), dim3(256), 0, c->stream, n_items, F.pairs, c->adj_start.as<uint32_t>(),
                            c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), F.ent, ctr);
-        he = hipGetLastError();
-    }
-    for (size_t k = 0; k < qe.size() && he == hipSuccess; k++) {
+    });
+    for (size_t k = 0; k < qe.size(); k++) {
         const SetsQuery &K = plans[k];
-        auto launch = [&](auto... ord) {
-            hipLaunchKernelGGL((k_refine_delta<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0, c->stream, K.P,
-                               older[k], n_items, F.pairs, F.ent, F.keys, (uint32_t)n_keys, c->adj_start.as<uint32_t>(),
-                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), Q.words,
-                               (unsigned long long)limit, ctr, d_rows, (unsigned long long)matches_cap, ord...);
-        };
-        if (k) he = hipMemsetAsync(&ctr->ticket, 0, 4, c->stream);  // the next launch's tickets; total and cursor go on
-        if (he != hipSuccess) break;
+        if (k && call.ok()) call.he = hipMemsetAsync(&ctr->ticket, 0, 4, c->stream);  // the next launch's tickets; total and cursor go on
         // (the pairs and the non-edges are the query's, whatever the order: every launch runs the same instantiation)
-        if (K.n_non)
-            K.n_pairs ? launch(K.O, K.N) : launch(K.N);
-        else
-            K.n_pairs ? launch(K.O) : launch();
-        he = hipGetLastError();
+        call.launch([&] {
+            sets_dispatch(K, [&](auto... ord) {
+                hipLaunchKernelGGL((k_refine_delta<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0, c->stream,
+                                   K.P, older[k], n_items, F.pairs, F.ent, F.keys, (uint32_t)n_keys, c->adj_start.as<uint32_t>(),
+                                   c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
+                                   Q.words, (unsigned long long)limit, ctr, d_rows, (unsigned long long)matches_cap, ord...);
+            });
+        });
     }
-    if (he == hipSuccess && device_ms) he = hipEventRecord(ev1, c->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(c->h_pinned, ctr, sizeof(DeltaCounters), hipMemcpyDeviceToHost, c->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);  // the one wait of the call
-    if (he == hipSuccess) {
-        const uint32_t bad = reinterpret_cast<const uint32_t *>(c->h_pinned)[5];
-        if (bad) {
+    call.wait(ctr, sizeof(SetsCounters));  // all of it: `bad` is in the second half
+    if (call.ok()) {
+        if (reinterpret_cast<const SetsCounters *>(c->h_pinned)->bad) {
             set_error("%s: a delta edge is not an edge of the graph", who);
-            rc = GNNPE_ERR_ARG;
+            call.rc = GNNPE_ERR_ARG;
         } else {
             *answers = std::min<uint64_t>(c->h_pinned[0], limit);
             // every find reserved a row, so the first min(cursor, cap) rows are written
             const uint64_t n_rows = std::min<uint64_t>(c->h_pinned[1], matches_cap);
-            if (n_rows) he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
+            if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
         }
     }
-    if (he == hipSuccess && !rc && device_ms) {
-        float ms = 0.f;
-        he = hipEventElapsedTime(&ms, ev0, ev1);
-        *device_ms = ms;
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipStreamSynchronize(c->stream);
-    if (!rc && he != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(he));
-        rc = GNNPE_ERR_HIP;
-    }
-    return rc;
+    return call.finish(device_ms);
 }

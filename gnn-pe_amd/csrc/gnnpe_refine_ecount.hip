@@ -3,15 +3,16 @@
 // of the loaded CSR (nqe x entries uint64, row-major).
 //
 // The search is k_refine_vcount's (gnnpe_refine_vcount.hip), which is k_refine_sets': the same resident grid, tickets and
-// first-level items, the same loop over the shared steps of gnnpe_refine_sets.hip.h, used as they are, the same `pending` / total
-// flush every 1024 finds, 1024-chunk poll and three exits.  It writes no rows.  What it adds is the table, one level finer than
-// the per-vertex one:
+// first-level items, and from gnnpe_refine_sets.hip.h the ticket take, the loop over the shared steps (sets_walk), the `pending` /
+// total flush every 1024 finds, the 1024-chunk poll and the three exits, the tallies (SetsTally) and on the host the table
+// handling (sets_count_call).  It writes no rows.  What is this file's own is the table, one level finer than the per-vertex one
+// -- the plan edges, ient[], the leaf and flush below, hooked into the walk where k_refine_vcount's are -- and the entry point:
 //
 //   * every plan edge -- the pivot edge of position d >= 1 and each of its back edges -- carries a word (k << 1) | flip from the
 //     host (EcountEdges, by value beside the plan).  k is the query edge's number; flip = 1 when the EARLIER position's query
 //     vertex is b_k: the entry to credit then runs from the image of d to the earlier image.
 //   * per wave in LDS (EcountWave, this kernel's own; SetsWave is untouched): tally[d], the finds below the current image of
-//     position d, as in VcountTally, and ient[d], the CSR index of the entry (image of pivot[d] -> image of d): cbase[d] + ctz(m),
+//     position d (the shared SetsTally), and ient[d], the CSR index of the entry (image of pivot[d] -> image of d): cbase[d] + ctz(m),
 //     taken immediately before sets_descend at depth d.  Every lane writes every word.  Reads go through uni(), but for the
 //     lanes of flush(), which each read the image and the row of THEIR edge's earlier position.
 //   * flush(d), d >= 1, tally t != 0: lane i takes the i-th edge of position d (lane 0 the pivot edge, then the back edges: at
@@ -35,31 +36,15 @@
 
 namespace gnnpe {
 
-struct EcountCounters {  // one 32-byte block, zeroed before every launch; the host reads the first 16 bytes
-    unsigned long long total, flush_adds;  // finds; the atomic adds of flush() (the leaf's are finds x deg_Q(last position))
-    uint32_t ticket, pad[3];
-};
-static_assert(sizeof(EcountCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
-
 struct EcountEdges {  // (k << 1) | flip of every plan edge: 64 + 992 bytes by value
     uint16_t pivot[kSetsMaxQ];                            // of position d's pivot edge (d >= 1)
     uint16_t back[kSetsMaxQ * (kSetsMaxQ - 1) / 2];       // of P.back[j]
 };
 
 struct EcountWave {  // per wave in LDS, wave-uniform
-    uint32_t lo[kSetsMaxQ], hi[kSetsMaxQ];  // finds below the current image of a position, low and high word
-    uint32_t ient[kSetsMaxQ];               // CSR index of the entry (image of pivot[d] -> image of d)
+    SetsTally tally;            // finds below the current image of a position
+    uint32_t ient[kSetsMaxQ];   // CSR index of the entry (image of pivot[d] -> image of d)
 };
-
-__device__ __forceinline__ unsigned long long etally_get(const volatile EcountWave &T, uint32_t d)
-{
-    return ((unsigned long long)uni(T.hi[d]) << 32) | uni(T.lo[d]);
-}
-__device__ __forceinline__ void etally_set(volatile EcountWave &T, uint32_t d, unsigned long long x)
-{
-    T.lo[d] = (uint32_t)x;
-    T.hi[d] = (uint32_t)(x >> 32);
-}
 
 // index in nbrs of `target` in the ascending row [st, st + d), kNoEdge if it is not there
 __device__ __forceinline__ uint32_t row_pos(const uint32_t *__restrict__ nbrs, uint32_t st, uint32_t d, uint32_t target)
@@ -100,13 +85,14 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
                                                          const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
                                                          const uint32_t *__restrict__ labels, const uint32_t *__restrict__ bitmap,
                                                          uint64_t words, const uint32_t *__restrict__ revpos, unsigned long long limit,
-                                                         EcountCounters *ctr, unsigned long long *__restrict__ counts, uint64_t entries,
+                                                         SetsCounters *ctr, unsigned long long *__restrict__ counts, uint64_t entries,
                                                          Ord... ord)
 {
     __shared__ SetsWave s_wave[kSetsWavesPerBlock];
     __shared__ EcountWave s_tally[kSetsWavesPerBlock];
     volatile SetsWave &S = s_wave[threadIdx.x >> 6];
-    volatile EcountWave &T = s_tally[threadIdx.x >> 6];
+    volatile EcountWave &E = s_tally[threadIdx.x >> 6];
+    volatile SetsTally &T = E.tally;
     const SetsGraph G = {adj_start, adj_deg, nbrs, labels, bitmap, words};
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nq = P.nq, last = nq - 1;
@@ -114,32 +100,22 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
     const uint32_t n_items = nq == 1 ? (n_cand + 63u) / 64u : item_off[n_cand];
 
     for (;;) {
-        if (__hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) return;  // EXIT 1
-        uint32_t q = 0;
-        if (lane == 0) q = atomicAdd(&ctr->ticket, 1u);
-        q = uni(q);
+        if (sets_limit_reached(ctr, limit)) return;
+        const uint32_t q = sets_take_ticket(ctr, lane);
         if (q >= n_items) return;
-
         unsigned long long pending = 0;  // finds not yet added to the total
         bool stop = false;
         uint32_t flushed = 0;  // adds of flush() in this item: one more add per item for the GNNPE_DEBUG line, nothing reads it back
-        for (uint32_t d = 0; d < last; d++) etally_set(T, d, 0ull);
+        for (uint32_t d = 0; d < last; d++) tally_set(T, d, 0ull);
 
-        // cnt finds more: to the depth above the last and, every 1024, to the total
+        // cnt finds more: to the depth above the last and to the total
         auto found = [&](uint32_t cnt) {
-            if (last >= 1) etally_set(T, last - 1, etally_get(T, last - 1) + cnt);
-            pending += cnt;
-            if (pending >= 1024ull) {
-                unsigned long long before = 0;
-                if (lane == 0) before = atomicAdd(&ctr->total, pending);
-                before = uni64(before);
-                stop = before + pending >= limit;  // EXIT 2
-                pending = 0;
-            }
+            if (last >= 1) tally_set(T, last - 1, tally_get(T, last - 1) + cnt);
+            sets_found(ctr, limit, lane, cnt, pending, stop);
         };
         // the chunk [cb, ..) of survivors at the last depth: every survivor adds 1 to the entry of each query edge of the last
         // position -- its own pivot entry cb + lane and one per back edge --, their number goes to the depth above
-        auto leaf = [&](uint32_t cb, bool ok, uint32_t v) {
+        auto leaf = [&](uint32_t, uint32_t cb, bool ok, uint32_t v) {
             const uint32_t cnt = (uint32_t)__popcll(__ballot(ok));
             if (cnt == 0) return;
             if (ok) {
@@ -159,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
         // the subtree of position d's current image is complete: its finds to the entries of the position's query edges, one
         // lane each, and to the depth above
         auto flush = [&](uint32_t d) {
-            const unsigned long long t = etally_get(T, d);
+            const unsigned long long t = tally_get(T, d);
             if (t == 0) return;
             if (d >= 1) {
                 const uint32_t nb = (uint32_t)P.back_off[d + 1] - P.back_off[d];
@@ -168,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
                     uint32_t j, w16;
                     if (lane == 0) {
                         w16 = X.pivot[d];
-                        j = uni(T.ient[d]);
+                        j = uni(E.ient[d]);
                         if (w16 & 1u) j = entry_reverse(revpos, j, vs);
                     } else {
                         const uint32_t e = P.back_off[d] + lane - 1u, b = P.back[e];
@@ -177,10 +153,10 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
                     }
                     if (j != kNoEdge) atomicAdd(&counts[(uint64_t)(w16 >> 1) * entries + j], t);
                 }
-                etally_set(T, d - 1, etally_get(T, d - 1) + t);
+                tally_set(T, d - 1, tally_get(T, d - 1) + t);
                 flushed += nb + 1u;
             }
-            etally_set(T, d, 0ull);
+            tally_set(T, d, 0ull);
         };
 
         if (nq == 1) {  // no edge, no table: the finds alone
@@ -188,38 +164,17 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
             const uint32_t cnt = (uint32_t)__popcll(__ballot(sets_single_test(P, G, n_cand, i, v)));
             if (cnt) found(cnt);
         } else if (sets_item_decode(P, S, G, n_cand, cand, item_off, w_shift, q)) {
-            uint32_t d = 1, steps = 0;
-            while (d >= 1 && !stop) {
-                // a subtree that finds little still hears of the limit: a look at the total every 1024 chunks
-                if ((++steps & 1023u) == 0 &&
-                    __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + pending >= limit)
-                    break;  // EXIT 3
-                unsigned long long m = ((unsigned long long)uni(S.mask_hi[d]) << 32) | uni(S.mask_lo[d]);
-                if (m == 0) {
-                    // next chunk of the pivot row
-                    const uint32_t cb = uni(S.cbase[d]) + 64u, ce = uni(S.end[d]);
-                    if ((int32_t)(ce - cb) <= 0) {
-                        if (d < last) flush(d);  // the last sibling of this depth
-                        d--;
-                        continue;
-                    }
-                    S.cbase[d] = cb;
-                    uint32_t v;
-                    const bool ok = sets_lane_test<kOrdered>(P, S, G, d, cb, ce, lane, v, ord...);
-                    if (d == last) {
-                        leaf(cb, ok, v);
-                        continue;
-                    }
-                    m = __ballot(ok);
-                    if (m == 0) continue;
-                }
-                flush(d);  // the previous sibling, before the descent overwrites image[d]
-                T.ient[d] = uni(S.cbase[d]) + (uint32_t)__builtin_ctzll(m);  // the entry the descent takes
-                sets_descend<kOrdered>(P, S, G, d, m, lane, ord...);
-            }
+            sets_walk<kOrdered>(
+                P, S, G, ctr, limit, lane, pending, stop, last, SetsNoHook{}, leaf,
+                flush,  // the last sibling of this depth
+                [&](uint32_t d, unsigned long long m) {
+                    flush(d);  // the previous sibling, before the descent overwrites image[d]
+                    E.ient[d] = uni(S.cbase[d]) + (uint32_t)__builtin_ctzll(m);  // the entry the descent takes
+                },
+                ord...);
             flush(0);
         }
-        if (pending && lane == 0) atomicAdd(&ctr->total, pending);
+        sets_item_end(ctr, lane, pending);
         if (flushed && lane == 0) atomicAdd(&ctr->flush_adds, (unsigned long long)flushed);
         if (stop) return;
     }
@@ -281,74 +236,31 @@ extern "C" int gnnpe_refine_sets_edge_counts(gnnpe_ctx *c, const char *query_gra
         }
         nqe = (uint32_t)gnnpe_host::query_edges(q).size();
     }
-    const size_t table_bytes = (size_t)nqe * entries * 8;
+    const size_t cells = (size_t)nqe * entries;
     unsigned long long *d_counts = nullptr;
-    if (table_bytes) {
+    if (cells) {
         // context-owned, grow-only, of its own: a vertex-count call in between leaves it alone
-        if ((rc = c->q_ecounts.reserve(table_bytes))) return rc;
+        if ((rc = c->q_ecounts.reserve(cells * 8))) return rc;
         d_counts = c->q_ecounts.as<unsigned long long>();
     }
-    if (dev_counts) *dev_counts = d_counts;
-    if (Q.empty) {  // an empty set, or no start candidate: no map, and that is the whole answer
-        if (table_bytes) {
-            GNNPE_HIP_TRY(hipMemsetAsync(d_counts, 0, table_bytes, c->stream));
-            GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
-            if (host_counts) std::fill(host_counts, host_counts + (size_t)nqe * entries, 0ull);
-        }
-        *complete = 1;
-        return GNNPE_OK;
-    }
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t he = hipSuccess;
-    if (device_ms) he = hipEventCreate(&ev0);
-    if (he == hipSuccess && device_ms) he = hipEventCreate(&ev1);
-    if (he == hipSuccess) rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, ev0);
-    if (c->sw.debug)
-        fprintf(stderr, "[refine_ecount] shift=%u forced=%d cands=%u edges=%u flips=%u backflips=%u lastflip=%u hubs=%u cus=%d pairs=%u "
-                        "nonedges=%u\n", Q.w_shift, (int)Q.forced, n_cand, nqe, flips, backflips, nq > 1 ? X.pivot[nq - 1] & 1u : 0u,
-                c->n_hub, c->num_cus, Q.n_pairs, Q.n_non);
-    if (he == hipSuccess && !rc && table_bytes) he = hipMemsetAsync(d_counts, 0, table_bytes, c->stream);
-    if (he == hipSuccess && !rc) {
-        const SetsWork W(c->q_work, n_cand);
-        auto launch = [&](auto... ord) {
+    return sets_count_call(
+        who, c, &Q, candidate_bitmap, limit, d_counts, cells, answers, complete, host_counts, dev_counts, device_ms,
+        [&] {
+            fprintf(stderr, "[refine_ecount] shift=%u forced=%d cands=%u edges=%u flips=%u backflips=%u lastflip=%u hubs=%u cus=%d pairs=%u "
+                            "nonedges=%u\n", Q.w_shift, (int)Q.forced, n_cand, nqe, flips, backflips, nq > 1 ? X.pivot[nq - 1] & 1u : 0u,
+                    c->n_hub, c->num_cus, Q.n_pairs, Q.n_non);
+        },
+        [&](const SetsWork &W, auto... ord) {
             hipLaunchKernelGGL((k_refine_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)),
                                dim3(kBlock), 0, c->stream, Q.P, X, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(),
                                c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
-                               Q.words, c->revpos.as<uint32_t>(), (unsigned long long)limit, static_cast<EcountCounters *>(W.ctr),
+                               Q.words, c->revpos.as<uint32_t>(), (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr),
                                d_counts, entries, ord...);
-        };
-        if (Q.n_non)
-            Q.n_pairs ? launch(Q.O, Q.N) : launch(Q.N);
-        else
-            Q.n_pairs ? launch(Q.O) : launch();
-        he = hipGetLastError();
-        if (he == hipSuccess && device_ms) he = hipEventRecord(ev1, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(c->h_pinned, W.ctr, 16, hipMemcpyDeviceToHost, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);  // the one wait of the call
-    }
-    if (he == hipSuccess && !rc) {
-        *answers = std::min<uint64_t>(c->h_pinned[0], limit);
-        *complete = c->h_pinned[0] < limit ? 1 : 0;
-        if (c->sw.debug) {  // every atomic on the table: deg_Q(last position) leaf adds per find, and the flushes
+        },
+        [&](unsigned long long finds, unsigned long long flush_adds) {
+            // every atomic on the table: deg_Q(last position) leaf adds per find, and the flushes
             const uint32_t leaf_deg = nq > 1 ? 1u + Q.P.back_off[nq] - Q.P.back_off[nq - 1] : 0u;
-            fprintf(stderr, "[refine_ecount] finds=%llu flush_adds=%llu leaf_adds=%llu complete=%d\n", (unsigned long long)c->h_pinned[0],
-                    (unsigned long long)c->h_pinned[1], (unsigned long long)c->h_pinned[0] * leaf_deg, *complete);
-        }
-        // the table comes back only where it is asked for and means something
-        if (host_counts && *complete && table_bytes) he = hipMemcpy(host_counts, d_counts, table_bytes, hipMemcpyDeviceToHost);
-    }
-    if (he == hipSuccess && !rc && device_ms) {
-        float ms = 0.f;
-        he = hipEventElapsedTime(&ms, ev0, ev1);
-        *device_ms = ms;
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipStreamSynchronize(c->stream);
-    if (!rc && he != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(he));
-        rc = GNNPE_ERR_HIP;
-    }
-    return rc;
+            fprintf(stderr, "[refine_ecount] finds=%llu flush_adds=%llu leaf_adds=%llu complete=%d\n", finds, flush_adds, finds * leaf_deg,
+                    *complete);
+        });
 }

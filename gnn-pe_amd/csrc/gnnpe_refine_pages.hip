@@ -319,16 +319,12 @@ int gnnpe_refine_pages_next(gnnpe_match_cursor *cur, uint32_t *host_rows, uint64
     PagesCounters *d_ctr = static_cast<PagesCounters *>(W.ctr);
     GNNPE_HIP_TRY(hipMemsetAsync(d_ctr, 0, kPagesPerLaunchBytes, c->stream));
     GNNPE_HIP_TRY(hipEventRecord(cur->ev0, c->stream));
-    auto launch = [&](auto... ord) {
+    sets_dispatch(Q, [&](auto... ord) {
         hipLaunchKernelGGL((k_refine_pages<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(cur->blocks), dim3(kBlock), 0, c->stream, Q.P, Q.n_cand,
                            W.cand, W.item_off, cur->n_items, Q.w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(),
                            c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), cur->bitmap.as<uint32_t>(), Q.words, d_ctr,
                            cur->slots.as<PagesSlot>(), cur->page.as<uint32_t>(), (unsigned long long)rows_now, ord...);
-    };
-    if (Q.n_non)
-        Q.n_pairs ? launch(Q.O, Q.N) : launch(Q.N);
-    else
-        Q.n_pairs ? launch(Q.O) : launch();
+    });
     GNNPE_HIP_TRY(hipGetLastError());
     GNNPE_HIP_TRY(hipEventRecord(cur->ev1, c->stream));
     GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned, d_ctr, sizeof(PagesCounters), hipMemcpyDeviceToHost, c->stream));

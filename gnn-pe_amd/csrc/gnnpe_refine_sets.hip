@@ -30,21 +30,18 @@
 //     earlier positions that are no query neighbours (SetsNon).  A lane that passed every other test searches each of their
 //     images' rows, or its own, whichever is shorter, and fails if the edge is there: a subtree is cut at its first wrong vertex.
 //     Two more instantiations, plain and ordered; the two above hold none of it.  Figures: profiles/online_induced.txt.
-// host/refine_sets.cpp is the host form.  The paged form of this search (gnnpe_refine_pages.hip) takes the same steps, and every
-// step exists once, in gnnpe_refine_sets.hip.h: the lane test of a chunk, the descent, the item decode and the single-vertex item
-// on the device; the preparation of a query and the staging of its items on the host.  This file keeps what is the one-shot
-// call's own: the kernel's loop, its leaf (total, flush, limit) and its polling; the events and the single wait of the host.
-// The gfx950 code of both kernels against the copies they were: profiles/online_shared_steps.txt.
+// host/refine_sets.cpp is the host form.  Almost all of the above exists once, in gnnpe_refine_sets.hip.h, because other kernels
+// take it too.  The steps -- the lane test of a chunk, the descent, the item decode, the single-vertex item -- and on the host the
+// preparation of a query and the staging of its items are also the paged search's (gnnpe_refine_pages.hip;
+// profiles/online_shared_steps.txt).  The ticket take, the find accounting and the limit, the loop that drives the steps
+// (sets_walk) and the row-writing leaf, and on the host the events, the single wait and the error translation of a call (SetsCall),
+// are also those of the per-vertex and per-edge counts and of the delta matches (gnnpe_refine_vcount.hip, _ecount.hip, _delta.hip;
+// profiles/online_one_walk.txt).  What is this file's own: the kernel's signature and item setup with a leaf that is the shared
+// row leaf and no other hook, and the three entry points of the call.
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_refine_sets.hip.h"
 
 namespace gnnpe {
-
-struct SetsCounters {  // one 32-byte block, zeroed before every launch
-    unsigned long long total, cursor;
-    uint32_t ticket, pad[3];
-};
-static_assert(sizeof(SetsCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
 
 // One kernel, four instantiations.  k_refine_sets<false> is the plain search: the parameter pack is empty, nothing below that is
 // `if constexpr (kOrdered)` exists (here and in the shared steps), and the code is what it was before the ordered form existed.
@@ -71,74 +68,22 @@ __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_c
     bool rows_full = matches == nullptr;  // no row left to reserve
 
     for (;;) {
-        if (__hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) return;
-        uint32_t q = 0;
-        if (lane == 0) q = atomicAdd(&ctr->ticket, 1u);
-        q = uni(q);
+        if (sets_limit_reached(ctr, limit)) return;
+        const uint32_t q = sets_take_ticket(ctr, lane);
         if (q >= n_items) return;
-
         unsigned long long pending = 0;  // finds not yet added to the total
         bool stop = false;
-
         // the chunk of survivors at the last depth: count them, store their rows
-        auto leaf = [&](uint32_t d, bool ok, uint32_t v) {
-            const unsigned long long m = __ballot(ok);
-            const uint32_t cnt = (uint32_t)__popcll(m);
-            if (cnt == 0) return;
-            if (!rows_full) {
-                unsigned long long slot = 0;
-                if (lane == 0) slot = atomicAdd(&ctr->cursor, (unsigned long long)cnt);
-                slot = uni64(slot);
-                if (slot >= matches_cap) rows_full = true;
-                slot += (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-                if (ok && slot < matches_cap) {
-                    uint32_t *row = matches + slot * nq;
-                    for (uint32_t i = 0; i < d; i++) row[P.qv[i]] = S.image[i];
-                    row[P.qv[d]] = v;
-                }
-            }
-            pending += cnt;
-            if (pending >= 1024ull) {
-                unsigned long long before = 0;
-                if (lane == 0) before = atomicAdd(&ctr->total, pending);
-                before = uni64(before);
-                stop = before + pending >= limit;
-                pending = 0;
-            }
+        auto leaf = [&](uint32_t d, uint32_t, bool ok, uint32_t v) {
+            sets_leaf_rows(P, S, ctr, limit, matches, matches_cap, rows_full, lane, d, ok, v, pending, stop);
         };
-
         if (nq == 1) {
             const uint32_t i = q * 64u + lane, v = sets_single_cand(n_cand, cand, i);
-            leaf(0, sets_single_test(P, G, n_cand, i, v), v);
+            leaf(0, 0, sets_single_test(P, G, n_cand, i, v), v);
         } else if (sets_item_decode(P, S, G, n_cand, cand, item_off, w_shift, q)) {
-            uint32_t d = 1, steps = 0;
-            while (d >= 1 && !stop) {
-                // a subtree that finds little still hears of the limit: a look at the total every 1024 chunks
-                if ((++steps & 1023u) == 0 &&
-                    __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + pending >= limit)
-                    break;
-                unsigned long long m = ((unsigned long long)uni(S.mask_hi[d]) << 32) | uni(S.mask_lo[d]);
-                if (m == 0) {
-                    // next chunk of the pivot row
-                    const uint32_t cb = uni(S.cbase[d]) + 64u, ce = uni(S.end[d]);
-                    if ((int32_t)(ce - cb) <= 0) {
-                        d--;
-                        continue;
-                    }
-                    S.cbase[d] = cb;
-                    uint32_t v;
-                    const bool ok = sets_lane_test<kOrdered>(P, S, G, d, cb, ce, lane, v, ord...);
-                    if (d == last) {
-                        leaf(d, ok, v);
-                        continue;
-                    }
-                    m = __ballot(ok);
-                    if (m == 0) continue;
-                }
-                sets_descend<kOrdered>(P, S, G, d, m, lane, ord...);
-            }
+            sets_walk<kOrdered>(P, S, G, ctr, limit, lane, pending, stop, last, SetsNoHook{}, leaf, SetsNoHook{}, SetsNoHook{}, ord...);
         }
-        if (pending && lane == 0) atomicAdd(&ctr->total, pending);
+        sets_item_end(ctr, lane, pending);
         if (stop) return;
     }
 }
@@ -164,11 +109,8 @@ static int refine_sets_run(const char *who, uint32_t mode, gnnpe_ctx *c, const c
 
     // context-owned, grow-only: the work buffer, the bitmap, the rows
     if (matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))) return rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t he = hipSuccess;
-    if (device_ms) he = hipEventCreate(&ev0);
-    if (he == hipSuccess && device_ms) he = hipEventCreate(&ev1);
-    if (he == hipSuccess) rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, ev0);
+    SetsCall call(who, c, device_ms != nullptr);
+    if (call.ok()) call.rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, call.ev0);
     if (c->sw.debug) {
         char pairs[32] = "", non[32] = "";  // a distinct call appends pairs=K, an induced one nonedges=K
         if (mode & GNNPE_MATCH_DISTINCT) snprintf(pairs, sizeof pairs, " pairs=%u", Q.n_pairs);
@@ -177,43 +119,24 @@ static int refine_sets_run(const char *who, uint32_t mode, gnnpe_ctx *c, const c
                 c->num_cus, pairs, non);
     }
     uint32_t *d_rows = matches_cap ? c->q_matches.as<uint32_t>() : nullptr;
-    if (he == hipSuccess && !rc) {
+    call.launch([&] {
         const SetsWork W(c->q_work, n_cand);
-        auto launch = [&](auto... ord) {
+        sets_dispatch(Q, [&](auto... ord) {
             hipLaunchKernelGGL((k_refine_sets<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)), dim3(kBlock), 0,
                                c->stream, Q.P, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(),
                                c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), Q.words,
                                (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr), d_rows, (unsigned long long)matches_cap,
                                ord...);
-        };
-        if (Q.n_non)
-            Q.n_pairs ? launch(Q.O, Q.N) : launch(Q.N);
-        else
-            Q.n_pairs ? launch(Q.O) : launch();
-        he = hipGetLastError();
-        if (he == hipSuccess && device_ms) he = hipEventRecord(ev1, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(c->h_pinned, W.ctr, 16, hipMemcpyDeviceToHost, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);  // the one wait of a counting call
-    }
-    if (he == hipSuccess && !rc) {
+        });
+    });
+    call.wait(c->q_work.p, 16);
+    if (call.ok()) {
         *answers = std::min<uint64_t>(c->h_pinned[0], limit);
         // every find reserved a row, so the first min(cursor, cap) rows are written
         const uint64_t n_rows = std::min<uint64_t>(c->h_pinned[1], matches_cap);
-        if (n_rows) he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
+        if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
     }
-    if (he == hipSuccess && !rc && device_ms) {
-        float ms = 0.f;
-        he = hipEventElapsedTime(&ms, ev0, ev1);
-        *device_ms = ms;
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipStreamSynchronize(c->stream);
-    if (!rc && he != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(he));
-        rc = GNNPE_ERR_HIP;
-    }
-    return rc;
+    return call.finish(device_ms);
 }
 
 extern "C" {

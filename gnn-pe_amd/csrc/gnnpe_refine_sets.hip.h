@@ -1,8 +1,15 @@
-// gnnpe_refine_sets.hip.h -- what the two set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip)
-// and the paged k_refine_pages (gnnpe_refine_pages.hip).  On the device the plan by position in the matching order, the
-// per-wave search state in LDS and every STEP of the search: a chunk's lane test, the descent into a survivor, the decode of a
-// first-level item, the single-vertex item.  Each kernel keeps its own loop, leaf and polling.  On the host the preparation
-// of a query (sets_prepare) and the staging of its first-level items on the device (sets_stage_items).
+// gnnpe_refine_sets.hip.h -- what the set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip),
+// k_refine_vcount, k_refine_ecount and k_refine_delta (the files of those names) and the paged k_refine_pages
+// (gnnpe_refine_pages.hip).
+//   * All five, on the device: the plan by position in the matching order, the per-wave search state in LDS and every STEP of the
+//     search: a chunk's lane test, the descent into a survivor, the decode of a first-level item, the single-vertex item.  On the
+//     host the preparation of a query (sets_prepare), the staging of its first-level items (sets_stage_items) and the choice of
+//     the instantiation (sets_dispatch).
+//   * The four one-shot kernels, on the device: the counter block, the ticket take, the find accounting and the limit, the loop
+//     that drives the steps (sets_walk), the row-writing leaf of two of them and the tallies of the other two.  A kernel keeps
+//     its item setup and its hooks.  On the host the events, the single wait and the error translation of a call (SetsCall) and
+//     the table handling of the two count calls (sets_count_call).
+// k_refine_pages keeps its own loop, leaf and polling.
 #pragma once
 
 #include <hipcub/hipcub.hpp>
@@ -138,7 +145,7 @@ __device__ __forceinline__ void order_trim(const uint32_t *__restrict__ nbrs, ui
 }
 
 // ---- the steps of the search ---------------------------------------------------------------------------------------------------
-// Both kernels build a SetsGraph from their own parameters and keep the conventions of the state: S is read and written through
+// Every kernel builds a SetsGraph from their own parameters and keep the conventions of the state: S is read and written through
 // `volatile SetsWave &`, every word read from it goes through uni(), and no lane reads LDS that another lane alone wrote (every
 // lane writes every word).  The ordered instantiations pass their SetsOrder as the trailing pack, the induced ones their SetsNon
 // (after the SetsOrder, if both), the plain ones nothing.
@@ -254,7 +261,152 @@ __device__ __forceinline__ bool sets_single_test(const SetsPlan &P, const SetsGr
     return i < n_cand && G.labels[v] == P.label[0] && G.adj_deg[v] >= P.degree[0];
 }
 
-// ---- the host's side of both calls -----------------------------------------------------------------------------------------
+// ---- the walk of the one-shot kernels ------------------------------------------------------------------------------------------
+// k_refine_sets, k_refine_vcount, k_refine_ecount and k_refine_delta are one search: a wave takes a ticket, walks the item's subtree
+// chunk by chunk and leaves when the total has reached the limit.  That protocol exists once, here; a kernel adds its item setup and
+// the hooks of sets_walk.  (k_refine_pages suspends and resumes and has no limit: it keeps its own loop over the same steps.)
+// The three places where a wave hears of the limit are marked EXIT 1, 2 and 3; the proof in gnnpe_refine_vcount.hip that a count
+// table is complete iff total < limit rests on these three being the only ones.
+struct SetsCounters {  // the 32-byte block at the head of the work buffer (SetsWork), zeroed before every call
+    unsigned long long total;  // finds, each added once
+    union {
+        unsigned long long cursor;      // k_refine_sets, k_refine_delta: rows reserved
+        unsigned long long flush_adds;  // k_refine_vcount, k_refine_ecount: the atomic adds of their flushes (GNNPE_DEBUG prints it)
+    };
+    uint32_t ticket;  // the next item
+    uint32_t bad;     // k_delta_entries: a pair of F is no edge of the graph
+    uint32_t pad[2];
+};
+
+// the head of a wave's outer loop: the look at the total before an item, and the item's ticket.  A wave whose ticket is not below
+// the item count leaves as well.  (Two functions and the two returns in the kernel: one function with one result costs every
+// kernel a flag and a branch more per item.)
+__device__ __forceinline__ bool sets_limit_reached(const SetsCounters *ctr, unsigned long long limit)
+{
+    return __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit;  // EXIT 1
+}
+__device__ __forceinline__ uint32_t sets_take_ticket(SetsCounters *ctr, uint32_t lane)
+{
+    uint32_t q = 0;
+    if (lane == 0) q = atomicAdd(&ctr->ticket, 1u);
+    return uni(q);
+}
+
+// cnt finds more: `pending` holds a wave's finds not yet added to the total and goes there every 1024; `stop` = that add reached
+// the limit.  Both are registers of the calling kernel.
+__device__ __forceinline__ void sets_found(SetsCounters *ctr, unsigned long long limit, uint32_t lane, uint32_t cnt, unsigned long long &pending,
+                                           bool &stop)
+{
+    pending += cnt;
+    if (pending >= 1024ull) {
+        unsigned long long before = 0;
+        if (lane == 0) before = atomicAdd(&ctr->total, pending);
+        before = uni64(before);
+        stop = before + pending >= limit;  // EXIT 2 (sets_walk and the kernel's `if (stop) return` act on it)
+        pending = 0;
+    }
+}
+
+// the end of an item: what is left of `pending`
+__device__ __forceinline__ void sets_item_end(SetsCounters *ctr, uint32_t lane, unsigned long long pending)
+{
+    if (pending && lane == 0) atomicAdd(&ctr->total, pending);
+}
+
+// the leaf of the kernels that write rows: the survivors `ok` of a chunk at the last position d, lane's candidate v.  One atomic add
+// on the row cursor reserves a row each; lanes whose row is below the cap store image + own v in query-vertex order.
+__device__ __forceinline__ void sets_leaf_rows(const SetsPlan &P, const volatile SetsWave &S, SetsCounters *ctr, unsigned long long limit,
+                                               uint32_t *__restrict__ matches, unsigned long long matches_cap, bool &rows_full, uint32_t lane,
+                                               uint32_t d, bool ok, uint32_t v, unsigned long long &pending, bool &stop)
+{
+    const unsigned long long m = __ballot(ok);
+    const uint32_t cnt = (uint32_t)__popcll(m);
+    if (cnt == 0) return;
+    if (!rows_full) {
+        unsigned long long slot = 0;
+        if (lane == 0) slot = atomicAdd(&ctr->cursor, (unsigned long long)cnt);
+        slot = uni64(slot);
+        if (slot >= matches_cap) rows_full = true;
+        slot += (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+        if (ok && slot < matches_cap) {
+            uint32_t *row = matches + slot * P.nq;
+            for (uint32_t i = 0; i < d; i++) row[P.qv[i]] = S.image[i];
+            row[P.qv[d]] = v;
+        }
+    }
+    sets_found(ctr, limit, lane, cnt, pending, stop);
+}
+
+// the tallies of the kernels that fill a table: per wave in LDS, wave-uniform, the finds below the current image of a position, low
+// and high word.  The conventions of SetsWave hold: every lane writes every word, every read goes through uni().
+struct SetsTally {
+    uint32_t lo[kSetsMaxQ], hi[kSetsMaxQ];
+};
+__device__ __forceinline__ unsigned long long tally_get(const volatile SetsTally &T, uint32_t d)
+{
+    return ((unsigned long long)uni(T.hi[d]) << 32) | uni(T.lo[d]);
+}
+__device__ __forceinline__ void tally_set(volatile SetsTally &T, uint32_t d, unsigned long long x)
+{
+    T.lo[d] = (uint32_t)x;
+    T.hi[d] = (uint32_t)(x >> 32);
+}
+
+// a hook of sets_walk that a kernel does not need: it does nothing, and as a test it passes.  (By value: a reference to the walk's d
+// or to a lane's ok would keep them in memory until the inlining is done, and the code that comes out holds more registers.)
+struct SetsNoHook {
+    template <class... A>
+    __device__ __forceinline__ bool operator()(A...) const
+    {
+        return true;
+    }
+};
+
+// The walk of an item below depth 1, which sets_item_decode (or a kernel's own decode) has entered: per step the next chunk of the
+// current depth's pivot row, its lane test, the leaf at the last depth and the descent into a survivor above it; up when a row is
+// exhausted, done when depth 1 is.  A kernel's own work is four inlined callables:
+//   test(d, v)          for a lane that passed sets_lane_test with candidate v at depth d: false fails it
+//   leaf(d, cb, ok, v)  the chunk [cb, ..) at the last depth d: counts the survivors `ok` (sets_found) and does with them what the
+//                       kernel is for
+//   up(d)               the row of depth d < last is exhausted (the subtree of the last image of d is complete), before d--
+//   down(d, m)          before the descent into the lowest survivor of m at depth d
+// `pending` and `stop` are the kernel's registers, which its leaf passes to sets_found; the walk only reads them.  `last` is the last
+// position, nq - 1, which every kernel holds already.
+template <bool kOrdered, class Test, class Leaf, class Up, class Down, class... Ord>
+__device__ __forceinline__ void sets_walk(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G, const SetsCounters *ctr,
+                                          unsigned long long limit, uint32_t lane, const unsigned long long &pending, const bool &stop, uint32_t last,
+                                          Test &&test, Leaf &&leaf, Up &&up, Down &&down, const Ord &...ord)
+{
+    uint32_t d = 1, steps = 0;
+    while (d >= 1 && !stop) {
+        // a subtree that finds little still hears of the limit: a look at the total every 1024 chunks
+        if ((++steps & 1023u) == 0 && __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + pending >= limit)
+            break;  // EXIT 3
+        unsigned long long m = ((unsigned long long)uni(S.mask_hi[d]) << 32) | uni(S.mask_lo[d]);
+        if (m == 0) {
+            // next chunk of the pivot row
+            const uint32_t cb = uni(S.cbase[d]) + 64u, ce = uni(S.end[d]);
+            if ((int32_t)(ce - cb) <= 0) {
+                if (d < last) up(d);
+                d--;
+                continue;
+            }
+            S.cbase[d] = cb;
+            uint32_t v;
+            const bool ok = sets_lane_test<kOrdered>(P, S, G, d, cb, ce, lane, v, ord...) && test(d, v);
+            if (d == last) {
+                leaf(d, cb, ok, v);
+                continue;
+            }
+            m = __ballot(ok);
+            if (m == 0) continue;
+        }
+        down(d, m);
+        sets_descend<kOrdered>(P, S, G, d, m, lane, ord...);
+    }
+}
+
+// ---- the host's side of the calls ------------------------------------------------------------------------------------------
 // first-level chunks (of 1 << w_shift entries) in every start candidate's row: the scan's input; entry n_cand = 0 so that the
 // scan's last output is the total
 static __global__ void k_sets_cand_chunks(uint32_t n_cand, const uint32_t *__restrict__ cand, const uint32_t *__restrict__ adj_deg,
@@ -382,6 +534,7 @@ struct SetsWork {
     {
     }
 };
+static_assert(sizeof(SetsCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
 
 // a resident grid; a single-vertex query needs no more waves than it has items
 static inline uint32_t sets_grid_blocks(const gnnpe_ctx *c, uint32_t nq, uint32_t n_cand)
@@ -418,6 +571,105 @@ static inline int sets_stage_items(gnnpe_ctx *c, SetsQuery *Q, const uint32_t *b
     if ((rc = tmp.reserve(tb))) return rc;
     GNNPE_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, W.chunks, W.item_off, (int)(n_cand + 1), c->stream));
     return GNNPE_OK;
+}
+
+// the instantiation a query runs: f(), f(Q.O), f(Q.N) or f(Q.O, Q.N), as its pairs and non-edges ask
+template <class F>
+static inline void sets_dispatch(const SetsQuery &Q, F &&f)
+{
+    if (Q.n_non)
+        Q.n_pairs ? f(Q.O, Q.N) : f(Q.N);
+    else
+        Q.n_pairs ? f(Q.O) : f();
+}
+
+// A one-shot call from "arguments checked" to "rc returned": the two events of a timed call, the single wait, the error translation.
+// Between the constructor and finish() the call stages (ev0 is recorded where its uploads end), launches and reads h_pinned; every
+// such step runs only while ok(), and leaves its failure in rc (a code whose message is set) or he (a HIP error, translated at the
+// end).
+struct SetsCall {
+    const char *who;
+    gnnpe_ctx *c;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // null unless the call is timed
+    hipError_t he = hipSuccess;
+    int rc = GNNPE_OK;
+    SetsCall(const char *who_, gnnpe_ctx *c_, bool timed) : who(who_), c(c_)
+    {
+        if (timed) he = hipEventCreate(&ev0);
+        if (he == hipSuccess && timed) he = hipEventCreate(&ev1);
+    }
+    bool ok() const { return he == hipSuccess && !rc; }
+    // the launches of f
+    template <class F>
+    void launch(F &&f)
+    {
+        if (!ok()) return;
+        f();
+        he = hipGetLastError();
+    }
+    // after the last launch: the end of the timed span, the first `bytes` of the counters to h_pinned, and the one wait of the call
+    void wait(const void *ctr, size_t bytes)
+    {
+        if (ok() && ev1) he = hipEventRecord(ev1, c->stream);
+        if (ok()) he = hipMemcpyAsync(c->h_pinned, ctr, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (ok()) he = hipStreamSynchronize(c->stream);
+    }
+    // the device time of a call that succeeded, and the call's return code
+    int finish(double *device_ms)
+    {
+        if (ok() && device_ms) {
+            float ms = 0.f;
+            he = hipEventElapsedTime(&ms, ev0, ev1);
+            *device_ms = ms;
+        }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        (void)hipStreamSynchronize(c->stream);
+        if (!rc && he != hipSuccess) {
+            set_error("%s: %s", who, hipGetErrorString(he));
+            rc = GNNPE_ERR_HIP;
+        }
+        return rc;
+    }
+};
+
+// What the two count calls (vertex table, edge table) do after sets_prepare with a table of `cells` uint64 reserved at d_counts
+// (null if cells == 0).  An empty set or no start candidate: a zeroed table is the whole answer.  Otherwise the table is zeroed on
+// the stream, launch(W, ord...) starts the kernel, and after the wait *complete = total < limit; the table comes back to
+// host_counts only where it is asked for and means something.  With GNNPE_DEBUG staged() prints the call's line after the staging
+// and done(finds, flush_adds) its line after the wait.
+template <class Staged, class Launch, class Done>
+static inline int sets_count_call(const char *who, gnnpe_ctx *c, SetsQuery *Q, const uint32_t *bitmap, uint64_t limit,
+                                  unsigned long long *d_counts, size_t cells, uint64_t *answers, int *complete, uint64_t *host_counts,
+                                  void **dev_counts, double *device_ms, Staged &&staged, Launch &&launch, Done &&done)
+{
+    const size_t table_bytes = cells * 8;
+    if (dev_counts) *dev_counts = d_counts;
+    if (Q->empty) {
+        if (table_bytes) {
+            GNNPE_HIP_TRY(hipMemsetAsync(d_counts, 0, table_bytes, c->stream));
+            GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+            if (host_counts) std::fill(host_counts, host_counts + cells, 0ull);
+        }
+        *complete = 1;
+        return GNNPE_OK;
+    }
+    SetsCall call(who, c, device_ms != nullptr);
+    if (call.ok()) call.rc = sets_stage_items(c, Q, bitmap, c->q_work, c->q_bitmap, c->q_tmp, call.ev0);
+    if (c->sw.debug) staged();
+    if (call.ok() && table_bytes) call.he = hipMemsetAsync(d_counts, 0, table_bytes, c->stream);
+    call.launch([&] {
+        const SetsWork W(c->q_work, Q->n_cand);
+        sets_dispatch(*Q, [&](auto... ord) { launch(W, ord...); });
+    });
+    call.wait(c->q_work.p, 16);
+    if (call.ok()) {
+        *answers = std::min<uint64_t>(c->h_pinned[0], limit);
+        *complete = c->h_pinned[0] < limit ? 1 : 0;
+        if (c->sw.debug) done((unsigned long long)c->h_pinned[0], (unsigned long long)c->h_pinned[1]);
+        if (host_counts && *complete && table_bytes) call.he = hipMemcpy(host_counts, d_counts, table_bytes, hipMemcpyDeviceToHost);
+    }
+    return call.finish(device_ms);
 }
 
 }  // namespace gnnpe

@@ -1,13 +1,14 @@
 // gnnpe_refine_vcount.hip -- PER-VERTEX MATCH COUNTS of the set-restricted refinement: V_m(C) of include/gnnpe_online.h,
 // V[u][v] = the number of maps the mode counts that send query vertex u to data vertex v (nq x n uint64, row-major).
 //
-// The search is k_refine_sets' (gnnpe_refine_sets.hip): the same resident grid, tickets and first-level items, the same loop over
-// the shared steps of gnnpe_refine_sets.hip.h (sets_lane_test, sets_descend, sets_item_decode, the single-vertex item), the same
-// `pending` / total flush every 1024 finds and 1024-chunk poll.  It writes no rows.  What it adds is the table:
+// The search is k_refine_sets' (gnnpe_refine_sets.hip): the same resident grid, tickets and first-level items, and from
+// gnnpe_refine_sets.hip.h the ticket take (sets_limit_reached, sets_take_ticket), the loop over the shared steps (sets_walk), the `pending` / total flush
+// every 1024 finds (sets_found) and the 1024-chunk poll.  It writes no rows.  What is this file's own is the table -- the leaf and
+// flush below, hooked into the walk at the last depth, before d-- and before the descent -- and the entry point:
 //
 //   * adding 1 to the nq cells of every find would cost nq atomics per match.  Instead the wave TALLIES PER DEPTH AND FLUSHES ON
 //     THE WAY UP: tally[d], d = 0 .. nq-2, is the number of finds below the CURRENT image of position d -- wave-uniform, 64-bit,
-//     in an LDS array of this kernel's own (VcountTally: two words per depth; SetsWave is untouched).  The conventions of the
+//     in an LDS array beside SetsWave (SetsTally of the shared header: two words per depth; SetsWave is untouched).  The conventions of the
 //     shared state hold: every lane writes every word, every read goes through uni().
 //   * leaf (depth nq-1, a chunk with survivor ballot m): every surviving lane does one 64-bit atomic add of 1 on
 //     counts[qv[last] * n + its v] -- the addresses of a chunk are different entries of one row -- and tally[last-1] += popcount(m).
@@ -20,37 +21,20 @@
 //   * a wave counts its flushes and adds their number to the second counter word at the end of an item; with GNNPE_DEBUG=1 the
 //     host prints it beside the finds, which is how scripts/online_vertex_counts_measure.py knows the atomics per find.
 //
-// limit is a GUARD, not a cut: a wave that hears of the limit (the three exits marked EXIT below) leaves without flushing its
-// tallies, and the table is unspecified.  *complete = 1 iff |M| < limit, computed on the host from the total.  Why that is
+// limit is a GUARD, not a cut: a wave that hears of the limit (the three exits marked EXIT 1, 2 and 3 in gnnpe_refine_sets.hip.h:
+// sets_limit_reached, sets_found, sets_walk -- the only places where a wave reads the total against the limit, and this kernel's hooks
+// add none) leaves without flushing its tallies, and the table is unspecified.  *complete = 1 iff |M| < limit, computed on the host from the total.  Why that is
 // enough: `total` only ever receives finds, each once, so at every moment total + (any wave's pending) <= |M|.  Exit 1 needs
 // total >= limit, exit 2 needs before + pending >= limit, exit 3 needs total + pending >= limit: with |M| < limit none of the
 // three can be taken, every wave walks every item to its end, every tally is flushed, and the final total is |M| < limit.
 // Conversely a final total >= limit is |M| >= limit (the total never exceeds |M|), and the host says *complete = 0.
+// The host side after sets_prepare is sets_count_call of the shared header, with the edge counts: the table's zeroing, the empty
+// set's zero answer, `complete`, the copy back.
 // Resources of the four instantiations and the measurement: profiles/online_vertex_counts.txt.
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_refine_sets.hip.h"
 
 namespace gnnpe {
-
-struct VcountCounters {  // one 32-byte block, zeroed before every launch; the host reads the first 16 bytes
-    unsigned long long total, flush_adds;  // finds; the adds of flush() -- with the finds (one leaf add each) every atomic on the table
-    uint32_t ticket, pad[3];
-};
-static_assert(sizeof(VcountCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
-
-struct VcountTally {  // per wave in LDS, wave-uniform: finds below the current image of a position, low and high word
-    uint32_t lo[kSetsMaxQ], hi[kSetsMaxQ];
-};
-
-__device__ __forceinline__ unsigned long long tally_get(const volatile VcountTally &T, uint32_t d)
-{
-    return ((unsigned long long)uni(T.hi[d]) << 32) | uni(T.lo[d]);
-}
-__device__ __forceinline__ void tally_set(volatile VcountTally &T, uint32_t d, unsigned long long x)
-{
-    T.lo[d] = (uint32_t)x;
-    T.hi[d] = (uint32_t)(x >> 32);
-}
 
 // One kernel, four instantiations, as k_refine_sets: plain, SetsOrder (distinct), SetsNon (induced), both.
 template <bool kOrdered, class... Ord>
@@ -59,13 +43,13 @@ __global__ __launch_bounds__(kBlock) void k_refine_vcount(SetsPlan P, uint32_t n
                                                          const uint32_t *__restrict__ adj_start,
                                                          const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
                                                          const uint32_t *__restrict__ labels, const uint32_t *__restrict__ bitmap,
-                                                         uint64_t words, unsigned long long limit, VcountCounters *ctr,
+                                                         uint64_t words, unsigned long long limit, SetsCounters *ctr,
                                                          unsigned long long *__restrict__ counts, uint32_t n, Ord... ord)
 {
     __shared__ SetsWave s_wave[kSetsWavesPerBlock];
-    __shared__ VcountTally s_tally[kSetsWavesPerBlock];
+    __shared__ SetsTally s_tally[kSetsWavesPerBlock];
     volatile SetsWave &S = s_wave[threadIdx.x >> 6];
-    volatile VcountTally &T = s_tally[threadIdx.x >> 6];
+    volatile SetsTally &T = s_tally[threadIdx.x >> 6];
     const SetsGraph G = {adj_start, adj_deg, nbrs, labels, bitmap, words};
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nq = P.nq, last = nq - 1;
@@ -73,35 +57,25 @@ __global__ __launch_bounds__(kBlock) void k_refine_vcount(SetsPlan P, uint32_t n
     const uint32_t n_items = nq == 1 ? (n_cand + 63u) / 64u : item_off[n_cand];
 
     for (;;) {
-        if (__hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= limit) return;  // EXIT 1
-        uint32_t q = 0;
-        if (lane == 0) q = atomicAdd(&ctr->ticket, 1u);
-        q = uni(q);
+        if (sets_limit_reached(ctr, limit)) return;
+        const uint32_t q = sets_take_ticket(ctr, lane);
         if (q >= n_items) return;
-
         unsigned long long pending = 0;  // finds not yet added to the total
         bool stop = false;
         uint32_t flushed = 0;  // adds of flush() in this item: one more add per item for the GNNPE_DEBUG line, nothing reads it back
         for (uint32_t d = 0; d < last; d++) tally_set(T, d, 0ull);
 
         // the chunk of survivors at the last depth: one add per survivor on its own cell, their number to the depth above
-        auto leaf = [&](uint32_t d, bool ok, uint32_t v) {
+        auto leaf = [&](uint32_t d, uint32_t, bool ok, uint32_t v) {
             const unsigned long long m = __ballot(ok);
             const uint32_t cnt = (uint32_t)__popcll(m);
             if (cnt == 0) return;
             if (ok) atomicAdd(&counts[(uint64_t)P.qv[d] * n + v], 1ull);
             if (d >= 1) tally_set(T, d - 1, tally_get(T, d - 1) + cnt);
-            pending += cnt;
-            if (pending >= 1024ull) {
-                unsigned long long before = 0;
-                if (lane == 0) before = atomicAdd(&ctr->total, pending);
-                before = uni64(before);
-                stop = before + pending >= limit;  // EXIT 2
-                pending = 0;
-            }
+            sets_found(ctr, limit, lane, cnt, pending, stop);
         };
         // the subtree of position d's current image is complete: its finds to the image's cell and to the depth above
-        auto flush = [&](uint32_t d) {
+        auto flush = [&](uint32_t d, unsigned long long = 0) {
             const unsigned long long t = tally_get(T, d);
             if (t == 0) return;
             if (lane == 0) atomicAdd(&counts[(uint64_t)P.qv[d] * n + uni(S.image[d])], t);
@@ -112,39 +86,13 @@ __global__ __launch_bounds__(kBlock) void k_refine_vcount(SetsPlan P, uint32_t n
 
         if (nq == 1) {
             const uint32_t i = q * 64u + lane, v = sets_single_cand(n_cand, cand, i);
-            leaf(0, sets_single_test(P, G, n_cand, i, v), v);
+            leaf(0, 0, sets_single_test(P, G, n_cand, i, v), v);
         } else if (sets_item_decode(P, S, G, n_cand, cand, item_off, w_shift, q)) {
-            uint32_t d = 1, steps = 0;
-            while (d >= 1 && !stop) {
-                // a subtree that finds little still hears of the limit: a look at the total every 1024 chunks
-                if ((++steps & 1023u) == 0 &&
-                    __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + pending >= limit)
-                    break;  // EXIT 3
-                unsigned long long m = ((unsigned long long)uni(S.mask_hi[d]) << 32) | uni(S.mask_lo[d]);
-                if (m == 0) {
-                    // next chunk of the pivot row
-                    const uint32_t cb = uni(S.cbase[d]) + 64u, ce = uni(S.end[d]);
-                    if ((int32_t)(ce - cb) <= 0) {
-                        if (d < last) flush(d);  // the last sibling of this depth
-                        d--;
-                        continue;
-                    }
-                    S.cbase[d] = cb;
-                    uint32_t v;
-                    const bool ok = sets_lane_test<kOrdered>(P, S, G, d, cb, ce, lane, v, ord...);
-                    if (d == last) {
-                        leaf(d, ok, v);
-                        continue;
-                    }
-                    m = __ballot(ok);
-                    if (m == 0) continue;
-                }
-                flush(d);  // the previous sibling, before the descent overwrites image[d]
-                sets_descend<kOrdered>(P, S, G, d, m, lane, ord...);
-            }
+            // flush: the last sibling of a depth when its row is exhausted; the previous sibling before the descent overwrites image[d]
+            sets_walk<kOrdered>(P, S, G, ctr, limit, lane, pending, stop, last, SetsNoHook{}, leaf, flush, flush, ord...);
             flush(0);
         }
-        if (pending && lane == 0) atomicAdd(&ctr->total, pending);
+        sets_item_end(ctr, lane, pending);
         if (flushed && lane == 0) atomicAdd(&ctr->flush_adds, (unsigned long long)flushed);
         if (stop) return;
     }
@@ -168,65 +116,22 @@ extern "C" int gnnpe_refine_sets_vertex_counts(gnnpe_ctx *c, const char *query_g
     int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q);
     if (rc || limit == 0) return rc;  // limit 0: nothing is launched, and nothing is complete
     const uint32_t nq = Q.nq, n_cand = Q.n_cand, n = c->n;
-    const size_t table_bytes = (size_t)nq * n * 8;
     // context-owned, grow-only: the table beside the work buffer and the bitmap
-    if ((rc = c->q_vcounts.reserve(table_bytes))) return rc;
+    if ((rc = c->q_vcounts.reserve((size_t)nq * n * 8))) return rc;
     unsigned long long *d_counts = c->q_vcounts.as<unsigned long long>();
-    if (dev_counts) *dev_counts = d_counts;
-    if (Q.empty) {  // an empty set, or no start candidate: no map, and that is the whole answer
-        GNNPE_HIP_TRY(hipMemsetAsync(d_counts, 0, table_bytes, c->stream));
-        GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
-        if (host_counts) std::fill(host_counts, host_counts + (size_t)nq * n, 0ull);
-        *complete = 1;
-        return GNNPE_OK;
-    }
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t he = hipSuccess;
-    if (device_ms) he = hipEventCreate(&ev0);
-    if (he == hipSuccess && device_ms) he = hipEventCreate(&ev1);
-    if (he == hipSuccess) rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, ev0);
-    if (c->sw.debug)
-        fprintf(stderr, "[refine_vcount] shift=%u forced=%d cands=%u hubs=%u cus=%d pairs=%u nonedges=%u\n", Q.w_shift, (int)Q.forced,
-                n_cand, c->n_hub, c->num_cus, Q.n_pairs, Q.n_non);
-    if (he == hipSuccess && !rc) he = hipMemsetAsync(d_counts, 0, table_bytes, c->stream);
-    if (he == hipSuccess && !rc) {
-        const SetsWork W(c->q_work, n_cand);
-        auto launch = [&](auto... ord) {
+    return sets_count_call(
+        who, c, &Q, candidate_bitmap, limit, d_counts, (size_t)nq * n, answers, complete, host_counts, dev_counts, device_ms,
+        [&] {
+            fprintf(stderr, "[refine_vcount] shift=%u forced=%d cands=%u hubs=%u cus=%d pairs=%u nonedges=%u\n", Q.w_shift, (int)Q.forced,
+                    n_cand, c->n_hub, c->num_cus, Q.n_pairs, Q.n_non);
+        },
+        [&](const SetsWork &W, auto... ord) {
             hipLaunchKernelGGL((k_refine_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)),
                                dim3(kBlock), 0, c->stream, Q.P, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(),
                                c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
-                               Q.words, (unsigned long long)limit, static_cast<VcountCounters *>(W.ctr), d_counts, n, ord...);
-        };
-        if (Q.n_non)
-            Q.n_pairs ? launch(Q.O, Q.N) : launch(Q.N);
-        else
-            Q.n_pairs ? launch(Q.O) : launch();
-        he = hipGetLastError();
-        if (he == hipSuccess && device_ms) he = hipEventRecord(ev1, c->stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(c->h_pinned, W.ctr, 16, hipMemcpyDeviceToHost, c->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);  // the one wait of the call
-    }
-    if (he == hipSuccess && !rc) {
-        *answers = std::min<uint64_t>(c->h_pinned[0], limit);
-        *complete = c->h_pinned[0] < limit ? 1 : 0;
-        if (c->sw.debug)  // every atomic on the table: one leaf add per find, and the flushes
-            fprintf(stderr, "[refine_vcount] finds=%llu flush_adds=%llu complete=%d\n", (unsigned long long)c->h_pinned[0],
-                    (unsigned long long)c->h_pinned[1], *complete);
-        // the table comes back only where it is asked for and means something
-        if (host_counts && *complete) he = hipMemcpy(host_counts, d_counts, table_bytes, hipMemcpyDeviceToHost);
-    }
-    if (he == hipSuccess && !rc && device_ms) {
-        float ms = 0.f;
-        he = hipEventElapsedTime(&ms, ev0, ev1);
-        *device_ms = ms;
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipStreamSynchronize(c->stream);
-    if (!rc && he != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(he));
-        rc = GNNPE_ERR_HIP;
-    }
-    return rc;
+                               Q.words, (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr), d_counts, n, ord...);
+        },
+        [&](unsigned long long finds, unsigned long long flush_adds) {  // every atomic on the table: one leaf add per find, and the flushes
+            fprintf(stderr, "[refine_vcount] finds=%llu flush_adds=%llu complete=%d\n", finds, flush_adds, *complete);
+        });
 }
