@@ -50,6 +50,10 @@ SIGNATURES = {
     "gnnpe_set_multigraph_rows": (C.c_int, [_vp, C.c_uint32, _u64p, _u32p]),
     "gnnpe_host_read_membership": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     "gnnpe_host_free": (None, [_vp]),
+    "gnnpe_host_csr_apply_edges": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint64, _u32p, _u32p, C.c_uint64,
+                                             _u64p]),
+    "gnnpe_csr_apply_edges": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u64p, _f64p]),
+    "gnnpe_csr_download": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _u64p]),
     "gnnpe_halo_need": (C.c_int, [_vp, C.c_uint32, _u32p, _vp, C.c_uint64, _u64p]),
     "gnnpe_rows_degree": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "gnnpe_rows_pack": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64]),
@@ -124,7 +128,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 15  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 16  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -490,6 +494,26 @@ def host_refine_sets_delta(g, query_path, bitmap, edges, limit=2 ** 64 - 1, dist
     if rc:
         raise GnnpeError(lib.gnnpe_last_error().decode())
     return out.value
+
+
+def host_apply_edges(g, insert=None, delete=None):
+    """gnnpe_host_csr_apply_edges: the graph dict of G' = (E(g) minus delete) plus insert, a compact CSR with g's labels.  The
+    lists hold pairs (x, y), either orientation, repeats tolerated; a loop, an id outside g, an insertion that is an edge, a
+    deletion that is none or an edge in both lists raises GnnpeError."""
+    lib = load()
+    o, nb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32)
+    ins, dele = _delta_pairs([] if insert is None else insert), _delta_pairs([] if delete is None else delete)
+    n = len(o) - 1
+    cap = len(nb) + 2 * len(ins)
+    out_o, out_nb, after = np.zeros(n + 1, np.uint32), np.zeros(cap, np.uint32), C.c_uint64()
+    rc = lib.gnnpe_host_csr_apply_edges(n, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(ins, _u32p) if len(ins) else None, len(ins),
+                                        _ptr(dele, _u32p) if len(dele) else None, len(dele), _ptr(out_o, _u32p),
+                                        _ptr(out_nb, _u32p), cap, C.byref(after))
+    if rc:
+        raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
+    out = dict(g)
+    out["offsets"], out["nbrs"] = out_o, out_nb[:after.value].copy()
+    return out
 
 
 def host_query_symmetry(query_path, pairs_cap=None):
@@ -1111,6 +1135,29 @@ class Engine:
         r, e, h = C.c_uint64(), C.c_uint64(), C.c_uint32()
         self._ck(self.lib.gnnpe_rows_held(self.ctx, C.byref(r), C.byref(e), C.byref(h)))
         return r.value, e.value, h.value
+
+    def apply_edges(self, insert=None, delete=None, timing=False):
+        """gnnpe_csr_apply_edges: the batch of edge insertions and deletions (pairs (x, y), either orientation, repeats tolerated)
+        applied to the whole graph on the device; afterwards the context is as load_csr of the new graph's compact CSR leaves
+        it.  Returns its entry count, (entries, device ms) with timing=True.  A refused batch raises GnnpeError and changes
+        nothing; an empty batch does nothing."""
+        ins, dele = _delta_pairs([] if insert is None else insert), _delta_pairs([] if delete is None else delete)
+        after, ms = C.c_uint64(), C.c_double()
+        self._ck(self.lib.gnnpe_csr_apply_edges(self.ctx, _ptr(ins, _u32p) if len(ins) else None, len(ins),
+                                                _ptr(dele, _u32p) if len(dele) else None, len(dele), C.byref(after),
+                                                C.byref(ms) if timing else None))
+        if len(ins) or len(dele):
+            self._rows_gen += 1  # device views of the count tables are stale
+            self.slab = (0, self.n)
+        self.entries = after.value
+        return (after.value, ms.value) if timing else after.value
+
+    def download_csr(self):
+        """gnnpe_csr_download: (offsets, nbrs) of the whole graph the context holds, the arrays the edge-count tables index"""
+        offsets, cnt = np.zeros(self.n + 1, np.uint32), C.c_uint64()
+        nbrs = np.zeros(self.rows_held()[1], np.uint32)
+        self._ck(self.lib.gnnpe_csr_download(self.ctx, _ptr(offsets, _u32p), _ptr(nbrs, _u32p), len(nbrs), C.byref(cnt)))
+        return offsets, nbrs[:cnt.value]
 
     def rows_drop_halo(self):
         self._ck(self.lib.gnnpe_rows_drop_halo(self.ctx))

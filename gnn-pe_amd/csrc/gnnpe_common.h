@@ -150,6 +150,9 @@ struct gnnpe_ctx {
     // counts the calls that load or change the rows (gnnpe_load_csr, gnnpe_load_rows, gnnpe_set_multigraph_rows, gnnpe_rows_append,
     // gnnpe_rows_drop_halo): what was opened on an earlier graph -- a match cursor, gnnpe_refine_pages_open -- refuses to go on
     uint64_t graph_gen = 0;
+    // gnnpe_csr_apply_edges (gnnpe_update.hip): the spare adj_start / adj_deg / nbrs the new graph is built in before they are
+    // swapped with the live ones (ping-pong, grow-only), and the batch's keys, ranks and touched rows
+    gnnpe::DevBuf upd_start, upd_deg, upd_nbrs, upd_work;
     // rows longer than 64 entries ("hub" rows of the l=2 enumeration): ids and adjacency ranges; graph-only, rebuilt
     // whenever rows are loaded / appended / dropped
     gnnpe::DevBuf hub_rows, hub_beg, hub_end;
@@ -311,3 +314,8 @@ struct gnnpe_ctx {
 void gnnpe_forget_emit_pref(gnnpe_ctx *c, const void *lo, size_t bytes);
 // per-pair output offsets of the current count, built on demand (gnnpe_engine.hip; internal, not part of the ABI header)
 extern "C" int gnnpe_ensure_eoff(gnnpe_ctx *c);
+// the loaders' shared tail (gnnpe_engine.hip), for gnnpe_csr_apply_edges (gnnpe_update.hip); not exported from the library.
+// finish_rows: validation, reverse positions and the hub list of the rows [first held row .., + n_new); synchronises the stream.
+// invalidate_derived: everything computed from the rows is stale.
+extern "C" __attribute__((visibility("hidden"))) int finish_rows(gnnpe_ctx *c, uint64_t n_new, const uint32_t *dev_new_rows);
+extern "C" __attribute__((visibility("hidden"))) void invalidate_derived(gnnpe_ctx *c);

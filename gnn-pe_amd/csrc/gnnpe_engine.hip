@@ -355,7 +355,7 @@ static int alloc_vertex_arrays(gnnpe_ctx *c, uint32_t n)
     return GNNPE_OK;
 }
 
-static void invalidate_derived(gnnpe_ctx *c)
+void invalidate_derived(gnnpe_ctx *c)
 {
     c->halo_min_rank = 0;  // called by the loaders only: a freshly loaded graph has no halo rows
     c->multigraph = false;
@@ -372,7 +372,7 @@ static void invalidate_derived(gnnpe_ctx *c)
 
 // Validation and the graph-only derived structure of the rows [first held row .., +n_new): reverse
 // positions and the hub-row list.  Synchronises the stream.
-static int finish_rows(gnnpe_ctx *c, uint64_t n_new, const uint32_t *dev_new_rows)
+int finish_rows(gnnpe_ctx *c, uint64_t n_new, const uint32_t *dev_new_rows)
 {
     int rc;
     if ((rc = c->small.reserve(1024))) return rc;

@@ -52,6 +52,9 @@ struct Options {
     // --delta-edges FILE (needs --refine sets; with --matches but not --all-matches, not with the count tables): one data edge
     // `x y` per line; the answer is the matches through at least one of them, each once (gnnpe_refine_sets_delta)
     std::string delta_edges_file;
+    // --apply-edges FILE (exact -m online / -m filter only): lines `+ x y` / `- x y`, a batch of edge insertions and deletions
+    // applied to the loaded data graph on the device before anything is computed from it (gnnpe_csr_apply_edges)
+    std::string apply_edges_file;
     bool induced = false;   // --induced (needs --refine sets): induced matching, query non-edges on data non-edges (GNNPE_MATCH_INDUCED)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
@@ -130,7 +133,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
-                   "           [--vertex-counts FILE | --edge-counts FILE | --delta-edges FILE]\n"
+                   "           [--vertex-counts FILE | --edge-counts FILE | --delta-edges FILE] [--apply-edges FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -143,7 +146,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       send a_k to x and b_k to y.  -n is a guard as for --vertex-counts;\n"
                    "       --delta-edges FILE (needs --refine sets; combines with --distinct, --induced and --matches, not with\n"
                    "       --all-matches or the count tables): FILE has one data edge `x y` per line; the answer is the number of matches\n"
-                   "       that put a query edge on at least one of them, each match once, and --matches writes those\n",
+                   "       that put a query edge on at least one of them, each match once, and --matches writes those;\n"
+                   "       --apply-edges FILE (exact mode only: --exact or -l 3): FILE has one line `+ x y` (insert the edge) or `- x y`\n"
+                   "       (delete it) per edge; the batch is applied to the data graph on the device and the query runs on the result:\n"
+                   "       the metadata block and the rows of --edge-counts / --vertex-counts are the updated graph's\n",
                    tool, tool);
             exit(0);
         }
@@ -160,12 +166,14 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             o.transport_explicit = true;
             continue;
         }
-        if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges") {
+        if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges" ||
+            a == "--apply-edges") {
             if (i + 1 >= argc) die(a + " needs a value");
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }
             if (a == "--vertex-counts") { o.vertex_counts_file = argv[++i]; continue; }
             if (a == "--edge-counts") { o.edge_counts_file = argv[++i]; continue; }
             if (a == "--delta-edges") { o.delta_edges_file = argv[++i]; continue; }
+            if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; continue; }
             o.refine = argv[++i];
             if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;

@@ -1,0 +1,87 @@
+// graph_update.cpp -- gnnpe_host_csr_apply_edges: sort and de-duplicate the directed keys of the two lists, check them against
+// the rows, merge row by row.  Plain C++; shares nothing with csrc/gnnpe_update.hip.
+#include "graph_update.h"
+
+#include <algorithm>
+
+namespace gnnpe_host {
+
+int update_edge_keys(uint32_t n, const uint32_t *edges, uint64_t n_edges, const char *what, std::vector<uint64_t> *keys, std::string *err)
+{
+    keys->clear();
+    keys->reserve(2 * n_edges);
+    for (uint64_t i = 0; i < n_edges; i++) {
+        const uint32_t x = edges[2 * i], y = edges[2 * i + 1];
+        if (x == y || x >= n || y >= n) {
+            *err = std::string(what) + " (" + std::to_string(x) + ", " + std::to_string(y) + ")" +
+                   (x == y ? " is a loop" : " names a vertex the graph does not have (n = " + std::to_string(n) + ")");
+            return -1;
+        }
+        keys->push_back(((uint64_t)x << 32) | y);
+        keys->push_back(((uint64_t)y << 32) | x);
+    }
+    std::sort(keys->begin(), keys->end());
+    keys->erase(std::unique(keys->begin(), keys->end()), keys->end());
+    return 0;
+}
+
+static std::string pair_text(uint64_t key) { return "(" + std::to_string((uint32_t)(key >> 32)) + ", " + std::to_string((uint32_t)key) + ")"; }
+
+int csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *insert_edges, uint64_t n_insert,
+                    const uint32_t *delete_edges, uint64_t n_delete, std::vector<uint32_t> *out_offsets, std::vector<uint32_t> *out_nbrs,
+                    std::string *err)
+{
+    std::vector<uint64_t> ins, del;
+    if (update_edge_keys(n, insert_edges, n_insert, "insertion", &ins, err) != 0) return -1;
+    if (update_edge_keys(n, delete_edges, n_delete, "deletion", &del, err) != 0) return -1;
+    auto is_edge = [&](uint64_t key) {
+        const uint32_t x = (uint32_t)(key >> 32), y = (uint32_t)key;
+        return std::binary_search(nbrs + offsets[x], nbrs + offsets[x + 1], y);
+    };
+    for (uint64_t k : ins) {
+        if (std::binary_search(del.begin(), del.end(), k)) {
+            *err = "edge " + pair_text(k) + " is in both lists";
+            return -1;
+        }
+        if (is_edge(k)) {
+            *err = "insertion " + pair_text(k) + " is already an edge of the graph";
+            return -1;
+        }
+    }
+    for (uint64_t k : del)
+        if (!is_edge(k)) {
+            *err = "deletion " + pair_text(k) + " is not an edge of the graph";
+            return -1;
+        }
+    const uint64_t after = (uint64_t)offsets[n] + ins.size() - del.size();
+    if (after + n >= (1ull << 32)) {
+        *err = std::to_string(after) + " entries + " + std::to_string(n) + " vertices exceed 32-bit addressing";
+        return -5;
+    }
+    out_offsets->assign((size_t)n + 1, 0);
+    out_nbrs->clear();
+    out_nbrs->reserve(after);
+    size_t pi = 0, pd = 0;
+    for (uint32_t x = 0; x < n; x++) {
+        (*out_offsets)[x] = (uint32_t)out_nbrs->size();
+        uint32_t j = offsets[x];
+        const uint32_t end = offsets[x + 1];
+        // the old row and the row's insert keys, both ascending, merged; an old entry that is the next delete key is skipped
+        for (;;) {
+            const bool have_ins = pi < ins.size() && (uint32_t)(ins[pi] >> 32) == x;
+            if (j < end && (!have_ins || nbrs[j] < (uint32_t)ins[pi])) {
+                if (pd < del.size() && del[pd] == (((uint64_t)x << 32) | nbrs[j])) pd++;
+                else out_nbrs->push_back(nbrs[j]);
+                j++;
+            } else if (have_ins) {
+                out_nbrs->push_back((uint32_t)ins[pi++]);
+            } else {
+                break;
+            }
+        }
+    }
+    (*out_offsets)[n] = (uint32_t)out_nbrs->size();
+    return 0;
+}
+
+}  // namespace gnnpe_host

@@ -1,0 +1,20 @@
+// graph_update.h -- a batch of undirected edge insertions and deletions applied to a CSR on the host: the host form of
+// gnnpe_csr_apply_edges (include/gnnpe_hip.h, ABI 16), the yardstick of the device form and the host mirror of a caller.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace gnnpe_host {
+
+// The two directed keys (x << 32) | y of every pair, ascending, each once.  -1 and *err for x == y or an id >= n.
+int update_edge_keys(uint32_t n, const uint32_t *edges, uint64_t n_edges, const char *what, std::vector<uint64_t> *keys, std::string *err);
+
+// G' = (E(G) minus D) plus I as a compact CSR.  0, or -1 (refusal: *err names one offending pair) / -5 (entries' + n >= 2^32);
+// nothing is written on a refusal.
+int csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *insert_edges, uint64_t n_insert,
+                    const uint32_t *delete_edges, uint64_t n_delete, std::vector<uint32_t> *out_offsets, std::vector<uint32_t> *out_nbrs,
+                    std::string *err);
+
+}  // namespace gnnpe_host

@@ -15,6 +15,7 @@
 
 #include "../../include/gnnpe_hip.h"
 #include "graph_loader.h"
+#include "graph_update.h"
 #include "query_plan.h"
 
 namespace gnnpe {
@@ -499,6 +500,33 @@ int gnnpe_host_load_aux_index(const char *path, uint32_t *n_nodes, uint32_t *L_o
     *degrees = d;
     *label_mbr = m;
     return 0;
+}
+
+int gnnpe_host_csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *insert_edges, uint64_t n_insert,
+                               const uint32_t *delete_edges, uint64_t n_delete, uint32_t *out_offsets, uint32_t *out_nbrs,
+                               uint64_t out_cap, uint64_t *n_entries_after)
+{
+    if (!offsets || (!nbrs && offsets[n]) || (!insert_edges && n_insert) || (!delete_edges && n_delete) || !out_offsets ||
+        !n_entries_after || (!out_nbrs && out_cap)) {
+        gnnpe::set_error("gnnpe_host_csr_apply_edges: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    *n_entries_after = 0;
+    std::vector<uint32_t> off, nb;
+    std::string err;
+    const int rc = gnnpe_host::csr_apply_edges(n, offsets, nbrs, insert_edges, n_insert, delete_edges, n_delete, &off, &nb, &err);
+    if (rc != 0) {
+        gnnpe::set_error("gnnpe_host_csr_apply_edges: %s", err.c_str());
+        return rc == -5 ? GNNPE_ERR_RANGE : GNNPE_ERR_ARG;
+    }
+    *n_entries_after = nb.size();
+    if (nb.size() > out_cap) {
+        gnnpe::set_error("gnnpe_host_csr_apply_edges: %zu entries, room for %llu", nb.size(), (unsigned long long)out_cap);
+        return GNNPE_ERR_ARG;
+    }
+    memcpy(out_offsets, off.data(), off.size() * 4);
+    if (!nb.empty()) memcpy(out_nbrs, nb.data(), nb.size() * 4);
+    return GNNPE_OK;
 }
 
 }  // extern "C"

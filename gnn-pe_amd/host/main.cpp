@@ -186,7 +186,10 @@ int run_filter(const Options &o)
     if (rc != 0) die(o.data_graph + ": " + err);
     if (exact && o.mode == "online" && !g.simple)  // the refinement counts embeddings in simple graphs only (gnnpe_refine)
         die(o.data_graph + " repeats an edge (duplicate `e` lines): exact -m online (--exact, -l 3) needs a simple graph");
-    fputs(g.metadata_text().c_str(), stdout);
+    // with --apply-edges the metadata block and the plan size are printed once the batch is applied: they describe the graph
+    // the answer is for
+    const bool updating = !o.apply_edges_file.empty();
+    if (!updating) fputs(g.metadata_text().c_str(), stdout);
     std::vector<uint32_t> sorted_nodes, membership;
     if (gnnpe_host::read_membership(o.dataset_path + "gnn-pe/membership.txt", g.n, o.partition_num, &sorted_nodes,
                                     &membership, &err) != 0)
@@ -204,7 +207,7 @@ int run_filter(const Options &o)
         exit(-1);
     }
     if (rc != 0) die(o.query_graph + ": " + gnnpe_last_error());
-    printf("%u\n", n_qp);  // gen_query_pde prints the plan size (custom.h:629)
+    if (!updating) printf("%u\n", n_qp);  // gen_query_pde prints the plan size (custom.h:629)
     if (gnnpe_device_count() <= 0) die("no HIP device: this tool has no CPU fallback");
     gnnpe_ctx *ctx = gnnpe_create(0);
     if (!ctx) die(std::string("gnnpe_create: ") + gnnpe_last_error());
@@ -212,6 +215,31 @@ int run_filter(const Options &o)
     std::vector<double> table((size_t)n_labels * o.vde_dim);
     check(gnnpe_host_label_table(n_labels, o.vde_dim, table.data()), "label table");
     check(load_graph_into(ctx, g), "load_csr");
+    if (updating) {  // the whole query runs on the updated graph
+        std::vector<uint32_t> ins, del;
+        FILE *af = fopen(o.apply_edges_file.c_str(), "r");
+        if (!af) die("cannot read " + o.apply_edges_file);
+        char sign = 0;
+        unsigned long long x = 0, y = 0;
+        for (int got; (got = fscanf(af, " %c %llu %llu", &sign, &x, &y)) != EOF;) {
+            if (got != 3 || (sign != '+' && sign != '-') || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull)
+                die(o.apply_edges_file + ": one `+ x y` or `- x y` per line expected");
+            std::vector<uint32_t> &to = sign == '+' ? ins : del;
+            to.push_back((uint32_t)x);
+            to.push_back((uint32_t)y);
+        }
+        fclose(af);
+        uint64_t entries = 0;
+        check(gnnpe_csr_apply_edges(ctx, ins.data(), ins.size() / 2, del.data(), del.size() / 2, &entries, nullptr), "--apply-edges");
+        // the host copy follows the device: the count tables below are indexed by the entries of the CSR the context holds
+        g.neighbors.assign(entries, 0);
+        check(gnnpe_csr_download(ctx, g.offsets.data(), g.neighbors.data(), entries, &entries), "csr_download");
+        g.m = (uint32_t)(entries / 2);
+        g.max_degree = 0;
+        for (uint32_t v = 0; v < g.n; v++) g.max_degree = std::max(g.max_degree, g.offsets[v + 1] - g.offsets[v]);
+        fputs(g.metadata_text().c_str(), stdout);
+        printf("%u\n", n_qp);
+    }
     check(gnnpe_set_order(ctx, sorted_nodes.data(), membership.data(), o.partition_num), "set_order");
     check(gnnpe_set_label_table(ctx, n_labels, o.vde_dim, table.data()), "set_label_table");
     check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
@@ -493,6 +521,10 @@ int main(int argc, char **argv)
     if (!o.delta_edges_file.empty() && (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty()))
         die("--delta-edges excludes --all-matches, --vertex-counts and --edge-counts");
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
+    // exact -m online / -m filter read nothing that was derived from the old graph (only the data graph and membership.txt)
+    if (!o.apply_edges_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
+        die("--apply-edges applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
+            "made from the graph as it was");
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "
             "embeddings, and only the start vertex's set may restrict the search there)");

@@ -178,6 +178,7 @@ int main(int argc, char **argv)
     // GNN-PGE/include/custom.h:47-49: path_length = 1 + 1 (vertices per path), pde_dim = vde_dim * path_length
     if (o.path_length != 2) die("-l " + std::to_string(o.path_length) + ": only the reference default (2) is supported");
     if (o.partition_num == 0) die("-p must be >= 1");
+    if (!o.apply_edges_file.empty()) die("--apply-edges is an option of gnnpe_main's exact -m online / -m filter");
     if (o.mode == "online" || o.mode == "filter") return run_online(o);
     if (o.mode != "offline") return 0;
 

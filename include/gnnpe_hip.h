@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GNNPE_ABI_VERSION 15
+#define GNNPE_ABI_VERSION 16
 
 #define GNNPE_OK 0
 #define GNNPE_ERR_ARG (-1)     /* bad argument / call order */
@@ -128,6 +128,63 @@ int gnnpe_host_load_multigraph(const char *path, uint32_t *n, uint32_t *m, uint3
 /* membership.txt (main.cpp:77-85): sorted_nodes[n], membership[n] caller-allocated; p = partition_num. */
 int gnnpe_host_read_membership(const char *path, uint32_t n, uint32_t p, uint32_t *sorted_nodes, uint32_t *membership);
 void gnnpe_host_free(void *ptr);
+
+/* ---- ABI version 16: edge insertions and deletions applied to the resident graph -------------------------------------------
+ * gnnpe_load_csr is the only other way to change the graph a context holds: the caller rebuilds the whole CSR and uploads all of
+ * it for a handful of edges.  These calls apply a BATCH of undirected edge insertions I and deletions D to the whole graph the
+ * context holds, on the device, from the few kilobytes that describe the batch.  It is the middle step of the loop that
+ * gnnpe_refine_sets_delta (include/gnnpe_online.h, ABI 15) exists for: delta over D on G, apply, delta over I on G'.
+ *
+ * Edge lists.  insert_edges / delete_edges: k x 2 uint32 pairs (x, y), either orientation.  A repeat, or both orientations of one
+ * edge, inside one list means the edge once (as gnnpe_refine_sets_delta takes F).  Either list may be NULL where its count is 0.
+ *
+ * Result.  G' = (E(G) minus D) plus I on the same n vertices with the same labels, as a COMPACT CSR: row x starts at the sum of
+ * the new degrees below x, the rows lie back to back, each strictly ascending.  The layout is determined by G' alone, so the
+ * entry indices j of gnnpe_refine_sets_edge_counts after the call index exactly the arrays the host form and gnnpe_csr_download
+ * return.
+ *
+ * State after a successful device call: precisely what gnnpe_load_csr(ctx, n, offsets', nbrs', labels) leaves, offsets' / nbrs'
+ * being the compact CSR of G'.  The graph generation moves on, so open match cursors (gnnpe_refine_pages_*) refuse to go on; the
+ * reverse positions, the hub-row list and the neighbours' labels are rebuilt; order, slab, label-table results, counts and
+ * everything else derived from the rows are reset as the loader resets them; the device tables of
+ * gnnpe_refine_sets_vertex_counts / _edge_counts are no longer valid (their "rows loaded or changed").
+ *
+ * Refusals.  Each leaves the context exactly as it was -- the same graph, the same generation (open cursors go on working),
+ * derived state kept: the new arrays are built in spare buffers and swapped in only on success.
+ *   - GNNPE_ERR_ARG, on the host before anything is launched: x == y, or an id >= n.
+ *   - GNNPE_ERR_ARG, found on the device and reported through one counter block in the call's single wait: an insertion that is
+ *     already an edge of G, a deletion that is not, one edge in both lists (any orientations).  The message names one offending
+ *     pair, the same one on every run.
+ *   - GNNPE_ERR_UNSUPPORTED: no whole graph on the device (nothing loaded, or gnnpe_load_rows), or the multigraph state.
+ *   - GNNPE_ERR_RANGE: entries' + n >= 2^32, the bound the 32-bit offsets and the refinement's items already live under.
+ *   - an allocation the device refuses before the swap (the spare arrays, the batch's work area, a larger revpos / label array)
+ *     returns its error and leaves the context usable and unchanged.  The rebuild after the swap is gnnpe_load_csr's own tail and
+ *     fails as that does: if the device refuses the few words of the hub list or of the sort's temporary storage there, the context
+ *     is left without a graph, as after a failed gnnpe_load_csr, and takes the next gnnpe_load_csr.
+ * n_insert == n_delete == 0 succeeds, launches nothing and changes nothing: the generation stays, cursors stay valid.
+ *
+ * gnnpe_host_csr_apply_edges: the host form (host/graph_update.cpp): sort and de-duplicate the keys, merge row by row.  The same
+ *   semantics and refusals (no context, so no UNSUPPORTED); nothing is written on a refusal.  out_offsets: n + 1 words; out_nbrs:
+ *   out_cap words -- too few returns GNNPE_ERR_ARG with *n_entries_after set (entries + 2 n_insert always suffices).  It shares
+ *   no code with the device form: it is its yardstick, and the host mirror of a caller (the host forms of the refinements take the
+ *   CSR, and the edge-count tables are indexed by its entries).
+ * gnnpe_csr_apply_edges: the device form (csrc/gnnpe_update.hip).  *n_entries_after (may be NULL) = offsets'[n]; on a refusal it
+ *   holds the unchanged graph's entries.  *device_ms (may be NULL) covers everything between the upload of the keys and the end of
+ *   the rebuild of the derived structure, not the uploads.  Transient memory: a second neighbour array (and second start / degree
+ *   arrays), kept as the next call's spare (ping-pong, grow-only).
+ * gnnpe_csr_download: the CSR the context holds, back on the host -- for a caller without a host mirror, the arrays the edge tables
+ *   index.  Whole graph only (GNNPE_ERR_UNSUPPORTED otherwise).  host_offsets: n + 1 words; nbrs_cap too small returns
+ *   GNNPE_ERR_ARG with *n_entries set. */
+int gnnpe_host_csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
+                               const uint32_t *insert_edges, uint64_t n_insert,
+                               const uint32_t *delete_edges, uint64_t n_delete,
+                               uint32_t *out_offsets, uint32_t *out_nbrs, uint64_t out_cap,
+                               uint64_t *n_entries_after);
+int gnnpe_csr_apply_edges(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint64_t n_insert,
+                          const uint32_t *delete_edges, uint64_t n_delete,
+                          uint64_t *n_entries_after, double *device_ms);
+int gnnpe_csr_download(gnnpe_ctx *ctx, uint32_t *host_offsets, uint32_t *host_nbrs,
+                       uint64_t nbrs_cap, uint64_t *n_entries);
 
 /* ---- halo exchange helpers (device side of the RCCL all-to-all-v) ----------------- */
 /* List the vertices whose adjacency rows this context needs but does not hold -- every vertex referenced by

@@ -265,7 +265,8 @@ int gnnpe_refine_sets_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, 
 
 /* ---- ABI version 15: the matches through a given set of data edges, each once ----------------------------------------------
  * "Which matches use one of these data edges?" is the primitive of incremental (continuous) subgraph matching:
- *   - edges were added to G: load the new graph and ask for the matches through the added edges -- exactly the new matches;
+ *   - edges were added to G: load the new graph (gnnpe_csr_apply_edges of include/gnnpe_hip.h changes the resident one in place)
+ *     and ask for the matches through the added edges -- exactly the new matches;
  *   - edges are about to be removed: ask on the current graph for the matches through them -- exactly the ones that vanish.
  * Re-running the query pays for |M| where it needs the difference; pinning endpoints through the bitmap takes 2 nqe calls per
  * edge and reports a match through several of the edges several times; E_m(C) has the counts per edge, which do not add up to a
