@@ -128,7 +128,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 16  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 17  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -170,6 +170,14 @@ ONLINE_SIGNATURES = {
                                                C.c_uint32, _u64p]),
     "gnnpe_refine_sets_delta": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p, C.c_uint64,
                                           _f64p]),
+    "gnnpe_host_refine_sets_delta_vertex_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p, C.c_uint64,
+                                                             C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p]),
+    "gnnpe_host_refine_sets_delta_edge_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p, C.c_uint64,
+                                                           C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p]),
+    "gnnpe_refine_sets_delta_vertex_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
+                                                        C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
+    "gnnpe_refine_sets_delta_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
+                                                      C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
 }
 _online = None
 
@@ -496,6 +504,37 @@ def host_refine_sets_delta(g, query_path, bitmap, edges, limit=2 ** 64 - 1, dist
     return out.value
 
 
+def _host_delta_table(fn_name, shape, g, query_path, bitmap, edges, limit, distinct, induced):
+    lib = load()
+    out, done = C.c_uint64(), C.c_int()
+    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
+    counts = np.zeros(shape, np.uint64)
+    rc = getattr(load_online(), fn_name)(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
+                                         _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
+                                         match_mode(distinct, induced), C.byref(out), C.byref(done), _ptr(counts, _u64p))
+    if rc:
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return out.value, bool(done.value), counts
+
+
+def host_refine_sets_delta_vertex_counts(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """The per-vertex table of the matches through a set of data edges on the host (include/gnnpe_online.h, ABI 17): (answers,
+    complete, counts) as host_refine_sets_vertex_counts, over the matches host_refine_sets_delta counts only; answers =
+    min(Delta, limit), complete = Delta < limit.  `edges` as for host_refine_sets_delta."""
+    bm = _np(bitmap, np.uint32)
+    n = len(g["offsets"]) - 1
+    return _host_delta_table("gnnpe_host_refine_sets_delta_vertex_counts", (_bitmap_rows(bm, n), n), g, query_path, bm, edges, limit,
+                             distinct, induced)
+
+
+def host_refine_sets_delta_edge_counts(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """The per-edge table of the matches through a set of data edges on the host (include/gnnpe_online.h, ABI 17): (answers,
+    complete, counts) as host_refine_sets_edge_counts, over the matches host_refine_sets_delta counts only."""
+    shape = (len(host_query_edges(query_path)), int(np.asarray(g["offsets"])[-1]))
+    return _host_delta_table("gnnpe_host_refine_sets_delta_edge_counts", shape, g, query_path, bitmap, edges, limit, distinct, induced)
+
+
 def host_apply_edges(g, insert=None, delete=None):
     """gnnpe_host_csr_apply_edges: the graph dict of G' = (E(g) minus delete) plus insert, a compact CSR with g's labels.  The
     lists hold pairs (x, y), either orientation, repeats tolerated; a loop, an id outside g, an insertion that is an edge, a
@@ -759,6 +798,7 @@ class Engine:
         self.e = 0
         self.entries = 0  # adjacency entries of the CSR given to load_csr: the width of the edge-count tables
         self._rows_gen = self._ecounts_call = 0  # what an edge-count device view is valid for
+        self._delta_counts_call = {"vertex": 0, "edge": 0}  # ... and a view of a delta table
         self.slab = (0, 0)
         self.total = None
         self._pools = []
@@ -1047,6 +1087,56 @@ class Engine:
                                                        len(e), int(limit), match_mode(distinct, induced), C.byref(out),
                                                        _ptr(rows, _u32p) if cap else None, cap, C.byref(ms)))
         return out.value, rows[:min(out.value, cap)], ms.value
+
+    def _refine_sets_delta_counts(self, kind, shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign):
+        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
+        bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
+        counts = None if device or accum is not None else np.zeros(shape, np.uint64)
+        if accum is None:
+            self._delta_counts_call[kind] += 1
+        fn = getattr(load_online(), f"gnnpe_refine_sets_delta_{kind}_counts")
+        self._ck(fn(self.ctx, query_path.encode(), _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
+                    match_mode(distinct, induced), C.byref(out), C.byref(done), _ptr(counts, _u64p), C.byref(ptr),
+                    None if accum is None else C.c_void_p(int(accum)), int(sign), C.byref(ms)))
+        if counts is None:
+            counts = _DevArray(int(ptr.value or 0), shape, "<i8", owner=self)
+            if accum is None:
+                counts.valid_for = (kind, self._rows_gen, self._delta_counts_call[kind])
+        return out.value, bool(done.value), counts, ms.value
+
+    def refine_sets_delta_vertex_counts(self, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False, device=False,
+                                        accum=None, sign=1):
+        """The per-vertex table of the matches through a set of data edges on the device (gnnpe_refine_sets_delta_vertex_counts):
+        (answers, complete, counts, device ms) as refine_sets_vertex_counts, over the matches refine_sets_delta counts only.
+        device=True: counts is a view of the context's own table for this call, valid until the next such call or until the rows
+        are loaded or changed (apply_edges); delta_counts_to_host(counts) copies it back.  accum: a device pointer (an int, a
+        tensor's data_ptr()) to the caller's (nq, n) uint64 table on the context's device: nothing is zeroed, every cell gets
+        sign * its count added (sign +1 or -1, mod 2^64), counts is a view of the caller's memory, and a refused call leaves it
+        untouched.  Pass the default limit when accumulating."""
+        bm = _np(bitmap, np.uint32)
+        return self._refine_sets_delta_counts("vertex", (_bitmap_rows(bm, self.n), self.n), query_path, bm, edges, limit, distinct,
+                                              induced, device, accum, sign)
+
+    def refine_sets_delta_edge_counts(self, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False, device=False,
+                                      accum=None, sign=1):
+        """The per-edge table of the matches through a set of data edges on the device (gnnpe_refine_sets_delta_edge_counts):
+        (answers, complete, counts, device ms) as refine_sets_edge_counts, over the matches refine_sets_delta counts only; the
+        columns are the adjacency entries of the graph the context holds now.  device, accum and sign as for
+        refine_sets_delta_vertex_counts, the caller's table being (nqe, entries) uint64."""
+        shape = (len(host_query_edges(query_path)), self.entries)
+        return self._refine_sets_delta_counts("edge", shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign)
+
+    def delta_counts_to_host(self, view):
+        """the context's own device table a refine_sets_delta_vertex_counts / _edge_counts(..., device=True) call returned, copied
+        to the host as uint64; a view from before the latest such call or from before the rows were loaded or changed is refused"""
+        kind = (getattr(view, "valid_for", None) or (None,))[0]
+        if getattr(view, "owner", None) is not self or kind not in self._delta_counts_call or \
+                view.valid_for != (kind, self._rows_gen, self._delta_counts_call[kind]):
+            raise GnnpeError("stale delta-count view: the table was replaced by a later call or the graph was loaded or changed")
+        nbytes = view.shape[0] * view.shape[1] * 8
+        if nbytes == 0:
+            return np.zeros(view.shape, np.uint64)
+        return self.copy_to_host(view.__cuda_array_interface__["data"][0], nbytes).view(np.uint64).reshape(view.shape)
 
     def edge_counts_to_host(self, view):
         """the device table a refine_sets_edge_counts(..., device=True) call returned, copied to the host as uint64; a view from

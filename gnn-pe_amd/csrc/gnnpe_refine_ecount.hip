@@ -29,53 +29,13 @@
 //
 // limit is a GUARD exactly as in k_refine_vcount: a wave that hears of the limit leaves without flushing, the table is then
 // unspecified, and *complete = 1 iff |M| < limit (the argument is written out in gnnpe_refine_vcount.hip).
+// EcountEdges, EcountWave, the entry searches and the adds of the leaf and of a flush are in gnnpe_refine_ecount.hip.h, which
+// k_refine_delta_ecount (gnnpe_refine_delta_counts.hip) includes as well.
 // Resources of the four instantiations and the measurement: profiles/online_edge_counts.txt.
 #include "../../include/gnnpe_online.h"
-#include "gnnpe_records.h"
-#include "gnnpe_refine_sets.hip.h"
+#include "gnnpe_refine_ecount.hip.h"
 
 namespace gnnpe {
-
-struct EcountEdges {  // (k << 1) | flip of every plan edge: 64 + 992 bytes by value
-    uint16_t pivot[kSetsMaxQ];                            // of position d's pivot edge (d >= 1)
-    uint16_t back[kSetsMaxQ * (kSetsMaxQ - 1) / 2];       // of P.back[j]
-};
-
-struct EcountWave {  // per wave in LDS, wave-uniform
-    SetsTally tally;            // finds below the current image of a position
-    uint32_t ient[kSetsMaxQ];   // CSR index of the entry (image of pivot[d] -> image of d)
-};
-
-// index in nbrs of `target` in the ascending row [st, st + d), kNoEdge if it is not there
-__device__ __forceinline__ uint32_t row_pos(const uint32_t *__restrict__ nbrs, uint32_t st, uint32_t d, uint32_t target)
-{
-    uint32_t lo = 0, hi = d;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        const uint32_t x = nbrs[st + mid];
-        if (x == target) return st + mid;
-        if (x < target) lo = mid + 1; else hi = mid;
-    }
-    return kNoEdge;
-}
-
-// the reverse (y -> x) of entry j = (x -> y), ys = adj_start[y]; kNoEdge if row y does not hold x
-__device__ __forceinline__ uint32_t entry_reverse(const uint32_t *__restrict__ revpos, uint32_t j, uint32_t ys)
-{
-    const uint32_t r = revpos[j];
-    return r == kNoEdge ? kNoEdge : ys + r;
-}
-
-// The entry of the data edge between an earlier image w (row ws, dw) and a later image v (row vs, dv): (w -> v), or with `flip`
-// (v -> w).  Searched in the shorter row, as the back-edge test does, and reversed if that is the other one.
-__device__ __forceinline__ uint32_t back_entry(const uint32_t *__restrict__ nbrs, const uint32_t *__restrict__ revpos, uint32_t w,
-                                               uint32_t ws, uint32_t dw, uint32_t v, uint32_t vs, uint32_t dv, bool flip)
-{
-    const bool in_v = dv <= dw;                                       // the search gives (v -> w), else (w -> v)
-    const uint32_t j = in_v ? row_pos(nbrs, vs, dv, w) : row_pos(nbrs, ws, dw, v);
-    if (j == kNoEdge || in_v == flip) return j;
-    return entry_reverse(revpos, j, in_v ? ws : vs);
-}
 
 // One kernel, four instantiations, as k_refine_sets: plain, SetsOrder (distinct), SetsNon (induced), both.
 template <bool kOrdered, class... Ord>
@@ -118,18 +78,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
         auto leaf = [&](uint32_t, uint32_t cb, bool ok, uint32_t v) {
             const uint32_t cnt = (uint32_t)__popcll(__ballot(ok));
             if (cnt == 0) return;
-            if (ok) {
-                const uint32_t vs = G.adj_start[v], dv = G.adj_deg[v];
-                const uint32_t pw = X.pivot[last];
-                uint32_t j = cb + lane;
-                if (pw & 1u) j = entry_reverse(revpos, j, vs);
-                if (j != kNoEdge) atomicAdd(&counts[(uint64_t)(pw >> 1) * entries + j], 1ull);
-                for (uint32_t e = P.back_off[last]; e < P.back_off[last + 1]; e++) {
-                    const uint32_t b = P.back[e], bw = X.back[e];
-                    j = back_entry(nbrs, revpos, uni(S.image[b]), uni(S.istart[b]), uni(S.ideg[b]), v, vs, dv, (bw & 1u) != 0);
-                    if (j != kNoEdge) atomicAdd(&counts[(uint64_t)(bw >> 1) * entries + j], 1ull);
-                }
-            }
+            if (ok) ecount_leaf_adds(P, X, S, G, revpos, counts, entries, lane, last, cb, v, 1ull);
             found(cnt);
         };
         // the subtree of position d's current image is complete: its finds to the entries of the position's query edges, one
@@ -139,20 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
             if (t == 0) return;
             if (d >= 1) {
                 const uint32_t nb = (uint32_t)P.back_off[d + 1] - P.back_off[d];
-                if (lane <= nb) {
-                    const uint32_t v = uni(S.image[d]), vs = uni(S.istart[d]), dv = uni(S.ideg[d]);
-                    uint32_t j, w16;
-                    if (lane == 0) {
-                        w16 = X.pivot[d];
-                        j = uni(E.ient[d]);
-                        if (w16 & 1u) j = entry_reverse(revpos, j, vs);
-                    } else {
-                        const uint32_t e = P.back_off[d] + lane - 1u, b = P.back[e];
-                        w16 = X.back[e];
-                        j = back_entry(nbrs, revpos, S.image[b], S.istart[b], S.ideg[b], v, vs, dv, (w16 & 1u) != 0);
-                    }
-                    if (j != kNoEdge) atomicAdd(&counts[(uint64_t)(w16 >> 1) * entries + j], t);
-                }
+                if (lane <= nb) ecount_flush_adds(P, X, S, E, G, revpos, counts, entries, lane, d, t);
                 tally_set(T, d - 1, tally_get(T, d - 1) + t);
                 flushed += nb + 1u;
             }
@@ -199,33 +135,11 @@ extern "C" int gnnpe_refine_sets_edge_counts(gnnpe_ctx *c, const char *query_gra
     if (rc || limit == 0) return rc;  // limit 0: nothing is launched, and nothing is complete
     const uint32_t nq = Q.nq, n_cand = Q.n_cand;
     const uint64_t entries = c->nbr_used;  // offsets[n] of gnnpe_load_csr: adj_start[x] = offsets[x], nbrs as handed over
-    // the query edges by number, from the plan: sets_prepare read a simple graph or its repeats count once here as well
+    // the query edges by number and the words of the plan edges: sets_prepare read a simple graph or its repeats count once here as well
     EcountEdges X = {};
     uint32_t nqe = 0, flips = 0, backflips = 0;
     if (!Q.empty) {
-        std::vector<std::pair<uint32_t, uint32_t>> qe;
-        auto norm = [&](uint32_t early, uint32_t late) {
-            const uint32_t a = Q.P.qv[early], b = Q.P.qv[late];
-            return std::make_pair(std::min(a, b), std::max(a, b));
-        };
-        for (uint32_t d = 1; d < nq; d++) {
-            qe.push_back(norm(Q.P.pivot[d], d));
-            for (uint32_t j = Q.P.back_off[d]; j < Q.P.back_off[d + 1]; j++) qe.push_back(norm(Q.P.back[j], d));
-        }
-        std::sort(qe.begin(), qe.end());
-        qe.erase(std::unique(qe.begin(), qe.end()), qe.end());
-        nqe = (uint32_t)qe.size();
-        auto word = [&](uint32_t early, uint32_t late, uint32_t *n_flip) {
-            const uint32_t k = (uint32_t)(std::lower_bound(qe.begin(), qe.end(), norm(early, late)) - qe.begin());
-            const uint32_t flip = Q.P.qv[early] > Q.P.qv[late] ? 1u : 0u;  // the earlier position's query vertex is b_k
-            *n_flip += flip;
-            return (uint16_t)((k << 1) | flip);
-        };
-        for (uint32_t d = 1; d < nq; d++) {
-            X.pivot[d] = word(Q.P.pivot[d], d, &flips);
-            for (uint32_t j = Q.P.back_off[d]; j < Q.P.back_off[d + 1]; j++) X.back[j] = word(Q.P.back[j], d, &backflips);
-        }
-        flips += backflips;
+        nqe = ecount_edges_from_plan(Q.P, &X, &flips, &backflips);
     } else if (nq > 1) {
         // an empty set: the table's height still has to be known for the zeros
         gnnpe_host::StaticGraph q;

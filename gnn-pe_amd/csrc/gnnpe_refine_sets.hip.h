@@ -1,12 +1,12 @@
 // gnnpe_refine_sets.hip.h -- what the set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip),
-// k_refine_vcount, k_refine_ecount and k_refine_delta (the files of those names) and the paged k_refine_pages
-// (gnnpe_refine_pages.hip).
-//   * All five, on the device: the plan by position in the matching order, the per-wave search state in LDS and every STEP of the
+// k_refine_vcount, k_refine_ecount and k_refine_delta (the files of those names), k_refine_delta_vcount and k_refine_delta_ecount
+// (gnnpe_refine_delta_counts.hip) and the paged k_refine_pages (gnnpe_refine_pages.hip).
+//   * All of them, on the device: the plan by position in the matching order, the per-wave search state in LDS and every STEP of the
 //     search: a chunk's lane test, the descent into a survivor, the decode of a first-level item, the single-vertex item.  On the
 //     host the preparation of a query (sets_prepare), the staging of its first-level items (sets_stage_items) and the choice of
 //     the instantiation (sets_dispatch).
-//   * The four one-shot kernels, on the device: the counter block, the ticket take, the find accounting and the limit, the loop
-//     that drives the steps (sets_walk), the row-writing leaf of two of them and the tallies of the other two.  A kernel keeps
+//   * The one-shot kernels, on the device: the counter block, the ticket take, the find accounting and the limit, the loop
+//     that drives the steps (sets_walk), the row-writing leaf of two of them and the tallies of the others.  A kernel keeps
 //     its item setup and its hooks.  On the host the events, the single wait and the error translation of a call (SetsCall) and
 //     the table handling of the two count calls (sets_count_call).
 // k_refine_pages keeps its own loop, leaf and polling.
@@ -271,10 +271,10 @@ struct SetsCounters {  // the 32-byte block at the head of the work buffer (Sets
     unsigned long long total;  // finds, each added once
     union {
         unsigned long long cursor;      // k_refine_sets, k_refine_delta: rows reserved
-        unsigned long long flush_adds;  // k_refine_vcount, k_refine_ecount: the atomic adds of their flushes (GNNPE_DEBUG prints it)
+        unsigned long long flush_adds;  // the kernels that fill a table: the atomic adds of their flushes (GNNPE_DEBUG prints it)
     };
     uint32_t ticket;  // the next item
-    uint32_t bad;     // k_delta_entries: a pair of F is no edge of the graph
+    uint32_t bad;     // k_delta_entries: a pair of F is no edge of the graph (the delta table kernels leave when it is set)
     uint32_t pad[2];
 };
 

@@ -171,7 +171,8 @@ struct Device {
 // matches only, so that the answer is I or ID; with --vertex-counts gnnpe_refine_sets_vertex_counts, which writes per data vertex
 // the matches it takes part in by query vertex; with --edge-counts gnnpe_refine_sets_edge_counts, the same per adjacency entry and
 // query edge; with --delta-edges gnnpe_refine_sets_delta, which counts and writes the matches through the listed data edges, each
-// once) and prints the reference's answer line instead of writing the file.
+// once, or with --delta-vertex-counts / --delta-edge-counts gnnpe_refine_sets_delta_vertex_counts / _edge_counts, which write the
+// count tables of those matches) and prints the reference's answer line instead of writing the file.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -286,6 +287,54 @@ int run_filter(const Options &o)
         const uint32_t match_mode = (o.distinct ? 1u /* GNNPE_MATCH_DISTINCT */ : 0u) | (o.induced ? 2u /* GNNPE_MATCH_INDUCED */ : 0u);
         uint64_t n_written = 0;
         uint64_t n_pages = 0;
+        // the files of --vertex-counts / --delta-vertex-counts and of --edge-counts / --delta-edge-counts, and F of --delta-edges
+        auto write_vertex_table = [&](const std::string &path, const std::vector<uint64_t> &table) {
+            FILE *vf = fopen(path.c_str(), "w");
+            if (!vf) die("cannot write " + path);
+            for (uint32_t v = 0; v < g.n; v++) {
+                bool any = false;
+                for (uint32_t u = 0; u < n_qv && !any; u++) any = table[(size_t)u * g.n + v] != 0;
+                if (!any) continue;
+                fprintf(vf, "%u", v);
+                for (uint32_t u = 0; u < n_qv; u++) fprintf(vf, " %llu", (unsigned long long)table[(size_t)u * g.n + v]);
+                fputc('\n', vf);
+            }
+            if (fclose(vf) != 0) die("write failed on " + path);
+        };
+        auto write_edge_table = [&](const std::string &path, uint32_t nqe, const std::vector<uint32_t> &qe, const std::vector<uint64_t> &table) {
+            const size_t entries = g.offsets[g.n];
+            FILE *ef = fopen(path.c_str(), "w");
+            if (!ef) die("cannot write " + path);
+            fputc('#', ef);
+            for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %u-%u", qe[2 * k], qe[2 * k + 1]);
+            fputc('\n', ef);
+            // the rows ascend, so the entries in CSR order are ascending by (x, y)
+            for (uint32_t x = 0; x < g.n; x++)
+                for (size_t j = g.offsets[x]; j < g.offsets[x + 1]; j++) {
+                    bool any = false;
+                    for (uint32_t k = 0; k < nqe && !any; k++) any = table[(size_t)k * entries + j] != 0;
+                    if (!any) continue;
+                    fprintf(ef, "%u %u", x, g.neighbors[j]);
+                    for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %llu", (unsigned long long)table[(size_t)k * entries + j]);
+                    fputc('\n', ef);
+                }
+            if (fclose(ef) != 0) die("write failed on " + path);
+        };
+        auto read_delta_edges = [&]() -> std::vector<uint32_t> {
+            std::vector<uint32_t> pairs;
+            FILE *df = fopen(o.delta_edges_file.c_str(), "r");
+            if (!df) die("cannot read " + o.delta_edges_file);
+            for (unsigned long long x, y;;) {
+                const int got = fscanf(df, "%llu %llu", &x, &y);
+                if (got == EOF) break;
+                if (got != 2 || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull) die(o.delta_edges_file + ": one `x y` per line expected");
+                pairs.push_back((uint32_t)x);
+                pairs.push_back((uint32_t)y);
+            }
+            fclose(df);
+            return pairs;
+        };
+        typedef int (*qedges_fn)(const char *, uint32_t *, uint32_t, uint32_t *);
         if (sets && o.all_matches) {
             // every embedding up to -n through the match cursor (gnnpe_refine_pages_*): one page on the host at a time
             typedef struct gnnpe_match_cursor cursor_t;
@@ -329,69 +378,57 @@ int run_filter(const Options &o)
             if (!complete)
                 die("--vertex-counts: the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " +
                     o.vertex_counts_file + " was not written; raise -n");
-            FILE *vf = fopen(o.vertex_counts_file.c_str(), "w");
-            if (!vf) die("cannot write " + o.vertex_counts_file);
-            for (uint32_t v = 0; v < g.n; v++) {
-                bool any = false;
-                for (uint32_t u = 0; u < n_qv && !any; u++) any = table[(size_t)u * g.n + v] != 0;
-                if (!any) continue;
-                fprintf(vf, "%u", v);
-                for (uint32_t u = 0; u < n_qv; u++) fprintf(vf, " %llu", (unsigned long long)table[(size_t)u * g.n + v]);
-                fputc('\n', vf);
-            }
-            if (fclose(vf) != 0) die("write failed on " + o.vertex_counts_file);
+            write_vertex_table(o.vertex_counts_file, table);
         } else if (sets && !o.edge_counts_file.empty()) {
             // per-edge match counts (gnnpe_refine_sets_edge_counts): -n is a guard, the table is exact only below it
             typedef int (*ecounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, int *, uint64_t *,
                                       void **, double *);
-            typedef int (*qedges_fn)(const char *, uint32_t *, uint32_t, uint32_t *);
             ecounts_fn ecounts = (ecounts_fn)dlsym(online, "gnnpe_refine_sets_edge_counts");
             qedges_fn qedges = (qedges_fn)dlsym(online, "gnnpe_host_query_edges");
             if (!ecounts || !qedges) die("libgnnpe_online.so does not export gnnpe_refine_sets_edge_counts");
             uint32_t nqe = 0;
             std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
             check(qedges(o.query_graph.c_str(), qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
-            const size_t entries = g.offsets[g.n];
-            std::vector<uint64_t> table((size_t)nqe * entries);
+            std::vector<uint64_t> table((size_t)nqe * g.offsets[g.n]);
             int complete = 0;
             check(ecounts(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, &complete, table.data(), nullptr,
                           &refine_ms), "refine_sets_edge_counts");
             if (!complete)
                 die("--edge-counts: the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " +
                     o.edge_counts_file + " was not written; raise -n");
-            FILE *ef = fopen(o.edge_counts_file.c_str(), "w");
-            if (!ef) die("cannot write " + o.edge_counts_file);
-            fputc('#', ef);
-            for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %u-%u", qe[2 * k], qe[2 * k + 1]);
-            fputc('\n', ef);
-            // the rows ascend, so the entries in CSR order are ascending by (x, y)
-            for (uint32_t x = 0; x < g.n; x++)
-                for (size_t j = g.offsets[x]; j < g.offsets[x + 1]; j++) {
-                    bool any = false;
-                    for (uint32_t k = 0; k < nqe && !any; k++) any = table[(size_t)k * entries + j] != 0;
-                    if (!any) continue;
-                    fprintf(ef, "%u %u", x, g.neighbors[j]);
-                    for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %llu", (unsigned long long)table[(size_t)k * entries + j]);
-                    fputc('\n', ef);
-                }
-            if (fclose(ef) != 0) die("write failed on " + o.edge_counts_file);
+            write_edge_table(o.edge_counts_file, nqe, qe, table);
+        } else if (sets && (!o.delta_vertex_counts_file.empty() || !o.delta_edge_counts_file.empty())) {
+            // the count tables of the matches through the data edges of --delta-edges (gnnpe_refine_sets_delta_vertex_counts /
+            // _edge_counts): -n is a guard as for --vertex-counts, the files are those of --vertex-counts / --edge-counts
+            typedef int (*dcounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, const uint32_t *, uint64_t, uint64_t, uint32_t, uint64_t *,
+                                      int *, uint64_t *, void **, void *, int, double *);
+            const bool edge_table = !o.delta_edge_counts_file.empty();
+            const std::string flag = edge_table ? "--delta-edge-counts" : "--delta-vertex-counts";
+            const std::string &path = edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file;
+            const char *name = edge_table ? "gnnpe_refine_sets_delta_edge_counts" : "gnnpe_refine_sets_delta_vertex_counts";
+            dcounts_fn dcounts = (dcounts_fn)dlsym(online, name);
+            qedges_fn qedges = (qedges_fn)dlsym(online, "gnnpe_host_query_edges");
+            if (!dcounts || !qedges) die(std::string("libgnnpe_online.so does not export ") + name);
+            uint32_t nqe = 0;
+            std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
+            check(qedges(o.query_graph.c_str(), qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
+            const std::vector<uint32_t> edges = read_delta_edges();
+            std::vector<uint64_t> table(edge_table ? (size_t)nqe * g.offsets[g.n] : (size_t)n_qv * g.n);
+            int complete = 0;
+            check(dcounts(ctx, o.query_graph.c_str(), bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &answers, &complete,
+                          table.data(), nullptr, nullptr, 1, &refine_ms), name + 6);
+            if (!complete)
+                die(flag + ": the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " + path +
+                    " was not written; raise -n");
+            if (edge_table) write_edge_table(path, nqe, qe, table);
+            else write_vertex_table(path, table);
         } else if (sets && !o.delta_edges_file.empty()) {
             // the matches through the data edges of FILE, each once (gnnpe_refine_sets_delta); --matches as below
             typedef int (*delta_fn)(gnnpe_ctx *, const char *, const uint32_t *, const uint32_t *, uint64_t, uint64_t, uint32_t, uint64_t *,
                                     uint32_t *, uint64_t, double *);
             delta_fn delta = (delta_fn)dlsym(online, "gnnpe_refine_sets_delta");
             if (!delta) die("libgnnpe_online.so does not export gnnpe_refine_sets_delta");
-            std::vector<uint32_t> edges;
-            FILE *df = fopen(o.delta_edges_file.c_str(), "r");
-            if (!df) die("cannot read " + o.delta_edges_file);
-            for (unsigned long long x, y;;) {
-                const int got = fscanf(df, "%llu %llu", &x, &y);
-                if (got == EOF) break;
-                if (got != 2 || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull) die(o.delta_edges_file + ": one `x y` per line expected");
-                edges.push_back((uint32_t)x);
-                edges.push_back((uint32_t)y);
-            }
-            fclose(df);
+            const std::vector<uint32_t> edges = read_delta_edges();
             const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
             std::vector<uint32_t> rows((size_t)cap * n_qv);
             check(delta(ctx, o.query_graph.c_str(), bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &answers,
@@ -520,6 +557,14 @@ int main(int argc, char **argv)
     if (!o.delta_edges_file.empty() && o.refine != "sets") die("--delta-edges needs --refine sets");
     if (!o.delta_edges_file.empty() && (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty()))
         die("--delta-edges excludes --all-matches, --vertex-counts and --edge-counts");
+    for (const char *flag : {"--delta-vertex-counts", "--delta-edge-counts"}) {
+        const bool edge_table = std::string(flag) == "--delta-edge-counts";
+        if ((edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file).empty()) continue;
+        if (o.refine != "sets") die(std::string(flag) + " needs --refine sets");
+        if (o.delta_edges_file.empty()) die(std::string(flag) + " needs --delta-edges FILE");
+        if (edge_table && !o.delta_vertex_counts_file.empty()) die("--delta-vertex-counts and --delta-edge-counts exclude each other");
+        if (!o.matches_file.empty()) die(std::string(flag) + " and --matches exclude each other");
+    }
     if (o.refine == "sets" && o.mode != "online") die("--refine sets applies to -m online only");
     // exact -m online / -m filter read nothing that was derived from the old graph (only the data graph and membership.txt)
     if (!o.apply_edges_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))

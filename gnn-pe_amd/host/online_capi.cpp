@@ -203,6 +203,61 @@ int gnnpe_host_refine_sets_delta(uint32_t n, const uint32_t *offsets, const uint
     return 0;
 }
 
+// gnnpe_host_refine_sets_delta_vertex_counts and gnnpe_host_refine_sets_delta_edge_counts
+// (counts may be null where the edge table is empty: refine_sets_delta_edge_counts looks at it once the query is known)
+static int host_delta_table(const char *who, bool edge_table, uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
+                            const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers, int *complete,
+                            uint64_t *counts)
+{
+    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || !complete || (!counts && !edge_table) ||
+        (!delta_edges && n_delta)) {
+        gnnpe::set_error("%s: null argument", who);
+        return GNNPE_ERR_ARG;
+    }
+    *answers = 0;
+    *complete = 0;
+    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
+        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
+        return GNNPE_ERR_ARG;
+    }
+    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0, induced = (mode & GNNPE_MATCH_INDUCED) != 0;
+    gnnpe_host::StaticGraph q;
+    std::string err;
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
+    gnnpe_host::QuerySymmetry sym;
+    if (distinct) sym = gnnpe_host::query_symmetry(q);
+    bool done = false;
+    const auto fn = edge_table ? gnnpe_host::refine_sets_delta_edge_counts : gnnpe_host::refine_sets_delta_vertex_counts;
+    if (fn(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, delta_edges, n_delta, limit, answers, &done, counts, &err,
+           distinct ? &sym.pairs : nullptr, induced) != 0) {
+        *answers = 0;
+        gnnpe::set_error("%s: %s", who, err.c_str());
+        return GNNPE_ERR_ARG;
+    }
+    *complete = done ? 1 : 0;
+    return 0;
+}
+
+int gnnpe_host_refine_sets_delta_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                               const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                               const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                               uint64_t *answers, int *complete, uint64_t *counts)
+{
+    return host_delta_table("gnnpe_host_refine_sets_delta_vertex_counts", false, n, offsets, nbrs, labels, query_graph_path,
+                            candidate_bitmap, delta_edges, n_delta, limit, mode, answers, complete, counts);
+}
+
+int gnnpe_host_refine_sets_delta_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                             const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                             const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                             uint64_t *answers, int *complete, uint64_t *counts)
+{
+    return host_delta_table("gnnpe_host_refine_sets_delta_edge_counts", true, n, offsets, nbrs, labels, query_graph_path,
+                            candidate_bitmap, delta_edges, n_delta, limit, mode, answers, complete, counts);
+}
+
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
 {
     if (!query_graph_path || !n_edges || (!edges && cap)) {

@@ -88,7 +88,8 @@ struct SetSearch {
 }  // namespace
 
 // refine_sets_count (no table), refine_sets_vertex_counts and refine_sets_edge_counts: one search, a table is filled at the finds;
-// refine_sets_delta_count: the same search, a find that touches no edge of `delta` is dropped
+// refine_sets_delta_count: the same search, a find that touches no edge of `delta` is dropped; refine_sets_delta_vertex_counts and
+// refine_sets_delta_edge_counts: both at once, the table is filled at the finds that are kept
 static int refine_sets_search(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
                               uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced,
                               uint64_t *vcounts, uint64_t *ecounts = nullptr, const std::vector<uint64_t> *delta = nullptr)
@@ -211,22 +212,72 @@ int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, s
     return 0;
 }
 
-int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
-                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+// F as ascending keys, each a checked edge of the graph: what the three delta forms refuse
+static int delta_keys_checked(const StaticGraph &data, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys,
+                              std::string *err)
 {
-    if (answers) *answers = 0;
-    std::vector<uint64_t> keys;
-    if (delta_edge_keys(data.n, delta_edges, n_delta, &keys, err) != 0) return -2;
-    for (uint64_t key : keys) {
+    if (delta_edge_keys(data.n, delta_edges, n_delta, keys, err) != 0) return -2;
+    for (uint64_t key : *keys) {
         const uint32_t x = (uint32_t)(key >> 32), y = (uint32_t)key;
         if (!std::binary_search(data.neighbors.begin() + data.offsets[x], data.neighbors.begin() + data.offsets[x + 1], y)) {
             if (err) *err = "delta edge (" + std::to_string(x) + ", " + std::to_string(y) + ") is not an edge of the graph";
             return -2;
         }
     }
+    return 0;
+}
+
+int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
+                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+{
+    if (answers) *answers = 0;
+    std::vector<uint64_t> keys;
+    if (delta_keys_checked(data, delta_edges, n_delta, &keys, err) != 0) return -2;
     // (an empty F drops every find; the walk still refuses what refine_sets_count refuses)
     return refine_sets_search(data, query, bitmap, words, keys.empty() ? 0 : limit, answers, err, pairs, induced, nullptr, nullptr, &keys);
+}
+
+// refine_sets_delta_vertex_counts (edge_table false) and refine_sets_delta_edge_counts (true): the search of refine_sets_delta_count
+// with the table of refine_sets_vertex_counts / refine_sets_edge_counts filled at the finds that are kept
+static int refine_sets_delta_table(bool edge_table, const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap,
+                                   uint64_t words, const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers,
+                                   bool *complete, uint64_t *counts, std::string *err,
+                                   const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+{
+    const size_t cells = edge_table ? query_edges(query).size() * (size_t)(data.n ? data.offsets[data.n] : 0) : (size_t)query.n * data.n;
+    if (answers) *answers = 0;
+    if (!complete || (!counts && cells)) {
+        if (err) *err = "refine_sets_delta counts: null argument";
+        return -2;
+    }
+    *complete = false;
+    std::vector<uint64_t> keys;
+    if (delta_keys_checked(data, delta_edges, n_delta, &keys, err) != 0) return -2;
+    if (cells) std::fill(counts, counts + cells, 0ull);
+    uint64_t *table = cells ? counts : nullptr;
+    const int rc = refine_sets_search(data, query, bitmap, words, keys.empty() ? 0 : limit, answers, err, pairs, induced,
+                                      edge_table ? nullptr : table, edge_table ? table : nullptr, &keys);
+    if (rc == 0) *complete = *answers < limit;  // as in refine_sets_vertex_counts, with Delta in the place of |M|; no F: 0 < limit
+    return rc;
+}
+
+int refine_sets_delta_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                                    const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
+                                    uint64_t *counts, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
+                                    bool induced)
+{
+    return refine_sets_delta_table(false, data, query, bitmap, words, delta_edges, n_delta, limit, answers, complete, counts, err, pairs,
+                                   induced);
+}
+
+int refine_sets_delta_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                                  const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
+                                  uint64_t *counts, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
+                                  bool induced)
+{
+    return refine_sets_delta_table(true, data, query, bitmap, words, delta_edges, n_delta, limit, answers, complete, counts, err, pairs,
+                                   induced);
 }
 
 }  // namespace gnnpe_host

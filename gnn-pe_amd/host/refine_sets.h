@@ -81,4 +81,17 @@ int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, c
                             const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
                             const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
 
+// VDelta_m(C, F) and EDelta_m(C, F) of include/gnnpe_online.h: the tables of refine_sets_vertex_counts / refine_sets_edge_counts
+// over the maps refine_sets_delta_count counts only.  The same unchanged backtracking over all of M, the F test at every find, then
+// the cell increments.  limit and *complete as in refine_sets_vertex_counts with Delta in the place of |M|; refusals as
+// refine_sets_delta_count.  A query without an edge has no edge table: counts may then be null.
+int refine_sets_delta_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                                    const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
+                                    uint64_t *counts, std::string *err,
+                                    const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+int refine_sets_delta_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
+                                  const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
+                                  uint64_t *counts, std::string *err,
+                                  const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+
 }  // namespace gnnpe_host

@@ -316,6 +316,76 @@ int gnnpe_refine_sets_delta(gnnpe_ctx *ctx, const char *query_graph_path, const 
                             const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
                             uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms);
 
+/* ---- ABI version 17: count tables of the matches through a set of data edges ----------------------------------------------
+ * The consumers of the ABI 13 and 14 tables -- graphlet degree vectors, local triangle and clique counts, the truss support of
+ * every edge -- do not want the rows of gnnpe_refine_sets_delta after a batch of edge changes.  They want their table brought up
+ * to date.  Re-running the whole count pays for |M|; tallying the delta rows on the host moves Delta * nq * 4 bytes and cannot be
+ * done at all where Delta is 10^9.  The functions below build the TABLES of the matches through F inside the edge-anchored search,
+ * and can add them to, or subtract them from, a table the caller keeps on the device:
+ *     T -= tables of Delta(G, D);  gnnpe_csr_apply_edges(ctx, I, D);  T += tables of Delta(G', I).
+ * Nothing per match leaves the device.
+ *
+ * M_m(C), the query edges (a_k, b_k), the entry index j, F and its hand-over as delta_edges are as in the ABI 13, 14 and 15 texts.
+ * Let Dset_m(C, F) = { f in M_m(C) : {f(a_k), f(b_k)} in F for at least one k }.
+ *
+ *   VD_m(C, F)[u][v] = |{ f in Dset : f(u) = v }|                      nq  x n           uint64, row-major
+ *   ED_m(C, F)[k][j] = |{ f in Dset : f(a_k) = x and f(b_k) = y }|     nqe x offsets[n]  uint64, j = (x -> y)
+ *
+ *   - every row of either table sums to |Dset| = Delta_m(C, F, 2^64 - 1).
+ *   - summing ED row k over the entries of data row x gives VD[a_k][x].
+ *   - F = E(G) and nq >= 2: VD = V_m(C) and ED = E_m(C).
+ *   - INSERTION IDENTITY, modes 0 and DISTINCT.  G' = G + F with F disjoint from E(G), the same C: as sets of maps
+ *     M(G') = M(G) + Dset(G', F), disjoint.  Hence V(G') = V(G) + VD(G', F), and E(G') = E(G) + ED(G', F) compared by the key
+ *     (x, y) of an entry -- the entry indices of G and G' differ; an entry of F has E(G) = 0.
+ *   - DELETION IDENTITY, the same modes.  V(G - D) = V(G) - VD(G, D), and the same for E by keys.
+ *   - the INDUCED modes: the tables are "the matches on the loaded graph that touch F", nothing more (the caveat of ABI 15).
+ *   - a single-vertex query has Delta = 0: the V table is all zeros, the E table is empty as in ABI 14.
+ *   - n_delta == 0: the tables are all zeros.
+ *
+ * limit is a GUARD exactly as in ABI 13 and 14, with Delta in the place of |M|: *answers = min(Delta, limit); *complete = 1 iff
+ * Delta < limit; with *complete = 0 the table is unspecified and nothing is copied to the host; limit == 0 launches nothing and
+ * gives *complete = 0; an empty C(u), no F or a single-vertex query launches nothing and gives a zero table and *complete = 1.
+ *
+ * gnnpe_host_refine_sets_delta_vertex_counts, gnnpe_host_refine_sets_delta_edge_counts: the host forms, the yardstick.  The unchanged
+ *   backtracking of gnnpe_host_refine_sets_mode over all of M; at every find the F test of gnnpe_host_refine_sets_delta, then the
+ *   cell increments of gnnpe_host_refine_sets_vertex_counts / _edge_counts.  They share nothing with the device search.  Refusals
+ *   are those of gnnpe_host_refine_sets_delta.  counts is the caller's (nq x n, nqe x offsets[n]; NULL is accepted for an empty
+ *   edge table).
+ * gnnpe_refine_sets_delta_vertex_counts, gnnpe_refine_sets_delta_edge_counts: the device forms (csrc/gnnpe_refine_delta_counts.hip):
+ *   the launches, items and charging rule of gnnpe_refine_sets_delta with the tallies and flushes of the ABI 13 / 14 kernels.
+ *   Requirements and refusals are exactly those of gnnpe_refine_sets_delta: a loop or an id >= n is refused on the host, a pair
+ *   that is no edge is found on the device and reported after the call's single wait, the context stays usable, and *answers is
+ *   0 on every refusal.
+ *   - dev_accum == NULL: sign must be 1 (else GNNPE_ERR_ARG).  The table lives in a context-owned, grow-only buffer of its own --
+ *     one for VD, another for ED, neither of them the buffers of ABI 13 and 14, whose device views are not disturbed -- and is
+ *     zeroed once per call, before the first launch.  It is valid until the next call of the same function on the context or
+ *     until the context's rows are loaded or changed (gnnpe_csr_apply_edges changes them).  host_counts and *dev_counts are as
+ *     in ABI 13 and 14.
+ *   - dev_accum != NULL: caller-owned device memory of the table's size on the context's device (gnnpe_dev_alloc, a torch
+ *     tensor).  sign is +1 or -1; host_counts must be NULL (else GNNPE_ERR_ARG); *dev_counts = dev_accum.  Nothing is zeroed:
+ *     every cell ends at old + sign * c mod 2^64, c the cell of the table above.  All work is on the context's stream.
+ *       . A refused call leaves the caller's table untouched, byte for byte: the pairs are looked up before the first search
+ *         launch starts, and a search wave that finds the error flag set leaves before its first item.
+ *       . With *complete = 0 the caller's table is unspecified: pass limit = 2^64 - 1 when accumulating.
+ *       . Where nothing is launched the table is untouched.
+ *   - *device_ms (may be NULL) covers the zeroing of a context-owned table and the kernels, not the uploads. */
+int gnnpe_host_refine_sets_delta_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                               const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                               const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                               uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_host_refine_sets_delta_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                             const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                             const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                             uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_refine_sets_delta_vertex_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                          const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                          uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
+                                          void *dev_accum, int sign, double *device_ms);
+int gnnpe_refine_sets_delta_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                        const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
+                                        uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
+                                        void *dev_accum, int sign, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
