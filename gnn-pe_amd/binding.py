@@ -407,47 +407,57 @@ def match_mode(distinct=False, induced=False):
     return (MATCH_DISTINCT if distinct else 0) | (MATCH_INDUCED if induced else 0)
 
 
+def _bitmap_rows(bm, n):
+    """query vertices of a bitmap: its rows, or for a flat one its words over ceil(n / 32)"""
+    return bm.shape[0] if bm.ndim == 2 else bm.size // max((n + 31) // 32, 1)
+
+
+def _delta_pairs(edges):
+    """F of the delta calls as a contiguous (n_delta, 2) uint32 array; ids that do not fit 32 bits are refused here"""
+    e = np.asarray(edges, np.int64).reshape(-1, 2)
+    if e.size and (e.min() < 0 or e.max() > 0xFFFFFFFF):
+        raise GnnpeError("delta edges: vertex ids are uint32")
+    return np.ascontiguousarray(e, np.uint32)
+
+
+def _host_sets(entry, g, query_path, bitmap, limit, mode=None, edges=None, shape=None):
+    """One call of a host entry of the set-restricted refinement (include/gnnpe_online.h): g, the bitmap, F where `edges` is
+    given, the mode word unless `mode` is None (the two entries without one), and a zeroed table where `shape` is given.
+    Returns answers, or with a table (answers, complete, counts); a refusal raises GnnpeError with the library's text."""
+    lib = load()
+    out, done = C.c_uint64(), C.c_int()
+    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm = _np(bitmap, np.uint32)
+    args = [len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(), _ptr(bm, _u32p)]
+    if edges is not None:
+        e = _delta_pairs(edges)
+        args += [_ptr(e, _u32p) if len(e) else None, len(e)]
+    args += [int(limit)] + ([] if mode is None else [mode]) + [C.byref(out)]
+    if shape is not None:
+        counts = np.zeros(shape, np.uint64)
+        args += [C.byref(done), _ptr(counts, _u64p)]
+    if getattr(load_online(), entry)(*args):
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return out.value if shape is None else (out.value, bool(done.value), counts)
+
+
 def host_refine_sets(g, query_path, bitmap, limit=0xFFFFFFFF, distinct=False, induced=False):
     """Set-restricted refinement on the host (include/gnnpe_online.h, R(C, limit)): the embeddings whose every image lies in its
     query vertex's set, counted up to `limit`.  distinct=True: D(C, limit), one embedding per distinct subgraph.  induced=True:
     I(C, limit) (with distinct ID): only the maps that send non-adjacent query vertices to non-adjacent data vertices."""
-    lib = load()
-    out = C.c_uint64()
-    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
-    bm = _np(bitmap, np.uint32)
     if induced:
-        rc = load_online().gnnpe_host_refine_sets_mode(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
-                                                       _ptr(bm, _u32p), int(limit), match_mode(distinct, induced), C.byref(out))
-    else:
-        fn = load_online().gnnpe_host_refine_sets_distinct if distinct else load_online().gnnpe_host_refine_sets
-        rc = fn(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(), _ptr(bm, _u32p), int(limit),
-                C.byref(out))
-    if rc:
-        raise GnnpeError(lib.gnnpe_last_error().decode())
-    return out.value
-
-
-def _bitmap_rows(bm, n):
-    """query vertices of a bitmap: its rows, or for a flat one its words over ceil(n / 32)"""
-    return bm.shape[0] if bm.ndim == 2 else bm.size // max((n + 31) // 32, 1)
+        return _host_sets("gnnpe_host_refine_sets_mode", g, query_path, bitmap, limit, match_mode(distinct, induced))
+    # (the entries of ABI 9 and ABI 11, which take no mode word)
+    return _host_sets("gnnpe_host_refine_sets_distinct" if distinct else "gnnpe_host_refine_sets", g, query_path, bitmap, limit)
 
 
 def host_refine_sets_vertex_counts(g, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False):
     """Per-vertex match counts on the host (include/gnnpe_online.h, V_m(C)): (answers, complete, counts) with counts[u, v] = the
     matches of the mode that send query vertex u to data vertex v, an (nq, n) uint64 array; nq is taken from the bitmap's rows.
     `limit` is a guard: answers = min(matches, limit), complete = matches < limit, and counts is exact only where complete."""
-    lib = load()
-    out, done = C.c_uint64(), C.c_int()
-    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
-    bm = _np(bitmap, np.uint32)
-    n = len(o) - 1
-    counts = np.zeros((_bitmap_rows(bm, n), n), np.uint64)
-    rc = load_online().gnnpe_host_refine_sets_vertex_counts(n, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
-                                                            _ptr(bm, _u32p), int(limit), match_mode(distinct, induced),
-                                                            C.byref(out), C.byref(done), _ptr(counts, _u64p))
-    if rc:
-        raise GnnpeError(lib.gnnpe_last_error().decode())
-    return out.value, bool(done.value), counts
+    bm, n = _np(bitmap, np.uint32), len(g["offsets"]) - 1
+    return _host_sets("gnnpe_host_refine_sets_vertex_counts", g, query_path, bm, limit, match_mode(distinct, induced),
+                      shape=(_bitmap_rows(bm, n), n))
 
 
 def host_query_edges(query_path):
@@ -462,77 +472,40 @@ def host_query_edges(query_path):
     return edges[:k.value].copy()
 
 
+def _edge_table_shape(g, query_path):
+    return len(host_query_edges(query_path)), int(np.asarray(g["offsets"])[-1])
+
+
 def host_refine_sets_edge_counts(g, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False):
     """Per-edge match counts on the host (include/gnnpe_online.h, E_m(C)): (answers, complete, counts) with counts[k, j] = the
     matches of the mode that send query edge k = host_query_edges(query_path)[k] = (a, b) onto adjacency entry j of g: a to the
     vertex whose row holds j, b to g["nbrs"][j]; an (nqe, len(g["nbrs"])) uint64 array.  `limit` is a guard: answers =
     min(matches, limit), complete = matches < limit, and counts is exact only where complete."""
-    lib = load()
-    out, done = C.c_uint64(), C.c_int()
-    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
-    bm = _np(bitmap, np.uint32)
-    counts = np.zeros((len(host_query_edges(query_path)), int(o[-1])), np.uint64)
-    rc = load_online().gnnpe_host_refine_sets_edge_counts(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p),
-                                                          query_path.encode(), _ptr(bm, _u32p), int(limit), match_mode(distinct, induced),
-                                                          C.byref(out), C.byref(done), _ptr(counts, _u64p))
-    if rc:
-        raise GnnpeError(lib.gnnpe_last_error().decode())
-    return out.value, bool(done.value), counts
-
-
-def _delta_pairs(edges):
-    """F of the delta calls as a contiguous (n_delta, 2) uint32 array; ids that do not fit 32 bits are refused here"""
-    e = np.asarray(edges, np.int64).reshape(-1, 2)
-    if e.size and (e.min() < 0 or e.max() > 0xFFFFFFFF):
-        raise GnnpeError("delta edges: vertex ids are uint32")
-    return np.ascontiguousarray(e, np.uint32)
+    return _host_sets("gnnpe_host_refine_sets_edge_counts", g, query_path, bitmap, limit, match_mode(distinct, induced),
+                      shape=_edge_table_shape(g, query_path))
 
 
 def host_refine_sets_delta(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
     """The matches through a set of data edges on the host (include/gnnpe_online.h, Delta_m(C, F, limit)): the number of matches
     of the mode that put at least one query edge on one of `edges` (pairs (x, y), either orientation, repeats tolerated), each
     match once, up to `limit`.  A pair that is no edge of g, a loop or an id outside g raises GnnpeError."""
-    lib = load()
-    out = C.c_uint64()
-    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
-    bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
-    rc = load_online().gnnpe_host_refine_sets_delta(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
-                                                    _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
-                                                    match_mode(distinct, induced), C.byref(out))
-    if rc:
-        raise GnnpeError(lib.gnnpe_last_error().decode())
-    return out.value
-
-
-def _host_delta_table(fn_name, shape, g, query_path, bitmap, edges, limit, distinct, induced):
-    lib = load()
-    out, done = C.c_uint64(), C.c_int()
-    o, nb, lb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
-    bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
-    counts = np.zeros(shape, np.uint64)
-    rc = getattr(load_online(), fn_name)(len(o) - 1, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lb, _u32p), query_path.encode(),
-                                         _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
-                                         match_mode(distinct, induced), C.byref(out), C.byref(done), _ptr(counts, _u64p))
-    if rc:
-        raise GnnpeError(lib.gnnpe_last_error().decode())
-    return out.value, bool(done.value), counts
+    return _host_sets("gnnpe_host_refine_sets_delta", g, query_path, bitmap, limit, match_mode(distinct, induced), edges)
 
 
 def host_refine_sets_delta_vertex_counts(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
     """The per-vertex table of the matches through a set of data edges on the host (include/gnnpe_online.h, ABI 17): (answers,
     complete, counts) as host_refine_sets_vertex_counts, over the matches host_refine_sets_delta counts only; answers =
     min(Delta, limit), complete = Delta < limit.  `edges` as for host_refine_sets_delta."""
-    bm = _np(bitmap, np.uint32)
-    n = len(g["offsets"]) - 1
-    return _host_delta_table("gnnpe_host_refine_sets_delta_vertex_counts", (_bitmap_rows(bm, n), n), g, query_path, bm, edges, limit,
-                             distinct, induced)
+    bm, n = _np(bitmap, np.uint32), len(g["offsets"]) - 1
+    return _host_sets("gnnpe_host_refine_sets_delta_vertex_counts", g, query_path, bm, limit, match_mode(distinct, induced), edges,
+                      (_bitmap_rows(bm, n), n))
 
 
 def host_refine_sets_delta_edge_counts(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
     """The per-edge table of the matches through a set of data edges on the host (include/gnnpe_online.h, ABI 17): (answers,
     complete, counts) as host_refine_sets_edge_counts, over the matches host_refine_sets_delta counts only."""
-    shape = (len(host_query_edges(query_path)), int(np.asarray(g["offsets"])[-1]))
-    return _host_delta_table("gnnpe_host_refine_sets_delta_edge_counts", shape, g, query_path, bitmap, edges, limit, distinct, induced)
+    return _host_sets("gnnpe_host_refine_sets_delta_edge_counts", g, query_path, bitmap, limit, match_mode(distinct, induced), edges,
+                      _edge_table_shape(g, query_path))
 
 
 def host_apply_edges(g, insert=None, delete=None):
@@ -1036,22 +1009,33 @@ class Engine:
             return out.value, ms.value
         return out.value, ms.value, rows[:min(out.value, cap)]
 
+    def _sets_table(self, entry, shape, query_path, bitmap, limit, distinct, induced, device, edges=None, accum=None, sign=1):
+        """One call of gnnpe_refine_sets_vertex_counts / _edge_counts or, where `edges` is given, of their _delta_ forms (which
+        alone take accum and sign): (answers, complete, counts, device ms).  counts is the host table of `shape`, or with
+        device=True or accum a view of the device table the call names."""
+        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
+        bm = _np(bitmap, np.uint32)
+        counts = None if device or accum is not None else np.zeros(shape, np.uint64)
+        args = [self.ctx, query_path.encode(), _ptr(bm, _u32p)]
+        if edges is not None:
+            args += [_ptr(edges, _u32p) if len(edges) else None, len(edges)]
+        args += [int(limit), match_mode(distinct, induced), C.byref(out), C.byref(done), _ptr(counts, _u64p), C.byref(ptr)]
+        if edges is not None:
+            args += [None if accum is None else C.c_void_p(int(accum)), int(sign)]
+        self._ck(getattr(load_online(), entry)(*args, C.byref(ms)))
+        if counts is None:
+            counts = _DevArray(int(ptr.value or 0), shape, "<i8", owner=self)
+        return out.value, bool(done.value), counts, ms.value
+
     def refine_sets_vertex_counts(self, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False, device=False):
         """Per-vertex match counts on the device (gnnpe_refine_sets_vertex_counts): (answers, complete, counts, device ms) with
         counts[u, v] = the matches of the mode that send query vertex u to data vertex v, (nq, n) uint64.  `limit` is a guard:
         complete = matches < limit, and counts is exact only where complete.  device=True: counts is a view of the context's
         device table (`torch.as_tensor(counts, device=...)` shares it: int64 words holding the uint64 counts), with no host copy,
         valid until the next call of this method or until another graph is loaded."""
-        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
         bm = _np(bitmap, np.uint32)
-        nq = _bitmap_rows(bm, self.n)
-        counts = None if device else np.zeros((nq, self.n), np.uint64)
-        self._ck(load_online().gnnpe_refine_sets_vertex_counts(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit),
-                                                               match_mode(distinct, induced), C.byref(out), C.byref(done),
-                                                               _ptr(counts, _u64p), C.byref(ptr), C.byref(ms)))
-        if device:
-            counts = _DevArray(int(ptr.value or 0), (nq, self.n), "<i8", owner=self)
-        return out.value, bool(done.value), counts, ms.value
+        return self._sets_table("gnnpe_refine_sets_vertex_counts", (_bitmap_rows(bm, self.n), self.n), query_path, bm, limit, distinct,
+                                induced, device)
 
     def refine_sets_edge_counts(self, query_path, bitmap, limit=2 ** 64 - 1, distinct=False, induced=False, device=False):
         """Per-edge match counts on the device (gnnpe_refine_sets_edge_counts): (answers, complete, counts, device ms) with
@@ -1060,18 +1044,12 @@ class Engine:
         where complete.  device=True: counts is a view of the context's device table (`torch.as_tensor(counts, device=...)`
         shares it: int64 words holding the uint64 counts), with no host copy, valid until the next call of this method or until
         another graph is loaded; edge_counts_to_host(counts) copies it back and refuses a view that is no longer valid."""
-        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
-        bm = _np(bitmap, np.uint32)
         shape = (len(host_query_edges(query_path)), self.entries)
-        counts = None if device else np.zeros(shape, np.uint64)
         self._ecounts_call += 1
-        self._ck(load_online().gnnpe_refine_sets_edge_counts(self.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit),
-                                                             match_mode(distinct, induced), C.byref(out), C.byref(done),
-                                                             _ptr(counts, _u64p), C.byref(ptr), C.byref(ms)))
+        got = self._sets_table("gnnpe_refine_sets_edge_counts", shape, query_path, bitmap, limit, distinct, induced, device)
         if device:
-            counts = _DevArray(int(ptr.value or 0), shape, "<i8", owner=self)
-            counts.valid_for = (self._rows_gen, self._ecounts_call)
-        return out.value, bool(done.value), counts, ms.value
+            got[2].valid_for = (self._rows_gen, self._ecounts_call)
+        return got
 
     def refine_sets_delta(self, query_path, bitmap, edges, limit=2 ** 64 - 1, matches_cap=0, distinct=False, induced=False):
         """The matches through a set of data edges on the device (gnnpe_refine_sets_delta): (answers, rows, device ms).  answers =
@@ -1089,20 +1067,14 @@ class Engine:
         return out.value, rows[:min(out.value, cap)], ms.value
 
     def _refine_sets_delta_counts(self, kind, shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign):
-        out, done, ms, ptr = C.c_uint64(), C.c_int(), C.c_double(), C.c_void_p()
-        bm, e = _np(bitmap, np.uint32), _delta_pairs(edges)
-        counts = None if device or accum is not None else np.zeros(shape, np.uint64)
+        e = _delta_pairs(edges)
         if accum is None:
             self._delta_counts_call[kind] += 1
-        fn = getattr(load_online(), f"gnnpe_refine_sets_delta_{kind}_counts")
-        self._ck(fn(self.ctx, query_path.encode(), _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
-                    match_mode(distinct, induced), C.byref(out), C.byref(done), _ptr(counts, _u64p), C.byref(ptr),
-                    None if accum is None else C.c_void_p(int(accum)), int(sign), C.byref(ms)))
-        if counts is None:
-            counts = _DevArray(int(ptr.value or 0), shape, "<i8", owner=self)
-            if accum is None:
-                counts.valid_for = (kind, self._rows_gen, self._delta_counts_call[kind])
-        return out.value, bool(done.value), counts, ms.value
+        got = self._sets_table(f"gnnpe_refine_sets_delta_{kind}_counts", shape, query_path, bitmap, limit, distinct, induced, device, e,
+                               accum, sign)
+        if device and accum is None:
+            got[2].valid_for = (kind, self._rows_gen, self._delta_counts_call[kind])
+        return got
 
     def refine_sets_delta_vertex_counts(self, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False, device=False,
                                         accum=None, sign=1):
@@ -1126,27 +1098,27 @@ class Engine:
         shape = (len(host_query_edges(query_path)), self.entries)
         return self._refine_sets_delta_counts("edge", shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign)
 
-    def delta_counts_to_host(self, view):
-        """the context's own device table a refine_sets_delta_vertex_counts / _edge_counts(..., device=True) call returned, copied
-        to the host as uint64; a view from before the latest such call or from before the rows were loaded or changed is refused"""
-        kind = (getattr(view, "valid_for", None) or (None,))[0]
-        if getattr(view, "owner", None) is not self or kind not in self._delta_counts_call or \
-                view.valid_for != (kind, self._rows_gen, self._delta_counts_call[kind]):
-            raise GnnpeError("stale delta-count view: the table was replaced by a later call or the graph was loaded or changed")
+    def _counts_view_to_host(self, view, stamp, stale):
+        """a device table of this context copied to the host as uint64, unless its valid_for is not `stamp` any more"""
+        if getattr(view, "owner", None) is not self or getattr(view, "valid_for", None) != stamp:
+            raise GnnpeError(stale)
         nbytes = view.shape[0] * view.shape[1] * 8
         if nbytes == 0:
             return np.zeros(view.shape, np.uint64)
         return self.copy_to_host(view.__cuda_array_interface__["data"][0], nbytes).view(np.uint64).reshape(view.shape)
 
+    def delta_counts_to_host(self, view):
+        """the context's own device table a refine_sets_delta_vertex_counts / _edge_counts(..., device=True) call returned, copied
+        to the host as uint64; a view from before the latest such call or from before the rows were loaded or changed is refused"""
+        kind = (getattr(view, "valid_for", None) or (None,))[0]
+        return self._counts_view_to_host(view, (kind, self._rows_gen, self._delta_counts_call.get(kind)),
+                                         "stale delta-count view: the table was replaced by a later call or the graph was loaded or changed")
+
     def edge_counts_to_host(self, view):
         """the device table a refine_sets_edge_counts(..., device=True) call returned, copied to the host as uint64; a view from
         before the latest such call or from before the rows were loaded again is refused: the buffer holds something else by now"""
-        if getattr(view, "owner", None) is not self or getattr(view, "valid_for", None) != (self._rows_gen, self._ecounts_call):
-            raise GnnpeError("stale edge-count view: the table was replaced by a later refine_sets_edge_counts call or the graph was loaded again")
-        nbytes = view.shape[0] * view.shape[1] * 8
-        if nbytes == 0:
-            return np.zeros(view.shape, np.uint64)
-        return self.copy_to_host(view.__cuda_array_interface__["data"][0], nbytes).view(np.uint64).reshape(view.shape)
+        return self._counts_view_to_host(view, (self._rows_gen, self._ecounts_call),
+                                         "stale edge-count view: the table was replaced by a later refine_sets_edge_counts call or the graph was loaded again")
 
     def open_match_cursor(self, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
         """A MatchCursor over the embeddings gnnpe_refine_sets counts (gnnpe_refine_pages_open), or with distinct=True over the ones

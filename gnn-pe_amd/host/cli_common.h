@@ -2,6 +2,7 @@
 // gnnpge_main (GNN-PGE/src/main.cpp mirror).  Both reference programs take the same eight CLI11 flags.
 #pragma once
 
+#include <dlfcn.h>
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
@@ -262,6 +263,26 @@ inline std::string exe_dir()
     const size_t cut = s.rfind('/');
     return cut == std::string::npos ? "" : s.substr(0, cut + 1);
 }
+
+// -m online: libgnnpe_online.so (include/gnnpe_online.h), which lives beside the binary and is never linked against
+inline void *open_online(const char *tool)
+{
+    void *online = dlopen((exe_dir() + "libgnnpe_online.so").c_str(), RTLD_NOW | RTLD_GLOBAL);
+    if (!online) online = dlopen("libgnnpe_online.so", RTLD_NOW | RTLD_GLOBAL);
+    if (!online) die(std::string("-m online needs libgnnpe_online.so beside ") + tool + ": " + dlerror());
+    return online;
+}
+
+// A function of that library, typed from its declaration in the header: ONLINE(gnnpe_refine)(ctx, ...) where `online` is the
+// handle.  A call that does not match the declaration does not compile (dlsym itself checks nothing).
+template <class F>
+F online_sym(void *lib, const char *name)
+{
+    F fn = (F)dlsym(lib, name);
+    if (!fn) die(std::string("libgnnpe_online.so does not export ") + name);
+    return fn;
+}
+#define ONLINE(fn) cli::online_sym<decltype(&fn)>(online, #fn)
 
 // Size of the index.dat a partition of `points` paths becomes, so that the 2 GiB limit above is checked BEFORE anything is
 // written: the library's own figure for the builder that will write the file (gnnpe_index_file_bytes: 0 = the pair-major build

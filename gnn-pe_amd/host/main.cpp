@@ -18,7 +18,6 @@
 //     (SURVEY D4); its online binary cannot read those files.  `-m online|filter -l 3` queries with 4-vertex paths, in exact
 //     mode (the reference has no l = 3 semantics to follow).  Other -l values are refused;
 //   - path counts beyond 2^32-1 are refused unless --allow-large (the reference's `ui` overflows).
-#include <dlfcn.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -35,6 +34,7 @@
 #include <vector>
 
 #include "../../include/gnnpe_hip.h"
+#include "../../include/gnnpe_online.h"  // for the types of its functions only: the library is dlopen()ed (cli_common.h, ONLINE)
 #include "cli_common.h"
 #include "graph_loader.h"
 #include "slab_offline.h"
@@ -155,6 +155,181 @@ struct Device {
     uint64_t total = 0, base = 0;
 };
 
+// the file of --vertex-counts / --delta-vertex-counts: a line `v c_0 .. c_{nq-1}` for every data vertex with a count
+void write_vertex_table(const std::string &path, const StaticGraph &g, uint32_t n_qv, const std::vector<uint64_t> &table)
+{
+    FILE *vf = fopen(path.c_str(), "w");
+    if (!vf) die("cannot write " + path);
+    for (uint32_t v = 0; v < g.n; v++) {
+        bool any = false;
+        for (uint32_t u = 0; u < n_qv && !any; u++) any = table[(size_t)u * g.n + v] != 0;
+        if (!any) continue;
+        fprintf(vf, "%u", v);
+        for (uint32_t u = 0; u < n_qv; u++) fprintf(vf, " %llu", (unsigned long long)table[(size_t)u * g.n + v]);
+        fputc('\n', vf);
+    }
+    if (fclose(vf) != 0) die("write failed on " + path);
+}
+
+// the file of --edge-counts / --delta-edge-counts: the query edges in a `#` line, then a line `x y c_0 .. c_{nqe-1}` for every
+// adjacency entry with a count
+void write_edge_table(const std::string &path, const StaticGraph &g, uint32_t nqe, const std::vector<uint32_t> &qe,
+                      const std::vector<uint64_t> &table)
+{
+    const size_t entries = g.offsets[g.n];
+    FILE *ef = fopen(path.c_str(), "w");
+    if (!ef) die("cannot write " + path);
+    fputc('#', ef);
+    for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %u-%u", qe[2 * k], qe[2 * k + 1]);
+    fputc('\n', ef);
+    // the rows ascend, so the entries in CSR order are ascending by (x, y)
+    for (uint32_t x = 0; x < g.n; x++)
+        for (size_t j = g.offsets[x]; j < g.offsets[x + 1]; j++) {
+            bool any = false;
+            for (uint32_t k = 0; k < nqe && !any; k++) any = table[(size_t)k * entries + j] != 0;
+            if (!any) continue;
+            fprintf(ef, "%u %u", x, g.neighbors[j]);
+            for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %llu", (unsigned long long)table[(size_t)k * entries + j]);
+            fputc('\n', ef);
+        }
+    if (fclose(ef) != 0) die("write failed on " + path);
+}
+
+// F of --delta-edges: one `x y` per line
+std::vector<uint32_t> read_delta_edges(const std::string &path)
+{
+    std::vector<uint32_t> pairs;
+    FILE *df = fopen(path.c_str(), "r");
+    if (!df) die("cannot read " + path);
+    for (unsigned long long x, y;;) {
+        const int got = fscanf(df, "%llu %llu", &x, &y);
+        if (got == EOF) break;
+        if (got != 2 || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull) die(path + ": one `x y` per line expected");
+        pairs.push_back((uint32_t)x);
+        pairs.push_back((uint32_t)y);
+    }
+    fclose(df);
+    return pairs;
+}
+
+// the file of --matches: one match per line, the images of the query vertices in their order
+struct MatchFile {
+    const std::string &path;
+    uint32_t n_qv;
+    FILE *f;
+    MatchFile(const std::string &path_, uint32_t n_qv_) : path(path_), n_qv(n_qv_), f(fopen(path_.c_str(), "w"))
+    {
+        if (!f) die("cannot write " + path);
+    }
+    void write(const std::vector<uint32_t> &rows, uint64_t n_rows)
+    {
+        for (uint64_t k = 0; k < n_rows; k++)
+            for (uint32_t u = 0; u < n_qv; u++) fprintf(f, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
+    }
+    void close()
+    {
+        if (fclose(f) != 0) die("write failed on " + path);
+    }
+};
+
+// -m online, main.cpp:173-181: the refinement on the candidate sets.  On the device, through libgnnpe_online.so: gnnpe_refine,
+// or with --refine sets, where the sets are complete, one of the set-restricted forms, all in the mode of --distinct (every
+// matching subgraph once) and --induced (induced matches only, so that the answer is I or ID):
+//   --all-matches            every match up to -n into --matches, page by page through the match cursor (gnnpe_refine_pages_*)
+//   --vertex-counts FILE     gnnpe_refine_sets_vertex_counts: per data vertex the matches it takes part in, by query vertex
+//   --edge-counts FILE       gnnpe_refine_sets_edge_counts: the same per adjacency entry and query edge
+//   --delta-edges FILE       gnnpe_refine_sets_delta: the matches through the listed data edges, each once; with
+//                            --delta-vertex-counts / --delta-edge-counts FILE gnnpe_refine_sets_delta_vertex_counts / _edge_counts,
+//                            the count tables of those matches
+//   none of these            gnnpe_refine_sets_mode
+// The two one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
+struct Refinement {
+    void *online = nullptr;  // the library's handle
+    uint64_t answers = 0, n_written = 0, n_pages = 0;
+    double refine_ms = 0.0;
+};
+
+Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g, const std::vector<uint32_t> &bitmap, uint32_t n_qv,
+                         uint64_t limit)
+{
+    Refinement r;
+    void *online = r.online = open_online(o.tool);
+    const char *query = o.query_graph.c_str();
+    if (o.refine != "sets") {
+        check(ONLINE(gnnpe_refine)(ctx, query, bitmap.data(), limit, &r.answers, &r.refine_ms), "refine");
+        return r;
+    }
+    const uint32_t match_mode = (o.distinct ? GNNPE_MATCH_DISTINCT : 0u) | (o.induced ? GNNPE_MATCH_INDUCED : 0u);
+    const bool through = !o.delta_edges_file.empty();
+    const struct {
+        const char *flag, *what;
+        const std::string &path;
+        bool edge_table;
+    } tables[] = {{"--vertex-counts", "refine_sets_vertex_counts", o.vertex_counts_file, false},
+                  {"--edge-counts", "refine_sets_edge_counts", o.edge_counts_file, true},
+                  {"--delta-vertex-counts", "refine_sets_delta_vertex_counts", o.delta_vertex_counts_file, false},
+                  {"--delta-edge-counts", "refine_sets_delta_edge_counts", o.delta_edge_counts_file, true}};
+    for (const auto &t : tables) {
+        if (t.path.empty()) continue;
+        uint32_t nqe = 0;
+        std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
+        if (t.edge_table) check(ONLINE(gnnpe_host_query_edges)(query, qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
+        const std::vector<uint32_t> edges = through ? read_delta_edges(o.delta_edges_file) : std::vector<uint32_t>();
+        std::vector<uint64_t> table(t.edge_table ? (size_t)nqe * g.offsets[g.n] : (size_t)n_qv * g.n);
+        int complete = 0;
+        if (through)
+            check((t.edge_table ? ONLINE(gnnpe_refine_sets_delta_edge_counts) : ONLINE(gnnpe_refine_sets_delta_vertex_counts))(
+                      ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers, &complete, table.data(),
+                      nullptr, nullptr, 1, &r.refine_ms), t.what);
+        else
+            check((t.edge_table ? ONLINE(gnnpe_refine_sets_edge_counts) : ONLINE(gnnpe_refine_sets_vertex_counts))(
+                      ctx, query, bitmap.data(), limit, match_mode, &r.answers, &complete, table.data(), nullptr, &r.refine_ms), t.what);
+        if (!complete)
+            die(std::string(t.flag) + ": the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " + t.path +
+                " was not written; raise -n");
+        if (t.edge_table) write_edge_table(t.path, g, nqe, qe, table);
+        else write_vertex_table(t.path, g, n_qv, table);
+        return r;
+    }
+    if (o.all_matches) {  // one page on the host at a time
+        const uint64_t page = std::min<uint64_t>(o.match_page, std::max<uint64_t>(limit, 1));
+        gnnpe_match_cursor *cur = nullptr;
+        check(ONLINE(gnnpe_refine_pages_open_mode)(ctx, query, bitmap.data(), limit, page, match_mode, &cur), "refine_pages_open");
+        const auto pages_next = ONLINE(gnnpe_refine_pages_next);
+        MatchFile mf(o.matches_file, n_qv);
+        std::vector<uint32_t> rows((size_t)page * n_qv);
+        for (int done = 0; !done;) {
+            uint64_t got = 0;
+            double page_ms = 0.0;
+            check(pages_next(cur, rows.data(), &got, &done, &page_ms), "refine_pages_next");
+            mf.write(rows, got);
+            r.answers += got;
+            r.refine_ms += page_ms;
+            r.n_pages++;
+        }
+        ONLINE(gnnpe_refine_pages_close)(cur);
+        mf.close();
+        r.n_written = r.answers;
+        return r;
+    }
+    const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
+    std::vector<uint32_t> rows((size_t)cap * n_qv);
+    if (through) {
+        const std::vector<uint32_t> edges = read_delta_edges(o.delta_edges_file);
+        check(ONLINE(gnnpe_refine_sets_delta)(ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers,
+                                              cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta");
+    } else {
+        check(ONLINE(gnnpe_refine_sets_mode)(ctx, query, bitmap.data(), limit, match_mode, &r.answers, cap ? rows.data() : nullptr, cap,
+                                             &r.refine_ms), "refine_sets");
+    }
+    if (!o.matches_file.empty()) {
+        MatchFile mf(o.matches_file, n_qv);
+        mf.write(rows, r.n_written = std::min(r.answers, cap));
+        mf.close();
+    }
+    return r;
+}
+
 // Exact mode (--exact at -l 2, always at -l 3): the plan of gnnpe_host_query_plan_exact, every path tested in
 // both orientations, so that the refinement counts every embedding.  Same answer line and candidates.bin; --timing adds the plan
 // sizes by path width and the candidate count of every query vertex.
@@ -164,15 +339,8 @@ struct Device {
 // all_paths.txt, no index.dat: only the data graph and membership.txt (any order gives the same candidate sets).
 // Writes <f>gnn-pe/candidates.bin: uint32 n_query_vertices; per query vertex uint32 count + ascending data vertex
 // ids -- the reference's candidate_set, ready for its refinement (main.cpp:176-179).  -m online goes on with the
-// refinement on the device (gnnpe_refine; with --refine sets, where the sets are complete, gnnpe_refine_sets, which can
-// also hand back the embeddings: --matches, at most 2^20 of them, or with --all-matches all of them page by page through
-// the match cursor, gnnpe_refine_pages_*; with --distinct the _distinct forms, which count and write every matching subgraph
-// once, and a second line `Automorphisms: K`; with --induced the _mode forms with GNNPE_MATCH_INDUCED, which count and write induced
-// matches only, so that the answer is I or ID; with --vertex-counts gnnpe_refine_sets_vertex_counts, which writes per data vertex
-// the matches it takes part in by query vertex; with --edge-counts gnnpe_refine_sets_edge_counts, the same per adjacency entry and
-// query edge; with --delta-edges gnnpe_refine_sets_delta, which counts and writes the matches through the listed data edges, each
-// once, or with --delta-vertex-counts / --delta-edge-counts gnnpe_refine_sets_delta_vertex_counts / _edge_counts, which write the
-// count tables of those matches) and prints the reference's answer line instead of writing the file.
+// refinement on the device (refine_online) and prints the reference's answer line instead of writing the file, with --distinct
+// a second line `Automorphisms: K`.
 int run_filter(const Options &o)
 {
     const auto t0 = Clock::now();
@@ -269,229 +437,41 @@ int run_filter(const Options &o)
         exact_json += "], ";
     }
     if (o.mode == "online") {  // main.cpp:173-181: refinement on the candidate sets, then the answer line
-        uint64_t limit = 0xFFFFFFFFull, answers = 0;  // MAX_LIMIT = UINT_MAX (main.cpp:62-69)
+        uint64_t limit = 0xFFFFFFFFull;  // MAX_LIMIT = UINT_MAX (main.cpp:62-69)
         if (o.answers != "MAX") {
             uint32_t lim;
             if (!parse_u32(o.answers, &lim)) die("-n must be MAX or an integer");
             limit = lim;
         }
-        double refine_ms = 0.0;
-        // the refinement lives in libgnnpe_online.so (include/gnnpe_online.h: out of scope, frozen), beside this binary
-        typedef int (*refine_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t *, double *);
-        void *online = dlopen((exe_dir() + "libgnnpe_online.so").c_str(), RTLD_NOW | RTLD_GLOBAL);
-        if (!online) online = dlopen("libgnnpe_online.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!online) die(std::string("-m online needs libgnnpe_online.so beside ") + o.tool + ": " + dlerror());
-        refine_fn refine = (refine_fn)dlsym(online, "gnnpe_refine");
-        if (!refine) die("libgnnpe_online.so does not export gnnpe_refine");
+        const Refinement r = refine_online(o, ctx, g, bitmap, n_qv, limit);
         const bool sets = o.refine == "sets";
-        const uint32_t match_mode = (o.distinct ? 1u /* GNNPE_MATCH_DISTINCT */ : 0u) | (o.induced ? 2u /* GNNPE_MATCH_INDUCED */ : 0u);
-        uint64_t n_written = 0;
-        uint64_t n_pages = 0;
-        // the files of --vertex-counts / --delta-vertex-counts and of --edge-counts / --delta-edge-counts, and F of --delta-edges
-        auto write_vertex_table = [&](const std::string &path, const std::vector<uint64_t> &table) {
-            FILE *vf = fopen(path.c_str(), "w");
-            if (!vf) die("cannot write " + path);
-            for (uint32_t v = 0; v < g.n; v++) {
-                bool any = false;
-                for (uint32_t u = 0; u < n_qv && !any; u++) any = table[(size_t)u * g.n + v] != 0;
-                if (!any) continue;
-                fprintf(vf, "%u", v);
-                for (uint32_t u = 0; u < n_qv; u++) fprintf(vf, " %llu", (unsigned long long)table[(size_t)u * g.n + v]);
-                fputc('\n', vf);
-            }
-            if (fclose(vf) != 0) die("write failed on " + path);
-        };
-        auto write_edge_table = [&](const std::string &path, uint32_t nqe, const std::vector<uint32_t> &qe, const std::vector<uint64_t> &table) {
-            const size_t entries = g.offsets[g.n];
-            FILE *ef = fopen(path.c_str(), "w");
-            if (!ef) die("cannot write " + path);
-            fputc('#', ef);
-            for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %u-%u", qe[2 * k], qe[2 * k + 1]);
-            fputc('\n', ef);
-            // the rows ascend, so the entries in CSR order are ascending by (x, y)
-            for (uint32_t x = 0; x < g.n; x++)
-                for (size_t j = g.offsets[x]; j < g.offsets[x + 1]; j++) {
-                    bool any = false;
-                    for (uint32_t k = 0; k < nqe && !any; k++) any = table[(size_t)k * entries + j] != 0;
-                    if (!any) continue;
-                    fprintf(ef, "%u %u", x, g.neighbors[j]);
-                    for (uint32_t k = 0; k < nqe; k++) fprintf(ef, " %llu", (unsigned long long)table[(size_t)k * entries + j]);
-                    fputc('\n', ef);
-                }
-            if (fclose(ef) != 0) die("write failed on " + path);
-        };
-        auto read_delta_edges = [&]() -> std::vector<uint32_t> {
-            std::vector<uint32_t> pairs;
-            FILE *df = fopen(o.delta_edges_file.c_str(), "r");
-            if (!df) die("cannot read " + o.delta_edges_file);
-            for (unsigned long long x, y;;) {
-                const int got = fscanf(df, "%llu %llu", &x, &y);
-                if (got == EOF) break;
-                if (got != 2 || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull) die(o.delta_edges_file + ": one `x y` per line expected");
-                pairs.push_back((uint32_t)x);
-                pairs.push_back((uint32_t)y);
-            }
-            fclose(df);
-            return pairs;
-        };
-        typedef int (*qedges_fn)(const char *, uint32_t *, uint32_t, uint32_t *);
-        if (sets && o.all_matches) {
-            // every embedding up to -n through the match cursor (gnnpe_refine_pages_*): one page on the host at a time
-            typedef struct gnnpe_match_cursor cursor_t;
-            typedef int (*open_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t, uint32_t, cursor_t **);
-            typedef int (*next_fn)(cursor_t *, uint32_t *, uint64_t *, int *, double *);
-            typedef void (*close_fn)(cursor_t *);
-            open_fn pages_open = (open_fn)dlsym(online, "gnnpe_refine_pages_open_mode");
-            next_fn pages_next = (next_fn)dlsym(online, "gnnpe_refine_pages_next");
-            close_fn pages_close = (close_fn)dlsym(online, "gnnpe_refine_pages_close");
-            if (!pages_open || !pages_next || !pages_close) die("libgnnpe_online.so does not export gnnpe_refine_pages_*");
-            const uint64_t page = std::min<uint64_t>(o.match_page, std::max<uint64_t>(limit, 1));
-            cursor_t *cur = nullptr;
-            check(pages_open(ctx, o.query_graph.c_str(), bitmap.data(), limit, page, match_mode, &cur), "refine_pages_open");
-            FILE *mf = fopen(o.matches_file.c_str(), "w");
-            if (!mf) die("cannot write " + o.matches_file);
-            std::vector<uint32_t> rows((size_t)page * n_qv);
-            for (int done = 0; !done;) {
-                uint64_t got = 0;
-                double page_ms = 0.0;
-                check(pages_next(cur, rows.data(), &got, &done, &page_ms), "refine_pages_next");
-                for (uint64_t k = 0; k < got; k++)
-                    for (uint32_t u = 0; u < n_qv; u++)
-                        fprintf(mf, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
-                answers += got;
-                refine_ms += page_ms;
-                n_pages++;
-            }
-            pages_close(cur);
-            if (fclose(mf) != 0) die("write failed on " + o.matches_file);
-            n_written = answers;
-        } else if (sets && !o.vertex_counts_file.empty()) {
-            // per-vertex match counts (gnnpe_refine_sets_vertex_counts): -n is a guard, the table is exact only below it
-            typedef int (*vcounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, int *, uint64_t *,
-                                      void **, double *);
-            vcounts_fn vcounts = (vcounts_fn)dlsym(online, "gnnpe_refine_sets_vertex_counts");
-            if (!vcounts) die("libgnnpe_online.so does not export gnnpe_refine_sets_vertex_counts");
-            std::vector<uint64_t> table((size_t)n_qv * g.n);
-            int complete = 0;
-            check(vcounts(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, &complete, table.data(), nullptr,
-                          &refine_ms), "refine_sets_vertex_counts");
-            if (!complete)
-                die("--vertex-counts: the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " +
-                    o.vertex_counts_file + " was not written; raise -n");
-            write_vertex_table(o.vertex_counts_file, table);
-        } else if (sets && !o.edge_counts_file.empty()) {
-            // per-edge match counts (gnnpe_refine_sets_edge_counts): -n is a guard, the table is exact only below it
-            typedef int (*ecounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, int *, uint64_t *,
-                                      void **, double *);
-            ecounts_fn ecounts = (ecounts_fn)dlsym(online, "gnnpe_refine_sets_edge_counts");
-            qedges_fn qedges = (qedges_fn)dlsym(online, "gnnpe_host_query_edges");
-            if (!ecounts || !qedges) die("libgnnpe_online.so does not export gnnpe_refine_sets_edge_counts");
-            uint32_t nqe = 0;
-            std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
-            check(qedges(o.query_graph.c_str(), qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
-            std::vector<uint64_t> table((size_t)nqe * g.offsets[g.n]);
-            int complete = 0;
-            check(ecounts(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, &complete, table.data(), nullptr,
-                          &refine_ms), "refine_sets_edge_counts");
-            if (!complete)
-                die("--edge-counts: the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " +
-                    o.edge_counts_file + " was not written; raise -n");
-            write_edge_table(o.edge_counts_file, nqe, qe, table);
-        } else if (sets && (!o.delta_vertex_counts_file.empty() || !o.delta_edge_counts_file.empty())) {
-            // the count tables of the matches through the data edges of --delta-edges (gnnpe_refine_sets_delta_vertex_counts /
-            // _edge_counts): -n is a guard as for --vertex-counts, the files are those of --vertex-counts / --edge-counts
-            typedef int (*dcounts_fn)(gnnpe_ctx *, const char *, const uint32_t *, const uint32_t *, uint64_t, uint64_t, uint32_t, uint64_t *,
-                                      int *, uint64_t *, void **, void *, int, double *);
-            const bool edge_table = !o.delta_edge_counts_file.empty();
-            const std::string flag = edge_table ? "--delta-edge-counts" : "--delta-vertex-counts";
-            const std::string &path = edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file;
-            const char *name = edge_table ? "gnnpe_refine_sets_delta_edge_counts" : "gnnpe_refine_sets_delta_vertex_counts";
-            dcounts_fn dcounts = (dcounts_fn)dlsym(online, name);
-            qedges_fn qedges = (qedges_fn)dlsym(online, "gnnpe_host_query_edges");
-            if (!dcounts || !qedges) die(std::string("libgnnpe_online.so does not export ") + name);
-            uint32_t nqe = 0;
-            std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
-            check(qedges(o.query_graph.c_str(), qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
-            const std::vector<uint32_t> edges = read_delta_edges();
-            std::vector<uint64_t> table(edge_table ? (size_t)nqe * g.offsets[g.n] : (size_t)n_qv * g.n);
-            int complete = 0;
-            check(dcounts(ctx, o.query_graph.c_str(), bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &answers, &complete,
-                          table.data(), nullptr, nullptr, 1, &refine_ms), name + 6);
-            if (!complete)
-                die(flag + ": the matches reached -n " + std::to_string(limit) + ", so the table is not complete and " + path +
-                    " was not written; raise -n");
-            if (edge_table) write_edge_table(path, nqe, qe, table);
-            else write_vertex_table(path, table);
-        } else if (sets && !o.delta_edges_file.empty()) {
-            // the matches through the data edges of FILE, each once (gnnpe_refine_sets_delta); --matches as below
-            typedef int (*delta_fn)(gnnpe_ctx *, const char *, const uint32_t *, const uint32_t *, uint64_t, uint64_t, uint32_t, uint64_t *,
-                                    uint32_t *, uint64_t, double *);
-            delta_fn delta = (delta_fn)dlsym(online, "gnnpe_refine_sets_delta");
-            if (!delta) die("libgnnpe_online.so does not export gnnpe_refine_sets_delta");
-            const std::vector<uint32_t> edges = read_delta_edges();
-            const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
-            std::vector<uint32_t> rows((size_t)cap * n_qv);
-            check(delta(ctx, o.query_graph.c_str(), bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &answers,
-                        cap ? rows.data() : nullptr, cap, &refine_ms), "refine_sets_delta");
-            if (!o.matches_file.empty()) {
-                FILE *mf = fopen(o.matches_file.c_str(), "w");
-                if (!mf) die("cannot write " + o.matches_file);
-                n_written = std::min(answers, cap);
-                for (uint64_t k = 0; k < n_written; k++)
-                    for (uint32_t u = 0; u < n_qv; u++)
-                        fprintf(mf, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
-                if (fclose(mf) != 0) die("write failed on " + o.matches_file);
-            }
-        } else if (sets) {
-            // the set-restricted refinement (gnnpe_refine_sets); --matches: at most min(-n, 2^20) embeddings, one per line
-            typedef int (*refine_sets_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint32_t, uint64_t *, uint32_t *,
-                                          uint64_t, double *);
-            refine_sets_fn refine_sets = (refine_sets_fn)dlsym(online, "gnnpe_refine_sets_mode");
-            if (!refine_sets) die("libgnnpe_online.so does not export gnnpe_refine_sets_mode");
-            const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
-            std::vector<uint32_t> rows((size_t)cap * n_qv);
-            check(refine_sets(ctx, o.query_graph.c_str(), bitmap.data(), limit, match_mode, &answers, cap ? rows.data() : nullptr, cap,
-                              &refine_ms), "refine_sets");
-            if (!o.matches_file.empty()) {
-                FILE *mf = fopen(o.matches_file.c_str(), "w");
-                if (!mf) die("cannot write " + o.matches_file);
-                n_written = std::min(answers, cap);
-                for (uint64_t k = 0; k < n_written; k++)
-                    for (uint32_t u = 0; u < n_qv; u++)
-                        fprintf(mf, "%u%c", rows[(size_t)k * n_qv + u], u + 1 == n_qv ? '\n' : ' ');
-                if (fclose(mf) != 0) die("write failed on " + o.matches_file);
-            }
-        } else {
-            check(refine(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, &refine_ms), "refine");
-        }
         gnnpe_destroy(ctx);
-        printf("Answer Number: %llu Query Time (ms): %g\n", (unsigned long long)answers, ms + refine_ms);
+        printf("Answer Number: %llu Query Time (ms): %g\n", (unsigned long long)r.answers, ms + r.refine_ms);
         if (o.distinct) {
             // the answer is the number of distinct subgraphs; times the automorphisms it is the number of embeddings
-            typedef int (*symmetry_fn)(const char *, uint64_t *, uint32_t *, uint32_t, uint32_t *);
-            symmetry_fn symmetry = (symmetry_fn)dlsym(online, "gnnpe_host_query_symmetry");
-            if (!symmetry) die("libgnnpe_online.so does not export gnnpe_host_query_symmetry");
+            void *online = r.online;
             uint64_t aut = 0;
             std::vector<uint32_t> pairs((size_t)n_qv * n_qv);
             uint32_t n_pairs = 0;
-            check(symmetry(o.query_graph.c_str(), &aut, pairs.data(), (uint32_t)(pairs.size() / 2), &n_pairs), "query_symmetry");
+            check(ONLINE(gnnpe_host_query_symmetry)(o.query_graph.c_str(), &aut, pairs.data(), (uint32_t)(pairs.size() / 2), &n_pairs),
+                  "query_symmetry");
             printf("Automorphisms: %llu\n", (unsigned long long)aut);
         }
         if (o.induced) exact_json += "\"induced\": true, ";
         if (o.timing && sets && o.all_matches)
             fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"match_pages\": %llu, \"paths\": %llu, "
                             "\"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
-                    exact_json.c_str(), (unsigned long long)n_written, (unsigned long long)n_pages, (unsigned long long)P, n_qp, ms,
-                    refine_ms, secs(t0, Clock::now()));
+                    exact_json.c_str(), (unsigned long long)r.n_written, (unsigned long long)r.n_pages, (unsigned long long)P, n_qp, ms,
+                    r.refine_ms, secs(t0, Clock::now()));
         else if (o.timing && sets)
             fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"paths\": %llu, \"query_paths\": %u, "
                             "\"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
-                    exact_json.c_str(), (unsigned long long)n_written, (unsigned long long)P, n_qp, ms, refine_ms,
+                    exact_json.c_str(), (unsigned long long)r.n_written, (unsigned long long)P, n_qp, ms, r.refine_ms,
                     secs(t0, Clock::now()));
         else if (o.timing)
             fprintf(stderr, "{%s\"paths\": %llu, \"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, "
                             "\"end_to_end_s\": %.3f}\n",
-                    exact_json.c_str(), (unsigned long long)P, n_qp, ms, refine_ms, secs(t0, Clock::now()));
+                    exact_json.c_str(), (unsigned long long)P, n_qp, ms, r.refine_ms, secs(t0, Clock::now()));
         gnnpe_host_free(qv);
         gnnpe_host_free(ql);
         gnnpe_host_free(qd);

@@ -17,11 +17,10 @@
 // reference's answer line.  Unlike the reference it writes nothing: a missing partitions/partition-i/index.dat is not
 // built as a side effect, and no index.dat is read.  -m filter stops after the filter and writes
 // <f>gnn-pge/candidates.bin (the format of gnnpe_main's <f>gnn-pe/candidates.bin).
-#include <dlfcn.h>
-
 #include <string>
 #include <vector>
 
+#include "../../include/gnnpe_online.h"  // for the type of gnnpe_refine only: the library is dlopen()ed (cli_common.h, ONLINE)
 #include "cli_common.h"
 #include "graph_loader.h"
 
@@ -132,13 +131,8 @@ int run_online(const Options &o)
         uint64_t answers = 0;
         double refine_ms = 0.0;
         // the refinement lives in libgnnpe_online.so beside this binary (include/gnnpe_online.h), as for gnnpe_main -m online
-        typedef int (*refine_fn)(gnnpe_ctx *, const char *, const uint32_t *, uint64_t, uint64_t *, double *);
-        void *online = dlopen((exe_dir() + "libgnnpe_online.so").c_str(), RTLD_NOW | RTLD_GLOBAL);
-        if (!online) online = dlopen("libgnnpe_online.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!online) die(std::string("-m online needs libgnnpe_online.so beside ") + o.tool + ": " + dlerror());
-        refine_fn refine = (refine_fn)dlsym(online, "gnnpe_refine");
-        if (!refine) die("libgnnpe_online.so does not export gnnpe_refine");
-        check(refine(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, &refine_ms), "refine");
+        void *online = open_online(o.tool);
+        check(ONLINE(gnnpe_refine)(ctx, o.query_graph.c_str(), bitmap.data(), limit, &answers, &refine_ms), "refine");
         gnnpe_destroy(ctx);
         printf("Answer Num: %llu Query Time (ms): %g\n", (unsigned long long)answers, plan_ms + ms + refine_ms);
         if (o.timing)

@@ -59,185 +59,101 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
     return 0;
 }
 
-// gnnpe_host_refine_sets (mode 0), gnnpe_host_refine_sets_distinct (GNNPE_MATCH_DISTINCT) and gnnpe_host_refine_sets_mode
-static int host_refine_sets(const char *who, uint32_t mode, uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
-                            const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit,
-                            uint64_t *answers)
+// The eight host entries of the set-restricted refinement are this one sequence: null checks, outputs cleared, unknown mode
+// bits, query load, the search (gnnpe_host::refine_sets_run), its refusal as the error text.  An entry is its name, its table kind
+// and whether it has F (`through`); what differs between them follows from those two:
+//   null checks   offsets, nbrs, labels, query_graph_path, candidate_bitmap and answers always; complete with a table; counts with
+//                 the vertex table only -- the edge table of a query without an edge is empty, so the search looks at counts once
+//                 the query is known; delta_edges unless n_delta is 0
+//   cleared       before the mode check *answers = 0 and *complete = 0 -- but not by the three entries with neither table nor F,
+//                 which leave *answers alone until the search starts
+//   refusal text  the search's own; with F behind "<who>: ".  A query that does not load returns the loader's code and text as
+//                 they are, in all eight.  *answers is 0 after a refusal of the search.
+// mode 0 and GNNPE_MATCH_DISTINCT are what gnnpe_host_refine_sets and gnnpe_host_refine_sets_distinct pass.
+static int host_sets(const char *who, gnnpe_host::SetsJob::Table table, bool through, uint32_t n, const uint32_t *offsets,
+                     const uint32_t *nbrs, const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                     const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers, int *complete,
+                     uint64_t *counts)
 {
-    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers) {
+    const bool has_table = table != gnnpe_host::SetsJob::kNoTable;
+    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || (has_table && !complete) ||
+        (table == gnnpe_host::SetsJob::kVertexTable && !counts) || (!delta_edges && n_delta)) {
         gnnpe::set_error("%s: null argument", who);
         return GNNPE_ERR_ARG;
     }
+    if (has_table || through) *answers = 0;
+    if (has_table) *complete = 0;
     if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
         gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
         return GNNPE_ERR_ARG;
     }
-    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
     gnnpe_host::StaticGraph q;
-    std::string err;
     if (int rc = load_query(query_graph_path, &q)) return rc;
     const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
     gnnpe_host::QuerySymmetry sym;
-    if (distinct) sym = gnnpe_host::query_symmetry(q);
-    if (gnnpe_host::refine_sets_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &err,
-                                      distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
-        gnnpe::set_error("%s", err.c_str());
+    gnnpe_host::SetsJob job;
+    if (mode & GNNPE_MATCH_DISTINCT) {
+        sym = gnnpe_host::query_symmetry(q);
+        job.pairs = &sym.pairs;
+    }
+    job.induced = (mode & GNNPE_MATCH_INDUCED) != 0;
+    job.table = table;
+    job.through = through;
+    job.delta_edges = delta_edges;
+    job.n_delta = n_delta;
+    std::string err;
+    bool done = false;
+    if (gnnpe_host::refine_sets_run(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, job, answers, &done, counts, &err) != 0) {
+        if (through) gnnpe::set_error("%s: %s", who, err.c_str());
+        else gnnpe::set_error("%s", err.c_str());
         return GNNPE_ERR_ARG;
     }
+    if (has_table) *complete = done ? 1 : 0;
     return 0;
 }
+
+#define HOST_SETS(entry, table, through, delta_edges, n_delta, mode, complete, counts)                                              \
+    host_sets(#entry, gnnpe_host::SetsJob::table, through, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, delta_edges, \
+              n_delta, limit, mode, answers, complete, counts)
 
 int gnnpe_host_refine_sets(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                            const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
 {
-    return host_refine_sets("gnnpe_host_refine_sets", 0u, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit, answers);
+    return HOST_SETS(gnnpe_host_refine_sets, kNoTable, false, nullptr, 0, 0u, nullptr, nullptr);
 }
 
 int gnnpe_host_refine_sets_distinct(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                     const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint64_t *answers)
 {
-    return host_refine_sets("gnnpe_host_refine_sets_distinct", GNNPE_MATCH_DISTINCT, n, offsets, nbrs, labels, query_graph_path,
-                            candidate_bitmap, limit, answers);
+    return HOST_SETS(gnnpe_host_refine_sets_distinct, kNoTable, false, nullptr, 0, GNNPE_MATCH_DISTINCT, nullptr, nullptr);
 }
 
 int gnnpe_host_refine_sets_mode(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                 const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
                                 uint64_t *answers)
 {
-    return host_refine_sets("gnnpe_host_refine_sets_mode", mode, n, offsets, nbrs, labels, query_graph_path, candidate_bitmap, limit,
-                            answers);
+    return HOST_SETS(gnnpe_host_refine_sets_mode, kNoTable, false, nullptr, 0, mode, nullptr, nullptr);
 }
 
 int gnnpe_host_refine_sets_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                          const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
                                          uint64_t *answers, int *complete, uint64_t *counts)
 {
-    const char *who = "gnnpe_host_refine_sets_vertex_counts";
-    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || !complete || !counts) {
-        gnnpe::set_error("%s: null argument", who);
-        return GNNPE_ERR_ARG;
-    }
-    *answers = 0;
-    *complete = 0;
-    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
-        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
-        return GNNPE_ERR_ARG;
-    }
-    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
-    gnnpe_host::StaticGraph q;
-    std::string err;
-    if (int rc = load_query(query_graph_path, &q)) return rc;
-    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
-    gnnpe_host::QuerySymmetry sym;
-    if (distinct) sym = gnnpe_host::query_symmetry(q);
-    bool done = false;
-    if (gnnpe_host::refine_sets_vertex_counts(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &done, counts, &err,
-                                              distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
-        gnnpe::set_error("%s", err.c_str());
-        return GNNPE_ERR_ARG;
-    }
-    *complete = done ? 1 : 0;
-    return 0;
+    return HOST_SETS(gnnpe_host_refine_sets_vertex_counts, kVertexTable, false, nullptr, 0, mode, complete, counts);
 }
 
 int gnnpe_host_refine_sets_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                        const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
                                        uint64_t *answers, int *complete, uint64_t *counts)
 {
-    const char *who = "gnnpe_host_refine_sets_edge_counts";
-    // (counts may be null where the table is empty: refine_sets_edge_counts looks at it once the query is known)
-    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || !complete) {
-        gnnpe::set_error("%s: null argument", who);
-        return GNNPE_ERR_ARG;
-    }
-    *answers = 0;
-    *complete = 0;
-    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
-        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
-        return GNNPE_ERR_ARG;
-    }
-    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
-    gnnpe_host::StaticGraph q;
-    std::string err;
-    if (int rc = load_query(query_graph_path, &q)) return rc;
-    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
-    gnnpe_host::QuerySymmetry sym;
-    if (distinct) sym = gnnpe_host::query_symmetry(q);
-    bool done = false;
-    if (gnnpe_host::refine_sets_edge_counts(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, answers, &done, counts, &err,
-                                            distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
-        gnnpe::set_error("%s", err.c_str());
-        return GNNPE_ERR_ARG;
-    }
-    *complete = done ? 1 : 0;
-    return 0;
+    return HOST_SETS(gnnpe_host_refine_sets_edge_counts, kEdgeTable, false, nullptr, 0, mode, complete, counts);
 }
 
 int gnnpe_host_refine_sets_delta(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                  const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *delta_edges,
                                  uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers)
 {
-    const char *who = "gnnpe_host_refine_sets_delta";
-    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || (!delta_edges && n_delta)) {
-        gnnpe::set_error("%s: null argument", who);
-        return GNNPE_ERR_ARG;
-    }
-    *answers = 0;
-    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
-        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
-        return GNNPE_ERR_ARG;
-    }
-    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0;
-    gnnpe_host::StaticGraph q;
-    std::string err;
-    if (int rc = load_query(query_graph_path, &q)) return rc;
-    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
-    gnnpe_host::QuerySymmetry sym;
-    if (distinct) sym = gnnpe_host::query_symmetry(q);
-    if (gnnpe_host::refine_sets_delta_count(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, delta_edges, n_delta, limit, answers, &err,
-                                            distinct ? &sym.pairs : nullptr, (mode & GNNPE_MATCH_INDUCED) != 0) != 0) {
-        *answers = 0;
-        gnnpe::set_error("%s: %s", who, err.c_str());
-        return GNNPE_ERR_ARG;
-    }
-    return 0;
-}
-
-// gnnpe_host_refine_sets_delta_vertex_counts and gnnpe_host_refine_sets_delta_edge_counts
-// (counts may be null where the edge table is empty: refine_sets_delta_edge_counts looks at it once the query is known)
-static int host_delta_table(const char *who, bool edge_table, uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
-                            const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap,
-                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers, int *complete,
-                            uint64_t *counts)
-{
-    if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || !complete || (!counts && !edge_table) ||
-        (!delta_edges && n_delta)) {
-        gnnpe::set_error("%s: null argument", who);
-        return GNNPE_ERR_ARG;
-    }
-    *answers = 0;
-    *complete = 0;
-    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
-        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
-        return GNNPE_ERR_ARG;
-    }
-    const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0, induced = (mode & GNNPE_MATCH_INDUCED) != 0;
-    gnnpe_host::StaticGraph q;
-    std::string err;
-    if (int rc = load_query(query_graph_path, &q)) return rc;
-    const gnnpe_host::StaticGraph g = graph_from_csr(n, offsets, nbrs, labels);
-    gnnpe_host::QuerySymmetry sym;
-    if (distinct) sym = gnnpe_host::query_symmetry(q);
-    bool done = false;
-    const auto fn = edge_table ? gnnpe_host::refine_sets_delta_edge_counts : gnnpe_host::refine_sets_delta_vertex_counts;
-    if (fn(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, delta_edges, n_delta, limit, answers, &done, counts, &err,
-           distinct ? &sym.pairs : nullptr, induced) != 0) {
-        *answers = 0;
-        gnnpe::set_error("%s: %s", who, err.c_str());
-        return GNNPE_ERR_ARG;
-    }
-    *complete = done ? 1 : 0;
-    return 0;
+    return HOST_SETS(gnnpe_host_refine_sets_delta, kNoTable, true, delta_edges, n_delta, mode, nullptr, nullptr);
 }
 
 int gnnpe_host_refine_sets_delta_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
@@ -245,8 +161,7 @@ int gnnpe_host_refine_sets_delta_vertex_counts(uint32_t n, const uint32_t *offse
                                                const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
                                                uint64_t *answers, int *complete, uint64_t *counts)
 {
-    return host_delta_table("gnnpe_host_refine_sets_delta_vertex_counts", false, n, offsets, nbrs, labels, query_graph_path,
-                            candidate_bitmap, delta_edges, n_delta, limit, mode, answers, complete, counts);
+    return HOST_SETS(gnnpe_host_refine_sets_delta_vertex_counts, kVertexTable, true, delta_edges, n_delta, mode, complete, counts);
 }
 
 int gnnpe_host_refine_sets_delta_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
@@ -254,9 +169,9 @@ int gnnpe_host_refine_sets_delta_edge_counts(uint32_t n, const uint32_t *offsets
                                              const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
                                              uint64_t *answers, int *complete, uint64_t *counts)
 {
-    return host_delta_table("gnnpe_host_refine_sets_delta_edge_counts", true, n, offsets, nbrs, labels, query_graph_path,
-                            candidate_bitmap, delta_edges, n_delta, limit, mode, answers, complete, counts);
+    return HOST_SETS(gnnpe_host_refine_sets_delta_edge_counts, kEdgeTable, true, delta_edges, n_delta, mode, complete, counts);
 }
+#undef HOST_SETS
 
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
 {

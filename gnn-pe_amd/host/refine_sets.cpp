@@ -87,14 +87,14 @@ struct SetSearch {
 
 }  // namespace
 
-// refine_sets_count (no table), refine_sets_vertex_counts and refine_sets_edge_counts: one search, a table is filled at the finds;
-// refine_sets_delta_count: the same search, a find that touches no edge of `delta` is dropped; refine_sets_delta_vertex_counts and
-// refine_sets_delta_edge_counts: both at once, the table is filled at the finds that are kept
-static int refine_sets_search(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
-                              uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced,
-                              uint64_t *vcounts, uint64_t *ecounts = nullptr, const std::vector<uint64_t> *delta = nullptr)
+// The walk of refine_sets_run: a table (of job.table's kind, zeroed) is filled at the finds; a find that touches no edge of
+// `delta` (F as ascending keys) is dropped
+static int refine_sets_walk(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
+                            const SetsJob &job, uint64_t *table, const std::vector<uint64_t> *delta, uint64_t *answers, std::string *err)
 {
     const uint32_t nq = query.n;
+    const auto *pairs = job.pairs;
+    uint64_t *vcounts = job.table == SetsJob::kVertexTable ? table : nullptr, *ecounts = job.table == SetsJob::kEdgeTable ? table : nullptr;
     if (!answers || !bitmap || words != ((uint64_t)data.n + 31) / 32) {
         if (err) *err = "refine_sets_count: one bitmap row of ceil(n / 32) words per query vertex expected";
         return -2;
@@ -110,7 +110,7 @@ static int refine_sets_search(const StaticGraph &data, const StaticGraph &query,
                 ecounts || delta ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>(), delta};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
     // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
-    for (uint32_t i = 1; induced && i < nq; i++)
+    for (uint32_t i = 1; job.induced && i < nq; i++)
         for (uint32_t j = 0; j < i; j++) {
             const uint32_t w = mo.order[j];
             if (w != mo.pivot[i] && std::find(s.back[i].begin(), s.back[i].end(), w) == s.back[i].end()) s.non[i].push_back(w);
@@ -141,29 +141,6 @@ static int refine_sets_search(const StaticGraph &data, const StaticGraph &query,
     return 0;
 }
 
-int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                      uint64_t limit, uint64_t *answers, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
-                      bool induced)
-{
-    return refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, nullptr);
-}
-
-int refine_sets_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                              uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
-                              const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
-{
-    if (!complete || !counts) {
-        if (err) *err = "refine_sets_vertex_counts: null argument";
-        return -2;
-    }
-    *complete = false;
-    std::fill(counts, counts + (size_t)query.n * data.n, 0ull);
-    const int rc = refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, counts);
-    // the search stops at `limit` finds: below it, it walked everything (limit 0 walks nothing, and 0 < 0 is false)
-    if (rc == 0) *complete = *answers < limit;
-    return rc;
-}
-
 std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query)
 {
     std::vector<std::pair<uint32_t, uint32_t>> out;
@@ -175,20 +152,11 @@ std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query)
     return out;
 }
 
-int refine_sets_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                            uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
-                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+size_t sets_table_cells(const StaticGraph &data, const StaticGraph &query, SetsJob::Table table)
 {
-    const size_t cells = query_edges(query).size() * (size_t)(data.n ? data.offsets[data.n] : 0);
-    if (!complete || (!counts && cells)) {
-        if (err) *err = "refine_sets_edge_counts: null argument";
-        return -2;
-    }
-    *complete = false;
-    if (cells) std::fill(counts, counts + cells, 0ull);
-    const int rc = refine_sets_search(data, query, bitmap, words, limit, answers, err, pairs, induced, nullptr, cells ? counts : nullptr);
-    if (rc == 0) *complete = *answers < limit;  // as in refine_sets_vertex_counts
-    return rc;
+    if (table == SetsJob::kVertexTable) return (size_t)query.n * data.n;
+    if (table == SetsJob::kEdgeTable) return query_edges(query).size() * (size_t)(data.n ? data.offsets[data.n] : 0);
+    return 0;
 }
 
 int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys, std::string *err)
@@ -212,7 +180,7 @@ int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, s
     return 0;
 }
 
-// F as ascending keys, each a checked edge of the graph: what the three delta forms refuse
+// F as ascending keys, each a checked edge of the graph: what a job through F refuses
 static int delta_keys_checked(const StaticGraph &data, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys,
                               std::string *err)
 {
@@ -227,57 +195,28 @@ static int delta_keys_checked(const StaticGraph &data, const uint32_t *delta_edg
     return 0;
 }
 
-int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
-                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
+int refine_sets_run(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
+                    const SetsJob &job, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err)
 {
+    const size_t cells = sets_table_cells(data, query, job.table);
     if (answers) *answers = 0;
-    std::vector<uint64_t> keys;
-    if (delta_keys_checked(data, delta_edges, n_delta, &keys, err) != 0) return -2;
-    // (an empty F drops every find; the walk still refuses what refine_sets_count refuses)
-    return refine_sets_search(data, query, bitmap, words, keys.empty() ? 0 : limit, answers, err, pairs, induced, nullptr, nullptr, &keys);
-}
-
-// refine_sets_delta_vertex_counts (edge_table false) and refine_sets_delta_edge_counts (true): the search of refine_sets_delta_count
-// with the table of refine_sets_vertex_counts / refine_sets_edge_counts filled at the finds that are kept
-static int refine_sets_delta_table(bool edge_table, const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap,
-                                   uint64_t words, const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers,
-                                   bool *complete, uint64_t *counts, std::string *err,
-                                   const std::vector<std::pair<uint32_t, uint32_t>> *pairs, bool induced)
-{
-    const size_t cells = edge_table ? query_edges(query).size() * (size_t)(data.n ? data.offsets[data.n] : 0) : (size_t)query.n * data.n;
-    if (answers) *answers = 0;
-    if (!complete || (!counts && cells)) {
-        if (err) *err = "refine_sets_delta counts: null argument";
+    if (job.table != SetsJob::kNoTable && (!complete || (!counts && cells))) {
+        // (the texts name the three forms this entry had once: callers show them)
+        if (err) *err = job.through ? "refine_sets_delta counts: null argument"
+                        : job.table == SetsJob::kVertexTable ? "refine_sets_vertex_counts: null argument"
+                                                             : "refine_sets_edge_counts: null argument";
         return -2;
     }
-    *complete = false;
+    if (complete) *complete = false;
     std::vector<uint64_t> keys;
-    if (delta_keys_checked(data, delta_edges, n_delta, &keys, err) != 0) return -2;
+    if (job.through && delta_keys_checked(data, job.delta_edges, job.n_delta, &keys, err) != 0) return -2;
     if (cells) std::fill(counts, counts + cells, 0ull);
-    uint64_t *table = cells ? counts : nullptr;
-    const int rc = refine_sets_search(data, query, bitmap, words, keys.empty() ? 0 : limit, answers, err, pairs, induced,
-                                      edge_table ? nullptr : table, edge_table ? table : nullptr, &keys);
-    if (rc == 0) *complete = *answers < limit;  // as in refine_sets_vertex_counts, with Delta in the place of |M|; no F: 0 < limit
+    // (an empty F drops every find: limit 0, and the walk still refuses what it refuses)
+    const int rc = refine_sets_walk(data, query, bitmap, words, job.through && keys.empty() ? 0 : limit, job, cells ? counts : nullptr,
+                                    job.through ? &keys : nullptr, answers, err);
+    // the walk stops at `limit` finds: below it, it walked everything (limit 0 walks nothing, and 0 < 0 is false; no F: 0 < limit)
+    if (rc == 0 && complete) *complete = *answers < limit;
     return rc;
-}
-
-int refine_sets_delta_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                                    const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
-                                    uint64_t *counts, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
-                                    bool induced)
-{
-    return refine_sets_delta_table(false, data, query, bitmap, words, delta_edges, n_delta, limit, answers, complete, counts, err, pairs,
-                                   induced);
-}
-
-int refine_sets_delta_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                                  const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
-                                  uint64_t *counts, std::string *err, const std::vector<std::pair<uint32_t, uint32_t>> *pairs,
-                                  bool induced)
-{
-    return refine_sets_delta_table(true, data, query, bitmap, words, delta_edges, n_delta, limit, answers, complete, counts, err, pairs,
-                                   induced);
 }
 
 }  // namespace gnnpe_host

@@ -1,10 +1,11 @@
 // refine_sets.h -- the SET-RESTRICTED refinement on the host: the CPU yardstick of csrc/gnnpe_refine_sets.hip.
 //
-// R(C, limit) = min(limit, number of maps f from query vertices to data vertices that are injective, keep labels, have
-// query degree <= data degree, map every query edge onto a data edge, and have f(u) in C(u) for EVERY query vertex u)
+// M = the maps f from query vertices to data vertices that are injective, keep labels, have query degree <= data degree, map
+// every query edge onto a data edge, and have f(u) in C(u) for EVERY query vertex u; R(C, limit) = min(limit, |M|)
 // (include/gnnpe_online.h).  host/refine.h restricts the start vertex only, as the reference does; where every C(u) is
 // complete the two agree, and both equal the true embedding count.  Plain backtracking in the order of
-// build_match_order (refine.h); the count does not depend on the order.
+// build_match_order (refine.h); the count does not depend on the order.  One entry, refine_sets_run, serves every result kind
+// of the header.
 #pragma once
 
 #include <algorithm>
@@ -38,33 +39,29 @@ inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words,
     return out;
 }
 
-// bitmap: query.n rows of `words` = ceil(data.n / 32) uint32, bit v of row u set <=> v in C(u) (the layout
-// gnnpe_filter_candidates writes).  Returns 0 and *answers, or <0 with *err (disconnected query graph).
-// pairs (optional): only the maps with f(a) < f(b) for every pair (a, b) are counted -- with the pairs of query_symmetry.h this is
-// D(C, limit), one embedding per distinct subgraph.
-// induced: only the maps that also send every two distinct, non-adjacent query vertices to non-adjacent data vertices are counted
-// -- I(C, limit), or with the pairs ID(C, limit).
-int refine_sets_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                      uint64_t limit, uint64_t *answers, std::string *err,
-                      const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
-
-// V_m(C) of include/gnnpe_online.h: counts[u * data.n + v] = the number of the maps refine_sets_count counts (same pairs, same
-// induced) that send query vertex u to data vertex v.  limit is a guard: *answers = min(|M|, limit), *complete = |M| < limit, and
-// the table is exact only where *complete (all zeros and complete where a set is empty).
-int refine_sets_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                              uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
-                              const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+// One search, two axes.  M is walked by the same backtracking whatever is asked; a SetsJob says
+//   which of them count: `pairs` (only the maps with f(a) < f(b) for every pair (a, b) -- with the pairs of query_symmetry.h one
+//       embedding per distinct subgraph), `induced` (only the maps that also send every two distinct, non-adjacent query vertices
+//       to non-adjacent data vertices), and F = `delta_edges` where `through` is set (only the maps that put at least one query
+//       edge on an edge of F, each once: one test at every find, nothing shared with the edge-anchored search of
+//       csrc/gnnpe_refine_delta.hip, whose yardstick this is);
+//   what every find that counts adds to: nothing, the vertex table (counts[u * data.n + v] += 1 for every query vertex u, v its
+//       image) or the edge table (counts[k * data.offsets[data.n] + j] += 1 for every query edge k = (a_k, b_k) of query_edges, j
+//       the adjacency entry f(a_k) -> f(b_k) of the data CSR, found by binary search in the row of f(a_k)).
+// In the names of include/gnnpe_online.h:       no table            vertex table   edge table
+//   all of M (through = false)                  R, D, I, ID         V_m(C)         E_m(C)
+//   the maps through F (through = true)         Delta_m(C, F)       VDelta_m(C, F) EDelta_m(C, F)
+struct SetsJob {
+    const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr;
+    bool induced = false;
+    enum Table { kNoTable, kVertexTable, kEdgeTable } table = kNoTable;
+    bool through = false;
+    const uint32_t *delta_edges = nullptr;  // F: n_delta pairs (x, y), either orientation, repeats tolerated; read where `through`
+    uint64_t n_delta = 0;
+};
 
 // The query edges as include/gnnpe_online.h numbers them: (a_k, b_k) with a_k < b_k, lexicographically ascending, each once.
 std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query);
-
-// E_m(C) of include/gnnpe_online.h: counts[k * data.offsets[data.n] + j] = the number of the maps refine_sets_count counts (same
-// pairs, same induced) that send query edge k = (a_k, b_k) onto the adjacency entry j = (f(a_k) -> f(b_k)) of the data CSR; j is
-// found by binary search in the row of f(a_k).  limit and *complete as in refine_sets_vertex_counts.  A query without an edge has
-// no table: counts may then be null.
-int refine_sets_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                            uint64_t limit, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err,
-                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
 
 // An undirected data edge {x, y} as one word: (min << 32) | max.
 inline uint64_t delta_key(uint32_t x, uint32_t y) { return ((uint64_t)std::min(x, y) << 32) | std::max(x, y); }
@@ -73,25 +70,21 @@ inline uint64_t delta_key(uint32_t x, uint32_t y) { return ((uint64_t)std::min(x
 // tolerated.  A loop or an id >= n returns <0 with *err; whether a pair is an edge of the graph is not looked at here.
 int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys, std::string *err);
 
-// Delta_m(C, F, limit) of include/gnnpe_online.h: min(limit, the maps refine_sets_count counts (same pairs, same induced) that put
-// at least one query edge on an edge of F), each once.  The backtracking of refine_sets_count, unchanged, with one test at every
-// find: it walks all of M and shares nothing with the edge-anchored search of csrc/gnnpe_refine_delta.hip, whose yardstick it is.
-// A pair that is no edge of the graph is refused (<0 with *err) by a binary search in the data row.
-int refine_sets_delta_count(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                            const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, std::string *err,
-                            const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+// The cells of a job's table: query.n * data.n, query edges * adjacency entries, or 0 without a table.  A query without an edge
+// has no edge table.
+size_t sets_table_cells(const StaticGraph &data, const StaticGraph &query, SetsJob::Table table);
 
-// VDelta_m(C, F) and EDelta_m(C, F) of include/gnnpe_online.h: the tables of refine_sets_vertex_counts / refine_sets_edge_counts
-// over the maps refine_sets_delta_count counts only.  The same unchanged backtracking over all of M, the F test at every find, then
-// the cell increments.  limit and *complete as in refine_sets_vertex_counts with Delta in the place of |M|; refusals as
-// refine_sets_delta_count.  A query without an edge has no edge table: counts may then be null.
-int refine_sets_delta_vertex_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                                    const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
-                                    uint64_t *counts, std::string *err,
-                                    const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
-int refine_sets_delta_edge_counts(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words,
-                                  const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t *answers, bool *complete,
-                                  uint64_t *counts, std::string *err,
-                                  const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr, bool induced = false);
+// bitmap: query.n rows of `words` = ceil(data.n / 32) uint32, bit v of row u set <=> v in C(u) (the layout
+// gnnpe_filter_candidates writes).  Returns 0 with *answers = min(limit, the maps that count), or <0 with *err and *answers = 0.
+// With a table, limit is a guard: *complete = the maps that count < limit (limit 0 walks nothing, and 0 < 0 is false), and the
+// table is exact only where *complete (all zeros and complete where a set is empty); without one, complete may be null.  counts
+// holds sets_table_cells cells and may be null where that is 0.
+// In this order: a null complete, or a null counts with cells, is refused; then F -- a loop, an id >= data.n, a pair that is no
+// edge of the graph (binary search in the data row) -- with counts still untouched; then the table is zeroed; then the walk refuses
+// a bitmap of other than `words` words per row, an ordering pair outside the query and a disconnected query graph, whatever the
+// limit, leaving the zeroed table.  An empty F drops every find: the walk runs with limit 0 and still refuses what it refuses,
+// *answers is 0 and *complete is 0 < limit.
+int refine_sets_run(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
+                    const SetsJob &job, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err);
 
 }  // namespace gnnpe_host

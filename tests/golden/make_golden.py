@@ -253,5 +253,29 @@ def main():
     print(json.dumps(gold, indent=1, sort_keys=True)[:3000])
 
 
+def host_sets_contract():
+    """host_sets_contract.json: what every case of tests/test_host_sets_contract.py leaves, recorded from the library that is
+    built now (no reference binary is needed).  Re-run: python tests/golden/make_golden.py host_sets_contract"""
+    import pathlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_host_sets_contract as contract
+
+    class Tmp:
+        def __init__(self, base):
+            self.base = pathlib.Path(base)
+
+        def mktemp(self, name):
+            return pathlib.Path(tempfile.mkdtemp(prefix=name, dir=self.base))
+
+    with tempfile.TemporaryDirectory() as wd:
+        gold = {entry: contract.observe(Tmp(wd), entry) for entry in contract.ENTRIES}
+    with open(os.path.join(HERE, "host_sets_contract.json"), "w") as f:
+        json.dump(gold, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["host_sets_contract"]:
+        host_sets_contract()
+    else:
+        main()
