@@ -128,7 +128,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 17  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 18  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -178,6 +178,11 @@ ONLINE_SIGNATURES = {
                                                         C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
     "gnnpe_refine_sets_delta_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
                                                       C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
+    "gnnpe_host_query_nonedges": (C.c_int, [C.c_char_p, _u32p, C.c_uint32, _u32p]),
+    "gnnpe_host_refine_sets_delta_nonedges": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p, C.c_uint64,
+                                                        C.c_uint64, C.c_uint32, _u64p]),
+    "gnnpe_refine_sets_delta_nonedges": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
+                                                   C.c_uint64, _f64p]),
 }
 _online = None
 
@@ -506,6 +511,26 @@ def host_refine_sets_delta_edge_counts(g, query_path, bitmap, edges, limit=2 ** 
     complete, counts) as host_refine_sets_edge_counts, over the matches host_refine_sets_delta counts only."""
     return _host_sets("gnnpe_host_refine_sets_delta_edge_counts", g, query_path, bitmap, limit, match_mode(distinct, induced), edges,
                       _edge_table_shape(g, query_path))
+
+
+def host_query_nonedges(query_path):
+    """gnnpe_host_query_nonedges: the non-adjacent pairs of the query as ABI 18 numbers them, an (nqn, 2) uint32 array of (a_k, b_k)
+    with a_k < b_k, lexicographically ascending."""
+    lib, online = load(), load_online()
+    k = C.c_uint32()
+    online.gnnpe_host_query_nonedges(query_path.encode(), None, 0, C.byref(k))  # (a file that does not load fails again below)
+    pairs = np.zeros((max(k.value, 1), 2), np.uint32)
+    if online.gnnpe_host_query_nonedges(query_path.encode(), _ptr(pairs, _u32p), k.value, C.byref(k)):
+        raise GnnpeError(lib.gnnpe_last_error().decode())
+    return pairs[:k.value].copy()
+
+
+def host_refine_sets_delta_nonedges(g, query_path, bitmap, pairs, limit=2 ** 64 - 1, distinct=False):
+    """The induced matches on a set of non-edges on the host (include/gnnpe_online.h, N_m(C, F, limit), ABI 18): the number of induced
+    matches (with distinct=True of the INDUCED | DISTINCT mode) that put at least one non-adjacent query pair on one of `pairs`
+    ((x, y), either orientation, repeats tolerated), each match once, up to `limit`.  A pair that is an edge of g, a loop or an id
+    outside g raises GnnpeError."""
+    return _host_sets("gnnpe_host_refine_sets_delta_nonedges", g, query_path, bitmap, limit, match_mode(distinct, True), pairs)
 
 
 def host_apply_edges(g, insert=None, delete=None):
@@ -1064,6 +1089,22 @@ class Engine:
         self._ck(load_online().gnnpe_refine_sets_delta(self.ctx, query_path.encode(), _ptr(bm, _u32p), _ptr(e, _u32p) if len(e) else None,
                                                        len(e), int(limit), match_mode(distinct, induced), C.byref(out),
                                                        _ptr(rows, _u32p) if cap else None, cap, C.byref(ms)))
+        return out.value, rows[:min(out.value, cap)], ms.value
+
+    def refine_sets_delta_nonedges(self, query_path, bitmap, pairs, limit=2 ** 64 - 1, matches_cap=0, distinct=False):
+        """The induced matches on a set of non-edges on the device (gnnpe_refine_sets_delta_nonedges): (answers, rows, device ms).
+        answers = min(limit, the induced matches -- with distinct=True of the INDUCED | DISTINCT mode -- that put at least one
+        non-adjacent query pair on one of `pairs`), each match once; rows as refine_sets_delta's.  `pairs`: (x, y) that are NOT
+        edges of the loaded graph, either orientation, repeats tolerated; a pair that is an edge is refused."""
+        out, ms = C.c_uint64(), C.c_double()
+        bm, e = _np(bitmap, np.uint32), _delta_pairs(pairs)
+        cap = min(int(matches_cap), int(limit))
+        nq = _bitmap_rows(bm, self.n)
+        rows = np.zeros((cap, nq), np.uint32)
+        self._ck(load_online().gnnpe_refine_sets_delta_nonedges(self.ctx, query_path.encode(), _ptr(bm, _u32p),
+                                                                _ptr(e, _u32p) if len(e) else None, len(e), int(limit),
+                                                                match_mode(distinct, True), C.byref(out),
+                                                                _ptr(rows, _u32p) if cap else None, cap, C.byref(ms)))
         return out.value, rows[:min(out.value, cap)], ms.value
 
     def _refine_sets_delta_counts(self, kind, shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign):

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta(SetsPlan P, SetsDelta D
         bool stop = false;
 
         sets_walk<kOrdered>(
-            P, S, G, ctr, limit, lane, pending, stop, last,
+            P, S, G, ctr, limit, lane, pending, stop, last, 1,
             // the charging rule: a query edge numbered below this launch's must not land in F
             [&](uint32_t d, uint32_t v) { return delta_older_ok(D, S, keys, n_keys, d, v); },
             // the chunk of survivors at the last depth: count them, store their rows

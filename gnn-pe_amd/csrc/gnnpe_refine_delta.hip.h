@@ -1,6 +1,8 @@
 // gnnpe_refine_delta.hip.h -- what the searches anchored at the entries of a set F of data edges share: k_refine_delta
 // (gnnpe_refine_delta.hip, Delta_m(C, F, limit) and its rows) and k_refine_delta_vcount / k_refine_delta_ecount
-// (gnnpe_refine_delta_counts.hip, the tables of the same matches).  On the device the key search, the entries of the pairs, the decode
+// (gnnpe_refine_delta_counts.hip, the tables of the same matches) -- and, anchored at the pairs of a set of NON-edges,
+// k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip), which takes the lookup with its sense inverted, the charging rule, the
+// buffer of F and the host's side as they are and brings its own item decode.  On the device the key search, the entries of the pairs, the decode
 // of an item and the charging rule; on the host F as keys and pairs, the plan of every launch, the staging and the launches.  The
 // text that explains them is at the head of gnnpe_refine_delta.hip; a kernel keeps its leaf and its other hooks.
 #pragma once
@@ -28,10 +30,12 @@ __device__ __forceinline__ bool delta_has(const unsigned long long *__restrict__
     return false;
 }
 
-// one lane per directed pair (x, y), both below n: the index of y in x's row, or kDeltaNoEntry and the error flag
+// one lane per directed pair (x, y), both below n: the index of y in x's row, or kDeltaNoEntry.  The error flag is raised by a pair
+// without an entry where F must hold edges (want_entry != 0), and by a pair WITH one where it must hold non-edges (want_entry == 0,
+// gnnpe_refine_delta_nonedges.hip)
 static __global__ void k_delta_entries(uint32_t n_pairs, const uint32_t *__restrict__ pairs, const uint32_t *__restrict__ adj_start,
                                        const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
-                                       uint32_t *__restrict__ ent, SetsCounters *ctr)
+                                       uint32_t *__restrict__ ent, SetsCounters *ctr, uint32_t want_entry)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pairs) return;
@@ -48,7 +52,7 @@ static __global__ void k_delta_entries(uint32_t n_pairs, const uint32_t *__restr
         if (w < y) lo = mid + 1; else hi = mid;
     }
     ent[i] = j;
-    if (j == kDeltaNoEntry) atomicOr(&ctr->bad, 1u);
+    if ((j == kDeltaNoEntry) == (want_entry != 0u)) atomicOr(&ctr->bad, 1u);
 }
 
 // item q -> the directed entry x -> y at index j of the CSR; x is tested as position 0 (bit x of C, label, degree) and becomes
@@ -104,7 +108,7 @@ struct DeltaBuf {
 struct DeltaPlans {
     std::vector<uint64_t> keys;
     std::vector<uint32_t> pairs;
-    std::vector<std::pair<uint32_t, uint32_t>> qe;
+    std::vector<std::pair<uint32_t, uint32_t>> qe;  // the anchors of the launches: the query edges (or the non-adjacent query pairs)
     std::vector<SetsQuery> plans;
     std::vector<SetsDelta> older;
     std::vector<std::vector<uint32_t>> pos_of;
@@ -113,16 +117,18 @@ struct DeltaPlans {
 };
 
 // Fills D.  A loop or an id the graph does not have is refused here, before anything is launched; with D->nothing the pairs and the
-// plans are not built.
+// plans are not built.  With `nonedges` (gnnpe_refine_delta_nonedges.hip) the anchors `qe` of the launches are the query's
+// non-adjacent pairs in the place of its edges, each with the order of build_match_order_from_pair; `older` then holds the earlier
+// positions joined to a position by a lower-numbered non-adjacent pair.
 static inline int delta_plans(const char *who, gnnpe_ctx *c, const SetsQuery &Q, const gnnpe_host::StaticGraph &q, const uint32_t *delta_edges,
-                              uint64_t n_delta, uint32_t mode, DeltaPlans *D)
+                              uint64_t n_delta, uint32_t mode, DeltaPlans *D, bool nonedges = false)
 {
     std::string err;
     if (gnnpe_host::delta_edge_keys(c->n, delta_edges, n_delta, &D->keys, &err) != 0) {
         set_error("%s: %s", who, err.c_str());
         return GNNPE_ERR_ARG;
     }
-    D->qe = gnnpe_host::query_edges(q);
+    D->qe = nonedges ? gnnpe_host::query_nonedges(q) : gnnpe_host::query_edges(q);
     D->nothing = Q.empty || D->keys.empty() || D->qe.empty();
     if (D->nothing) return GNNPE_OK;
     const size_t n_keys = D->keys.size();
@@ -142,7 +148,8 @@ static inline int delta_plans(const char *who, gnnpe_ctx *c, const SetsQuery &Q,
     D->pos_of.resize(nqe);
     for (size_t k = 0; k < nqe; k++) {
         gnnpe_host::MatchOrder mo;
-        if (gnnpe_host::build_match_order_from_edge(q, D->qe[k].first, D->qe[k].second, &mo, &err) != 0) {
+        if ((nonedges ? gnnpe_host::build_match_order_from_pair : gnnpe_host::build_match_order_from_edge)(q, D->qe[k].first, D->qe[k].second, &mo,
+                                                                                                             &err) != 0) {
             set_error("%s: %s", who, err.c_str());
             return GNNPE_ERR_ARG;
         }
@@ -156,9 +163,10 @@ static inline int delta_plans(const char *who, gnnpe_ctx *c, const SetsQuery &Q,
 }
 
 // The staging of a call whose buffers (q_work, q_bitmap, q_delta) are reserved, on the context's stream: F and the bitmap go up, the
-// counters are zeroed, ev0 is recorded and k_delta_entries looks the pairs up.  Returns the blocks of a search launch: a resident
-// grid, or as many waves as there are items.
-static inline uint32_t delta_stage(SetsCall &call, gnnpe_ctx *c, const SetsQuery &Q, const DeltaPlans &D, const uint32_t *bitmap)
+// counters are zeroed, ev0 is recorded and k_delta_entries looks the pairs up -- each must be an edge of the graph, or with
+// `nonedges` none of them may be.  Returns the blocks of a search launch: a resident grid, or as many waves as there are items.
+static inline uint32_t delta_stage(SetsCall &call, gnnpe_ctx *c, const SetsQuery &Q, const DeltaPlans &D, const uint32_t *bitmap,
+                                   bool nonedges = false)
 {
     const size_t n_keys = D.keys.size();
     SetsCounters *ctr = c->q_work.as<SetsCounters>();
@@ -170,14 +178,16 @@ static inline uint32_t delta_stage(SetsCall &call, gnnpe_ctx *c, const SetsQuery
     if (call.ok() && call.ev0) call.he = hipEventRecord(call.ev0, c->stream);
     call.launch([&] {
         hipLaunchKernelGGL(k_delta_entries, dim3((D.n_items + 255) / 256), dim3(256), 0, c->stream, D.n_items, F.pairs,
-                           c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), F.ent, ctr);
+                           c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), F.ent, ctr, nonedges ? 0u : 1u);
     });
     return (uint32_t)std::min<uint64_t>(sets_grid_blocks(c, Q.nq, D.n_items), (D.n_items + kSetsWavesPerBlock - 1) / kSetsWavesPerBlock);
 }
 
-// One launch per query edge against the one counter block: launch(k, plan of k, ord...) starts the kernel of launch k in the
-// instantiation the plan asks for; the ticket is cleared in between, total and the second counter word go on.
-// (the pairs and the non-edges are the query's, whatever the order: every launch runs the same instantiation)
+// One launch per anchor (query edge, or non-adjacent query pair) against the one counter block: launch(k, plan of k, ord...) starts
+// the kernel of launch k in the instantiation the plan asks for; the ticket is cleared in between, total and the second counter word
+// go on.
+// (the pairs and the non-edges are the query's, whatever the order: every launch runs the same instantiation -- also where the
+// anchor is a non-adjacent pair and left out of the plan's non-edges, since every launch then tests one pair fewer than the query has)
 template <class Launch>
 static inline void delta_launches(SetsCall &call, gnnpe_ctx *c, const DeltaPlans &D, Launch &&launch)
 {

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_vcount(SetsPlan P, Sets
         };
 
         sets_walk<kOrdered>(
-            P, S, G, ctr, limit, lane, pending, stop, last,
+            P, S, G, ctr, limit, lane, pending, stop, last, 1,
             [&](uint32_t d, uint32_t v) { return delta_older_ok(D, S, keys, n_keys, d, v); },  // the charging rule
             leaf, flush, flush, ord...);
         flush(0);
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_ecount(SetsPlan P, Sets
         };
 
         sets_walk<kOrdered>(
-            P, S, G, ctr, limit, lane, pending, stop, last,
+            P, S, G, ctr, limit, lane, pending, stop, last, 1,
             [&](uint32_t d, uint32_t v) { return delta_older_ok(D, S, keys, n_keys, d, v); },  // the charging rule
             leaf,
             flush,  // the last sibling of this depth

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
             if (cnt) found(cnt);
         } else if (sets_item_decode(P, S, G, n_cand, cand, item_off, w_shift, q)) {
             sets_walk<kOrdered>(
-                P, S, G, ctr, limit, lane, pending, stop, last, SetsNoHook{}, leaf,
+                P, S, G, ctr, limit, lane, pending, stop, last, 1, SetsNoHook{}, leaf,
                 flush,  // the last sibling of this depth
                 [&](uint32_t d, unsigned long long m) {
                     flush(d);  // the previous sibling, before the descent overwrites image[d]

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_sets(SetsPlan P, uint32_t n_c
             const uint32_t i = q * 64u + lane, v = sets_single_cand(n_cand, cand, i);
             leaf(0, 0, sets_single_test(P, G, n_cand, i, v), v);
         } else if (sets_item_decode(P, S, G, n_cand, cand, item_off, w_shift, q)) {
-            sets_walk<kOrdered>(P, S, G, ctr, limit, lane, pending, stop, last, SetsNoHook{}, leaf, SetsNoHook{}, SetsNoHook{}, ord...);
+            sets_walk<kOrdered>(P, S, G, ctr, limit, lane, pending, stop, last, 1, SetsNoHook{}, leaf, SetsNoHook{}, SetsNoHook{}, ord...);
         }
         sets_item_end(ctr, lane, pending);
         if (stop) return;

@@ -1,6 +1,7 @@
 // gnnpe_refine_sets.hip.h -- what the set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip),
 // k_refine_vcount, k_refine_ecount and k_refine_delta (the files of those names), k_refine_delta_vcount and k_refine_delta_ecount
-// (gnnpe_refine_delta_counts.hip) and the paged k_refine_pages (gnnpe_refine_pages.hip).
+// (gnnpe_refine_delta_counts.hip), k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip) and the paged k_refine_pages
+// (gnnpe_refine_pages.hip).
 //   * All of them, on the device: the plan by position in the matching order, the per-wave search state in LDS and every STEP of the
 //     search: a chunk's lane test, the descent into a survivor, the decode of a first-level item, the single-vertex item.  On the
 //     host the preparation of a query (sets_prepare), the staging of its first-level items (sets_stage_items) and the choice of
@@ -262,7 +263,7 @@ __device__ __forceinline__ bool sets_single_test(const SetsPlan &P, const SetsGr
 }
 
 // ---- the walk of the one-shot kernels ------------------------------------------------------------------------------------------
-// k_refine_sets, k_refine_vcount, k_refine_ecount and k_refine_delta are one search: a wave takes a ticket, walks the item's subtree
+// k_refine_sets, k_refine_vcount, k_refine_ecount, k_refine_delta and k_refine_delta_nonedges are one search: a wave takes a ticket, walks the item's subtree
 // chunk by chunk and leaves when the total has reached the limit.  That protocol exists once, here; a kernel adds its item setup and
 // the hooks of sets_walk.  (k_refine_pages suspends and resumes and has no limit: it keeps its own loop over the same steps.)
 // The three places where a wave hears of the limit are marked EXIT 1, 2 and 3; the proof in gnnpe_refine_vcount.hip that a count
@@ -362,23 +363,24 @@ struct SetsNoHook {
     }
 };
 
-// The walk of an item below depth 1, which sets_item_decode (or a kernel's own decode) has entered: per step the next chunk of the
+// The walk of an item below depth `first`, which sets_item_decode (or a kernel's own decode) has entered: per step the next chunk of the
 // current depth's pivot row, its lane test, the leaf at the last depth and the descent into a survivor above it; up when a row is
-// exhausted, done when depth 1 is.  A kernel's own work is four inlined callables:
+// exhausted, done when depth `first` is.  A kernel's own work is four inlined callables:
 //   test(d, v)          for a lane that passed sets_lane_test with candidate v at depth d: false fails it
 //   leaf(d, cb, ok, v)  the chunk [cb, ..) at the last depth d: counts the survivors `ok` (sets_found) and does with them what the
 //                       kernel is for
 //   up(d)               the row of depth d < last is exhausted (the subtree of the last image of d is complete), before d--
 //   down(d, m)          before the descent into the lowest survivor of m at depth d
 // `pending` and `stop` are the kernel's registers, which its leaf passes to sets_found; the walk only reads them.  `last` is the last
-// position, nq - 1, which every kernel holds already.
+// position, nq - 1, which every kernel holds already.  `first` is the depth the decode has entered and the walk ends below: the
+// literal 1 for every kernel whose item fixes position 0, 2 for k_refine_delta_nonedges, whose item fixes positions 0 and 1.
 template <bool kOrdered, class Test, class Leaf, class Up, class Down, class... Ord>
 __device__ __forceinline__ void sets_walk(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G, const SetsCounters *ctr,
                                           unsigned long long limit, uint32_t lane, const unsigned long long &pending, const bool &stop, uint32_t last,
-                                          Test &&test, Leaf &&leaf, Up &&up, Down &&down, const Ord &...ord)
+                                          uint32_t first, Test &&test, Leaf &&leaf, Up &&up, Down &&down, const Ord &...ord)
 {
-    uint32_t d = 1, steps = 0;
-    while (d >= 1 && !stop) {
+    uint32_t d = first, steps = 0;
+    while (d >= first && !stop) {
         // a subtree that finds little still hears of the limit: a look at the total every 1024 chunks
         if ((++steps & 1023u) == 0 && __hip_atomic_load(&ctr->total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + pending >= limit)
             break;  // EXIT 3

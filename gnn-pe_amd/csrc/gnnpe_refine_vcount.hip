@@ -89,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_vcount(SetsPlan P, uint32_t n
             leaf(0, 0, sets_single_test(P, G, n_cand, i, v), v);
         } else if (sets_item_decode(P, S, G, n_cand, cand, item_off, w_shift, q)) {
             // flush: the last sibling of a depth when its row is exhausted; the previous sibling before the descent overwrites image[d]
-            sets_walk<kOrdered>(P, S, G, ctr, limit, lane, pending, stop, last, SetsNoHook{}, leaf, flush, flush, ord...);
+            sets_walk<kOrdered>(P, S, G, ctr, limit, lane, pending, stop, last, 1, SetsNoHook{}, leaf, flush, flush, ord...);
             flush(0);
         }
         sets_item_end(ctr, lane, pending);

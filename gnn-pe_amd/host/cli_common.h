@@ -53,6 +53,10 @@ struct Options {
     // --delta-edges FILE (needs --refine sets; with --matches but not --all-matches, not with the count tables): one data edge
     // `x y` per line; the answer is the matches through at least one of them, each once (gnnpe_refine_sets_delta)
     std::string delta_edges_file;
+    // --delta-nonedges FILE (needs --refine sets and --induced; with --matches but not --all-matches, not with --delta-edges or a
+    // count table): one data vertex pair `x y` per line, none of them an edge; the answer is the induced matches that put a
+    // non-adjacent query pair on at least one of them, each once (gnnpe_refine_sets_delta_nonedges)
+    std::string delta_nonedges_file;
     // --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges; not with each other, --matches or
     // the count tables): the table of --vertex-counts / --edge-counts over the matches through the delta edges only
     // (gnnpe_refine_sets_delta_vertex_counts / _edge_counts); -n is a guard as for --vertex-counts
@@ -139,7 +143,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "           [--vertex-counts FILE | --edge-counts FILE | --delta-edges FILE [--delta-vertex-counts FILE |\n"
-                   "           --delta-edge-counts FILE]] [--apply-edges FILE]\n"
+                   "           --delta-edge-counts FILE] | --delta-nonedges FILE] [--apply-edges FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -157,6 +161,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --distinct, --induced and --apply-edges, not with each other, --matches, --vertex-counts or --edge-counts) write\n"
                    "       the file of --vertex-counts / --edge-counts over the matches through the delta edges only.  -n is a guard as\n"
                    "       for --vertex-counts;\n"
+                   "       --delta-nonedges FILE (needs --refine sets and --induced; combines with --distinct and --matches, not with\n"
+                   "       --delta-edges, --all-matches or a count table): FILE has one pair of data vertices `x y` per line, none of them\n"
+                   "       an edge; the answer is the number of induced matches that put a non-adjacent query pair on at least one of\n"
+                   "       them, each match once -- the matches that inserting these edges destroys -- and --matches writes those;\n"
                    "       --apply-edges FILE (exact mode only: --exact or -l 3): FILE has one line `+ x y` (insert the edge) or `- x y`\n"
                    "       (delete it) per edge; the batch is applied to the data graph on the device and the query runs on the result:\n"
                    "       the metadata block and the rows of --edge-counts / --vertex-counts and of their --delta forms\n"
@@ -178,12 +186,14 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             continue;
         }
         if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges" ||
+            a == "--delta-nonedges" ||
             a == "--apply-edges" || a == "--delta-vertex-counts" || a == "--delta-edge-counts") {
             if (i + 1 >= argc) die(a + " needs a value");
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }
             if (a == "--vertex-counts") { o.vertex_counts_file = argv[++i]; continue; }
             if (a == "--edge-counts") { o.edge_counts_file = argv[++i]; continue; }
             if (a == "--delta-edges") { o.delta_edges_file = argv[++i]; continue; }
+            if (a == "--delta-nonedges") { o.delta_nonedges_file = argv[++i]; continue; }
             if (a == "--delta-vertex-counts") { o.delta_vertex_counts_file = argv[++i]; continue; }
             if (a == "--delta-edge-counts") { o.delta_edge_counts_file = argv[++i]; continue; }
             if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; continue; }

@@ -195,7 +195,7 @@ void write_edge_table(const std::string &path, const StaticGraph &g, uint32_t nq
     if (fclose(ef) != 0) die("write failed on " + path);
 }
 
-// F of --delta-edges: one `x y` per line
+// F of --delta-edges and of --delta-nonedges: one `x y` per line
 std::vector<uint32_t> read_delta_edges(const std::string &path)
 {
     std::vector<uint32_t> pairs;
@@ -241,8 +241,10 @@ struct MatchFile {
 //   --delta-edges FILE       gnnpe_refine_sets_delta: the matches through the listed data edges, each once; with
 //                            --delta-vertex-counts / --delta-edge-counts FILE gnnpe_refine_sets_delta_vertex_counts / _edge_counts,
 //                            the count tables of those matches
+//   --delta-nonedges FILE    gnnpe_refine_sets_delta_nonedges: the induced matches that put a non-adjacent query pair on one of
+//                            the listed non-edges, each once
 //   none of these            gnnpe_refine_sets_mode
-// The two one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
+// The three one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
 struct Refinement {
     void *online = nullptr;  // the library's handle
     uint64_t answers = 0, n_written = 0, n_pages = 0;
@@ -318,6 +320,10 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
         const std::vector<uint32_t> edges = read_delta_edges(o.delta_edges_file);
         check(ONLINE(gnnpe_refine_sets_delta)(ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers,
                                               cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta");
+    } else if (!o.delta_nonedges_file.empty()) {
+        const std::vector<uint32_t> pairs = read_delta_edges(o.delta_nonedges_file);
+        check(ONLINE(gnnpe_refine_sets_delta_nonedges)(ctx, query, bitmap.data(), pairs.data(), pairs.size() / 2, limit, match_mode, &r.answers,
+                                                       cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta_nonedges");
     } else {
         check(ONLINE(gnnpe_refine_sets_mode)(ctx, query, bitmap.data(), limit, match_mode, &r.answers, cap ? rows.data() : nullptr, cap,
                                              &r.refine_ms), "refine_sets");
@@ -537,6 +543,14 @@ int main(int argc, char **argv)
     if (!o.delta_edges_file.empty() && o.refine != "sets") die("--delta-edges needs --refine sets");
     if (!o.delta_edges_file.empty() && (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty()))
         die("--delta-edges excludes --all-matches, --vertex-counts and --edge-counts");
+    if (!o.delta_nonedges_file.empty()) {
+        if (o.refine != "sets") die("--delta-nonedges needs --refine sets");
+        if (!o.induced) die("--delta-nonedges needs --induced");
+        if (!o.delta_edges_file.empty()) die("--delta-nonedges and --delta-edges exclude each other");
+        if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty() || !o.delta_vertex_counts_file.empty() ||
+            !o.delta_edge_counts_file.empty())
+            die("--delta-nonedges excludes --all-matches, --vertex-counts, --edge-counts, --delta-vertex-counts and --delta-edge-counts");
+    }
     for (const char *flag : {"--delta-vertex-counts", "--delta-edge-counts"}) {
         const bool edge_table = std::string(flag) == "--delta-edge-counts";
         if ((edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file).empty()) continue;

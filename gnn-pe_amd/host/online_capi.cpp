@@ -59,7 +59,7 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
     return 0;
 }
 
-// The eight host entries of the set-restricted refinement are this one sequence: null checks, outputs cleared, unknown mode
+// The host entries of the set-restricted refinement are this one sequence: null checks, outputs cleared, unknown mode
 // bits, query load, the search (gnnpe_host::refine_sets_run), its refusal as the error text.  An entry is its name, its table kind
 // and whether it has F (`through`); what differs between them follows from those two:
 //   null checks   offsets, nbrs, labels, query_graph_path, candidate_bitmap and answers always; complete with a table; counts with
@@ -68,12 +68,12 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
 //   cleared       before the mode check *answers = 0 and *complete = 0 -- but not by the three entries with neither table nor F,
 //                 which leave *answers alone until the search starts
 //   refusal text  the search's own; with F behind "<who>: ".  A query that does not load returns the loader's code and text as
-//                 they are, in all eight.  *answers is 0 after a refusal of the search.
+//                 they are, in all of them.  *answers is 0 after a refusal of the search.
 // mode 0 and GNNPE_MATCH_DISTINCT are what gnnpe_host_refine_sets and gnnpe_host_refine_sets_distinct pass.
 static int host_sets(const char *who, gnnpe_host::SetsJob::Table table, bool through, uint32_t n, const uint32_t *offsets,
                      const uint32_t *nbrs, const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap,
                      const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers, int *complete,
-                     uint64_t *counts)
+                     uint64_t *counts, bool nonedges = false)
 {
     const bool has_table = table != gnnpe_host::SetsJob::kNoTable;
     if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || (has_table && !complete) ||
@@ -85,6 +85,10 @@ static int host_sets(const char *who, gnnpe_host::SetsJob::Table table, bool thr
     if (has_table) *complete = 0;
     if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
         gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
+        return GNNPE_ERR_ARG;
+    }
+    if (nonedges && !(mode & GNNPE_MATCH_INDUCED)) {
+        gnnpe::set_error("%s: the mode must contain GNNPE_MATCH_INDUCED", who);
         return GNNPE_ERR_ARG;
     }
     gnnpe_host::StaticGraph q;
@@ -99,6 +103,7 @@ static int host_sets(const char *who, gnnpe_host::SetsJob::Table table, bool thr
     job.induced = (mode & GNNPE_MATCH_INDUCED) != 0;
     job.table = table;
     job.through = through;
+    job.nonedges = nonedges;
     job.delta_edges = delta_edges;
     job.n_delta = n_delta;
     std::string err;
@@ -173,6 +178,15 @@ int gnnpe_host_refine_sets_delta_edge_counts(uint32_t n, const uint32_t *offsets
 }
 #undef HOST_SETS
 
+// (the ninth entry of that sequence: F holds non-edges, the mode must be an induced one)
+int gnnpe_host_refine_sets_delta_nonedges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                          const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *pairs,
+                                          uint64_t n_pairs, uint64_t limit, uint32_t mode, uint64_t *answers)
+{
+    return host_sets("gnnpe_host_refine_sets_delta_nonedges", gnnpe_host::SetsJob::kNoTable, true, n, offsets, nbrs, labels, query_graph_path,
+                     candidate_bitmap, pairs, n_pairs, limit, mode, answers, nullptr, nullptr, true);
+}
+
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
 {
     if (!query_graph_path || !n_edges || (!edges && cap)) {
@@ -190,6 +204,27 @@ int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32
     for (size_t k = 0; k < qe.size(); k++) {
         edges[2 * k] = qe[k].first;
         edges[2 * k + 1] = qe[k].second;
+    }
+    return 0;
+}
+
+int gnnpe_host_query_nonedges(const char *query_graph_path, uint32_t *pairs, uint32_t cap, uint32_t *n_pairs)
+{
+    if (!query_graph_path || !n_pairs || (!pairs && cap)) {
+        gnnpe::set_error("gnnpe_host_query_nonedges: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    gnnpe_host::StaticGraph q;
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const std::vector<std::pair<uint32_t, uint32_t>> qn = gnnpe_host::query_nonedges(q);
+    *n_pairs = (uint32_t)qn.size();
+    if (qn.size() > cap) {
+        gnnpe::set_error("gnnpe_host_query_nonedges: %zu pairs, room for %u", qn.size(), cap);
+        return GNNPE_ERR_ARG;
+    }
+    for (size_t k = 0; k < qn.size(); k++) {
+        pairs[2 * k] = qn[k].first;
+        pairs[2 * k + 1] = qn[k].second;
     }
     return 0;
 }

@@ -117,6 +117,23 @@ int build_match_order_from_edge(const StaticGraph &query, uint32_t a, uint32_t b
     return grow_match_order(query, seen, out, err);
 }
 
+int build_match_order_from_pair(const StaticGraph &query, uint32_t a, uint32_t b, MatchOrder *out, std::string *err)
+{
+    const uint32_t nq = query.n;
+    if (!out || a >= nq || b >= nq || a == b ||
+        std::binary_search(query.neighbors.begin() + query.offsets[a], query.neighbors.begin() + query.offsets[a + 1], b)) {
+        if (err) *err = "build_match_order_from_pair: (a, b) must be two different, non-adjacent vertices of the query";
+        return -2;
+    }
+    out->order = {a, b};
+    out->pivot = {a, a};  // (position 1 has no pivot: the entry stands for the anchor, and no row is walked for it)
+    out->back.clear();
+    out->back_off.assign(3, 0);  // neither position has a back neighbour
+    std::vector<uint8_t> seen(nq, 0);
+    seen[a] = seen[b] = 1;
+    return grow_match_order(query, seen, out, err);
+}
+
 int refine_count(const StaticGraph &data, const StaticGraph &query, const std::vector<std::vector<uint32_t>> &cand,
                  uint64_t limit, uint64_t *answers, std::string *err)
 {

@@ -33,6 +33,13 @@ int build_match_order(const StaticGraph &query, const std::vector<uint64_t> &can
 // back lists.  (a, b) must be an edge of the query; a disconnected query is refused.
 int build_match_order_from_edge(const StaticGraph &query, uint32_t a, uint32_t b, MatchOrder *out, std::string *err);
 
+// The same order anchored at a NON-ADJACENT pair of the query: order[0] = a, order[1] = b, then the rule above.  b is reached through
+// no adjacency row, so position 1 has no pivot: pivot[1] = a stands for the anchor itself (a plan built from this order therefore
+// counts the anchor neither as an edge to test nor as a non-edge to test).  The query is connected, so every position >= 2 has a
+// pivot among the earlier positions, which may be position 1.  (a, b) must be different and not adjacent; a disconnected query is
+// refused.
+int build_match_order_from_pair(const StaticGraph &query, uint32_t a, uint32_t b, MatchOrder *out, std::string *err);
+
 // candidates[u] = ascending data vertex ids of query vertex u.  Returns 0 and *answers, or <0 with *err
 // (disconnected query graph, size mismatch).
 int refine_count(const StaticGraph &data, const StaticGraph &query, const std::vector<std::vector<uint32_t>> &candidates,

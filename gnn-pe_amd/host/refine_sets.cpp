@@ -23,8 +23,9 @@ struct SetSearch {
     uint64_t count = 0, limit;
     uint64_t *vcounts = nullptr;              // vertex counts: nq x g.n cells, every find adds 1 to the cell of each of its images
     uint64_t *ecounts = nullptr;              // edge counts: qedges.size() x g.offsets[g.n] cells, every find adds 1 per query edge
-    std::vector<std::pair<uint32_t, uint32_t>> qedges;  // query_edges(q), for ecounts and delta
-    const std::vector<uint64_t> *delta = nullptr;       // delta: ascending keys (min << 32) | max; a find with no query edge on one is dropped
+    std::vector<std::pair<uint32_t, uint32_t>> qedges;  // query_edges(q), for ecounts
+    std::vector<std::pair<uint32_t, uint32_t>> anchors;  // delta: the query pairs looked up in F -- query_edges(q), or query_nonedges(q)
+    const std::vector<uint64_t> *delta = nullptr;       // delta: ascending keys (min << 32) | max; a find with no anchor on one is dropped
 
     bool in_set(uint32_t u, uint32_t v) const { return (bitmap[(size_t)u * words + (v >> 5)] >> (v & 31)) & 1u; }
     bool fits(uint32_t u, uint32_t v) const
@@ -41,8 +42,8 @@ struct SetSearch {
         if (depth == order.size()) {
             if (delta) {
                 bool touches = false;
-                for (size_t k = 0; k < qedges.size() && !touches; k++)
-                    touches = std::binary_search(delta->begin(), delta->end(), delta_key(image[qedges[k].first], image[qedges[k].second]));
+                for (size_t k = 0; k < anchors.size() && !touches; k++)
+                    touches = std::binary_search(delta->begin(), delta->end(), delta_key(image[anchors[k].first], image[anchors[k].second]));
                 if (!touches) return;
             }
             count++;
@@ -107,7 +108,8 @@ static int refine_sets_walk(const StaticGraph &data, const StaticGraph &query, c
     SetSearch s{data, query, bitmap, words, mo.order, mo.pivot, {}, std::vector<std::vector<uint32_t>>(nq),
                 std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0),
                 std::vector<uint8_t>(data.n, 0), 0, limit, vcounts, ecounts,
-                ecounts || delta ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>(), delta};
+                ecounts ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>(),
+                !delta ? std::vector<std::pair<uint32_t, uint32_t>>() : job.nonedges ? query_nonedges(query) : query_edges(query), delta};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
     // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
     for (uint32_t i = 1; job.induced && i < nq; i++)
@@ -152,6 +154,16 @@ std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query)
     return out;
 }
 
+std::vector<std::pair<uint32_t, uint32_t>> query_nonedges(const StaticGraph &query)
+{
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    for (uint32_t a = 0; a < query.n; a++)
+        for (uint32_t b = a + 1; b < query.n; b++)
+            if (!std::binary_search(query.neighbors.begin() + query.offsets[a], query.neighbors.begin() + query.offsets[a + 1], b))
+                out.emplace_back(a, b);
+    return out;
+}
+
 size_t sets_table_cells(const StaticGraph &data, const StaticGraph &query, SetsJob::Table table)
 {
     if (table == SetsJob::kVertexTable) return (size_t)query.n * data.n;
@@ -180,15 +192,17 @@ int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, s
     return 0;
 }
 
-// F as ascending keys, each a checked edge of the graph: what a job through F refuses
-static int delta_keys_checked(const StaticGraph &data, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys,
-                              std::string *err)
+// F as ascending keys, each a checked edge of the graph -- or, with `nonedges`, each checked NOT to be one: what a job through F
+// refuses
+static int delta_keys_checked(const StaticGraph &data, const uint32_t *delta_edges, uint64_t n_delta, bool nonedges,
+                              std::vector<uint64_t> *keys, std::string *err)
 {
     if (delta_edge_keys(data.n, delta_edges, n_delta, keys, err) != 0) return -2;
     for (uint64_t key : *keys) {
         const uint32_t x = (uint32_t)(key >> 32), y = (uint32_t)key;
-        if (!std::binary_search(data.neighbors.begin() + data.offsets[x], data.neighbors.begin() + data.offsets[x + 1], y)) {
-            if (err) *err = "delta edge (" + std::to_string(x) + ", " + std::to_string(y) + ") is not an edge of the graph";
+        if (std::binary_search(data.neighbors.begin() + data.offsets[x], data.neighbors.begin() + data.offsets[x + 1], y) == nonedges) {
+            if (err) *err = (nonedges ? "pair (" : "delta edge (") + std::to_string(x) + ", " + std::to_string(y) +
+                            (nonedges ? ") is an edge of the graph" : ") is not an edge of the graph");
             return -2;
         }
     }
@@ -209,7 +223,11 @@ int refine_sets_run(const StaticGraph &data, const StaticGraph &query, const uin
     }
     if (complete) *complete = false;
     std::vector<uint64_t> keys;
-    if (job.through && delta_keys_checked(data, job.delta_edges, job.n_delta, &keys, err) != 0) return -2;
+    if (job.nonedges && (!job.through || !job.induced || job.table != SetsJob::kNoTable)) {
+        if (err) *err = "the maps through a set of non-edges: an induced job without a table";
+        return -2;
+    }
+    if (job.through && delta_keys_checked(data, job.delta_edges, job.n_delta, job.nonedges, &keys, err) != 0) return -2;
     if (cells) std::fill(counts, counts + cells, 0ull);
     // (an empty F drops every find: limit 0, and the walk still refuses what it refuses)
     const int rc = refine_sets_walk(data, query, bitmap, words, job.through && keys.empty() ? 0 : limit, job, cells ? counts : nullptr,

@@ -51,17 +51,23 @@ inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words,
 // In the names of include/gnnpe_online.h:       no table            vertex table   edge table
 //   all of M (through = false)                  R, D, I, ID         V_m(C)         E_m(C)
 //   the maps through F (through = true)         Delta_m(C, F)       VDelta_m(C, F) EDelta_m(C, F)
+//   ... F of non-edges (nonedges = true)        N_m(C, F)           --             --
 struct SetsJob {
     const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr;
     bool induced = false;
     enum Table { kNoTable, kVertexTable, kEdgeTable } table = kNoTable;
     bool through = false;
+    bool nonedges = false;  // with `through`, `induced` and no table: F holds NON-edges of the graph, and a map counts if it puts a
+                            // non-adjacent query pair (query_nonedges) on one of them -- N_m(C, F) of include/gnnpe_online.h
     const uint32_t *delta_edges = nullptr;  // F: n_delta pairs (x, y), either orientation, repeats tolerated; read where `through`
     uint64_t n_delta = 0;
 };
 
 // The query edges as include/gnnpe_online.h numbers them: (a_k, b_k) with a_k < b_k, lexicographically ascending, each once.
 std::vector<std::pair<uint32_t, uint32_t>> query_edges(const StaticGraph &query);
+
+// The non-adjacent pairs of the query as include/gnnpe_online.h numbers them: (a_k, b_k) with a_k < b_k, lexicographically ascending.
+std::vector<std::pair<uint32_t, uint32_t>> query_nonedges(const StaticGraph &query);
 
 // An undirected data edge {x, y} as one word: (min << 32) | max.
 inline uint64_t delta_key(uint32_t x, uint32_t y) { return ((uint64_t)std::min(x, y) << 32) | std::max(x, y); }
@@ -80,7 +86,7 @@ size_t sets_table_cells(const StaticGraph &data, const StaticGraph &query, SetsJ
 // table is exact only where *complete (all zeros and complete where a set is empty); without one, complete may be null.  counts
 // holds sets_table_cells cells and may be null where that is 0.
 // In this order: a null complete, or a null counts with cells, is refused; then F -- a loop, an id >= data.n, a pair that is no
-// edge of the graph (binary search in the data row) -- with counts still untouched; then the table is zeroed; then the walk refuses
+// edge of the graph (binary search in the data row; with `nonedges` a pair that IS one) -- with counts still untouched; then the table is zeroed; then the walk refuses
 // a bitmap of other than `words` words per row, an ordering pair outside the query and a disconnected query graph, whatever the
 // limit, leaving the zeroed table.  An empty F drops every find: the walk runs with limit 0 and still refuses what it refuses,
 // *answers is 0 and *complete is 0 < limit.

@@ -282,7 +282,7 @@ int gnnpe_refine_sets_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, 
  *   - modes 0 and DISTINCT, G' = G plus F with F disjoint from E(G), the same C: |M(G')| = |M(G)| + Delta(G', F).  The degree
  *     test does not disturb this: a match that avoids F already has deg_Q(u) distinct neighbours of f(u) in G.
  *   - the INDUCED modes: Delta is still exactly "the matches on the loaded graph that touch F", but adding an edge can also
- *     DESTROY induced matches, and those are not Delta of the new graph.
+ *     DESTROY induced matches, and those are not Delta of the new graph.  They are N of the old graph: ABI 18, below.
  *   - F = E(G) and nq >= 2: Delta = |M|.
  *   - F = {{x, y}}: Delta = the sum over k of E[k][x->y] + E[k][y->x].
  *   - a single-vertex query has no edge: Delta = 0.  n_delta == 0: Delta = 0.  Nothing is launched in either case.
@@ -338,7 +338,8 @@ int gnnpe_refine_sets_delta(gnnpe_ctx *ctx, const char *query_graph_path, const 
  *     M(G') = M(G) + Dset(G', F), disjoint.  Hence V(G') = V(G) + VD(G', F), and E(G') = E(G) + ED(G', F) compared by the key
  *     (x, y) of an entry -- the entry indices of G and G' differ; an entry of F has E(G) = 0.
  *   - DELETION IDENTITY, the same modes.  V(G - D) = V(G) - VD(G, D), and the same for E by keys.
- *   - the INDUCED modes: the tables are "the matches on the loaded graph that touch F", nothing more (the caveat of ABI 15).
+ *   - the INDUCED modes: the tables are "the matches on the loaded graph that touch F", nothing more (the caveat of ABI 15; ABI 18
+ *     has the count of the other half, not its tables).
  *   - a single-vertex query has Delta = 0: the V table is all zeros, the E table is empty as in ABI 14.
  *   - n_delta == 0: the tables are all zeros.
  *
@@ -385,6 +386,59 @@ int gnnpe_refine_sets_delta_edge_counts(gnnpe_ctx *ctx, const char *query_graph_
                                         const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
                                         uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
                                         void *dev_accum, int sign, double *device_ms);
+
+/* ---- ABI version 18: the induced matches an edge change destroys or creates ------------------------------------------------------
+ * Under the INDUCED modes an edge change works both ways: a new edge creates the matches through it (Delta of ABI 15, asked after
+ * the insertion) and DESTROYS every match that had a non-adjacent query pair on its two ends; a removed edge destroys the matches
+ * through it and CREATES those.  The functions below are the mirror image of ABI 15: the matches that put a non-adjacent query pair
+ * on one of a given set of data vertex pairs -- asked before an insertion the matches it destroys, asked after a deletion the ones
+ * it created.  With them a caller keeps an induced count (a motif or graphlet count) current without re-running it.
+ *
+ * Terms as in the ABI 12 - 15 texts, M_m(C) as in ABI 13.  The non-adjacent pairs of the loaded simple query graph are written
+ * (a_k, b_k) with a_k < b_k and sorted lexicographically, k = 0 .. nqn - 1.  gnnpe_host_query_nonedges hands that list out (pairs:
+ * cap x 2 uint32; conventions exactly as gnnpe_host_query_edges: *n_pairs is always set, and a cap below it returns GNNPE_ERR_ARG).
+ * F is a set of unordered data vertex pairs that are NOT edges of the loaded graph, handed over as pairs: n_pairs x 2 uint32
+ * (x, y), either orientation; repeats and both orientations of one pair are tolerated and mean the pair once.
+ *
+ *   N_m(C, F, limit) = min(limit, |{ f in M_m(C) : {f(a_k), f(b_k)} in F for at least one k }|)     m contains GNNPE_MATCH_INDUCED
+ *
+ * Every such map is counted and listed ONCE, however many of its non-adjacent pairs land in F.  Write Nset_m(C, F) for the set of
+ * these maps and Dset_m(C, F) for the set of ABI 17.  The identities below hold for the INDUCED modes with the same C on both
+ * graphs (a label bitmap, for instance; a degree bitmap differs between the two):
+ *   - INSERTION.  G' = G + F with F disjoint from E(G).  As sets of maps M(G') = (M(G) - Nset(G, F)) + Dset(G', F), the union
+ *     disjoint and Nset(G, F) inside M(G): |M(G')| = |M(G)| - N(G, F) + Delta(G', F).
+ *   - DELETION.  G' = G - D with D inside E(G).  M(G') = (M(G) - Dset(G, D)) + Nset(G', D): |M(G')| = |M(G)| - Delta(G, D) + N(G', D).
+ *   - MIXED BATCH, exact in two steps: first delete D (Delta on the graph before, gnnpe_csr_apply_edges, N on the graph after), then
+ *     insert I (N on the graph before, gnnpe_csr_apply_edges, Delta on the graph after).  One step with both lists is not exact: a
+ *     map can lose one pair to D and gain another from I.
+ *   - F = all non-edges of G and a query with a non-adjacent pair: N = |M_m(C)|.
+ *   - a query without a non-adjacent pair (1 or 2 vertices, K_n), or n_pairs == 0: N = 0, and nothing is launched.
+ *   (The degree test does not disturb the identities for the reason given in ABI 15, and the ordering pairs do not depend on the
+ *   graph.)
+ *
+ * Refusals, all GNNPE_ERR_ARG with *answers = 0:
+ *   - a mode without GNNPE_MATCH_INDUCED, or with unknown bits.
+ *   - x == y, or an id >= n: checked on the host before anything is launched.
+ *   - a pair that IS an edge of the graph.  The device form finds it on the device and reports it with the counter block, in the
+ *     call's single wait; the context stays usable afterwards.  (Where nothing is launched the device form does not look the pairs
+ *     up.)
+ *   - everything else exactly as gnnpe_refine_sets_mode.
+ *
+ * gnnpe_host_refine_sets_delta_nonedges: the host form, the yardstick.  The unchanged backtracking of gnnpe_host_refine_sets_mode
+ *   over all of M with one test at every find (is the image of some non-adjacent query pair among the sorted keys of F); F's pairs
+ *   are checked to be non-edges up front.  It shares nothing with the device search.
+ * gnnpe_refine_sets_delta_nonedges: the device form (csrc/gnnpe_refine_delta_nonedges.hip): one launch per non-adjacent query pair k
+ *   over one item per directed pair of F, in a matching order that starts at (a_k, b_k) and walks from the third position on; a map
+ *   is kept in the launch of its lowest-numbered non-adjacent pair in F only.  Its cost follows N and nqn,
+ *   not |M|.  matches, matches_cap, the row layout, *device_ms and the ownership of the buffers are exactly those of
+ *   gnnpe_refine_sets_delta; there is no paged form and there are no count tables of Nset. */
+int gnnpe_host_query_nonedges(const char *query_graph_path, uint32_t *pairs, uint32_t cap, uint32_t *n_pairs);
+int gnnpe_host_refine_sets_delta_nonedges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                          const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *pairs,
+                                          uint64_t n_pairs, uint64_t limit, uint32_t mode, uint64_t *answers);
+int gnnpe_refine_sets_delta_nonedges(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                     const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode, uint64_t *answers,
+                                     uint32_t *matches, uint64_t matches_cap, double *device_ms);
 
 #ifdef __cplusplus
 }
