@@ -128,7 +128,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 18  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 19  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -183,6 +183,15 @@ ONLINE_SIGNATURES = {
                                                         C.c_uint64, C.c_uint32, _u64p]),
     "gnnpe_refine_sets_delta_nonedges": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
                                                    C.c_uint64, _f64p]),
+    "gnnpe_host_refine_sets_delta_nonedges_vertex_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p,
+                                                                      C.c_uint64, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int),
+                                                                      _u64p]),
+    "gnnpe_host_refine_sets_delta_nonedges_edge_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p,
+                                                                    C.c_uint64, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p]),
+    "gnnpe_refine_sets_delta_nonedges_vertex_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                                 _u64p, C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
+    "gnnpe_refine_sets_delta_nonedges_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
+                                                               C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
 }
 _online = None
 
@@ -533,6 +542,23 @@ def host_refine_sets_delta_nonedges(g, query_path, bitmap, pairs, limit=2 ** 64 
     return _host_sets("gnnpe_host_refine_sets_delta_nonedges", g, query_path, bitmap, limit, match_mode(distinct, True), pairs)
 
 
+def host_refine_sets_delta_nonedges_vertex_counts(g, query_path, bitmap, pairs, limit=2 ** 64 - 1, distinct=False):
+    """The per-vertex table of the induced matches on a set of non-edges on the host (include/gnnpe_online.h, VN_m(C, F), ABI 19):
+    (answers, complete, counts) as host_refine_sets_vertex_counts, over the matches host_refine_sets_delta_nonedges counts only;
+    answers = min(N, limit), complete = N < limit.  `pairs` as for host_refine_sets_delta_nonedges."""
+    bm, n = _np(bitmap, np.uint32), len(g["offsets"]) - 1
+    return _host_sets("gnnpe_host_refine_sets_delta_nonedges_vertex_counts", g, query_path, bm, limit, match_mode(distinct, True), pairs,
+                      (_bitmap_rows(bm, n), n))
+
+
+def host_refine_sets_delta_nonedges_edge_counts(g, query_path, bitmap, pairs, limit=2 ** 64 - 1, distinct=False):
+    """The per-edge table of the induced matches on a set of non-edges on the host (include/gnnpe_online.h, EN_m(C, F), ABI 19):
+    (answers, complete, counts) as host_refine_sets_edge_counts -- the rows are the query EDGES of host_query_edges -- over the
+    matches host_refine_sets_delta_nonedges counts only."""
+    return _host_sets("gnnpe_host_refine_sets_delta_nonedges_edge_counts", g, query_path, bitmap, limit, match_mode(distinct, True), pairs,
+                      _edge_table_shape(g, query_path))
+
+
 def host_apply_edges(g, insert=None, delete=None):
     """gnnpe_host_csr_apply_edges: the graph dict of G' = (E(g) minus delete) plus insert, a compact CSR with g's labels.  The
     lists hold pairs (x, y), either orientation, repeats tolerated; a loop, an id outside g, an insertion that is an edge, a
@@ -796,7 +822,8 @@ class Engine:
         self.e = 0
         self.entries = 0  # adjacency entries of the CSR given to load_csr: the width of the edge-count tables
         self._rows_gen = self._ecounts_call = 0  # what an edge-count device view is valid for
-        self._delta_counts_call = {"vertex": 0, "edge": 0}  # ... and a view of a delta table
+        # ... and a view of a delta table, or of a table over non-edges
+        self._delta_counts_call = {"vertex": 0, "edge": 0, "nonedges_vertex": 0, "nonedges_edge": 0}
         self.slab = (0, 0)
         self.total = None
         self._pools = []
@@ -1139,6 +1166,29 @@ class Engine:
         shape = (len(host_query_edges(query_path)), self.entries)
         return self._refine_sets_delta_counts("edge", shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign)
 
+    def refine_sets_delta_nonedges_vertex_counts(self, query_path, bitmap, pairs, limit=2 ** 64 - 1, distinct=False, device=False,
+                                                 accum=None, sign=1):
+        """The per-vertex table of the induced matches on a set of non-edges on the device
+        (gnnpe_refine_sets_delta_nonedges_vertex_counts): (answers, complete, counts, device ms) as refine_sets_vertex_counts, over
+        the matches refine_sets_delta_nonedges counts only (with distinct=True of the INDUCED | DISTINCT mode).  device, accum and
+        sign exactly as for refine_sets_delta_vertex_counts: a device=True view is of the context's own table for this call, valid
+        until the next such call or until the rows are loaded or changed (apply_edges), and delta_counts_to_host(counts) copies it
+        back.  With refine_sets_delta_vertex_counts an induced table is maintained across apply_edges: -VN(G, I), apply, +VD(G', I)
+        for an insertion, -VD(G, D), apply, +VN(G', D) for a deletion."""
+        bm = _np(bitmap, np.uint32)
+        return self._refine_sets_delta_counts("nonedges_vertex", (_bitmap_rows(bm, self.n), self.n), query_path, bm, pairs, limit,
+                                              distinct, True, device, accum, sign)
+
+    def refine_sets_delta_nonedges_edge_counts(self, query_path, bitmap, pairs, limit=2 ** 64 - 1, distinct=False, device=False,
+                                               accum=None, sign=1):
+        """The per-edge table of the induced matches on a set of non-edges on the device
+        (gnnpe_refine_sets_delta_nonedges_edge_counts): (answers, complete, counts, device ms) as refine_sets_edge_counts -- the rows
+        are the query edges, the columns the adjacency entries of the graph the context holds now -- over the matches
+        refine_sets_delta_nonedges counts only.  device, accum and sign as for refine_sets_delta_nonedges_vertex_counts, the caller's
+        table being (nqe, entries) uint64."""
+        shape = (len(host_query_edges(query_path)), self.entries)
+        return self._refine_sets_delta_counts("nonedges_edge", shape, query_path, bitmap, pairs, limit, distinct, True, device, accum, sign)
+
     def _counts_view_to_host(self, view, stamp, stale):
         """a device table of this context copied to the host as uint64, unless its valid_for is not `stamp` any more"""
         if getattr(view, "owner", None) is not self or getattr(view, "valid_for", None) != stamp:
@@ -1149,8 +1199,8 @@ class Engine:
         return self.copy_to_host(view.__cuda_array_interface__["data"][0], nbytes).view(np.uint64).reshape(view.shape)
 
     def delta_counts_to_host(self, view):
-        """the context's own device table a refine_sets_delta_vertex_counts / _edge_counts(..., device=True) call returned, copied
-        to the host as uint64; a view from before the latest such call or from before the rows were loaded or changed is refused"""
+        """the context's own device table a refine_sets_delta_vertex_counts / _edge_counts or refine_sets_delta_nonedges_vertex_counts
+        / _edge_counts(..., device=True) call returned, copied to the host as uint64; a view from before the latest such call or from before the rows were loaded or changed is refused"""
         kind = (getattr(view, "valid_for", None) or (None,))[0]
         return self._counts_view_to_host(view, (kind, self._rows_gen, self._delta_counts_call.get(kind)),
                                          "stale delta-count view: the table was replaced by a later call or the graph was loaded or changed")

@@ -1,9 +1,10 @@
 // gnnpe_refine_delta.hip.h -- what the searches anchored at the entries of a set F of data edges share: k_refine_delta
 // (gnnpe_refine_delta.hip, Delta_m(C, F, limit) and its rows) and k_refine_delta_vcount / k_refine_delta_ecount
 // (gnnpe_refine_delta_counts.hip, the tables of the same matches) -- and, anchored at the pairs of a set of NON-edges,
-// k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip), which takes the lookup with its sense inverted, the charging rule, the
-// buffer of F and the host's side as they are and brings its own item decode.  On the device the key search, the entries of the pairs, the decode
-// of an item and the charging rule; on the host F as keys and pairs, the plan of every launch, the staging and the launches.  The
+// k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip) and k_refine_delta_nonedges_vcount / _ecount
+// (gnnpe_refine_delta_nonedges_counts.hip), which take the lookup with its sense inverted, the charging rule, the buffer of F and the
+// host's side as they are and share their own item decode (nonedge_item_decode).  On the device the key search, the entries of the
+// pairs, the two decodes of an item and the charging rule; on the host F as keys and pairs, the plan of every launch, the staging and the launches.  The
 // text that explains them is at the head of gnnpe_refine_delta.hip; a kernel keeps its leaf and its other hooks.
 #pragma once
 
@@ -74,6 +75,47 @@ __device__ __forceinline__ bool delta_item_decode(const SetsPlan &P, volatile Se
     S.end[1] = j + 1u;
     S.mask_lo[1] = 0;
     S.mask_hi[1] = 0;
+    return true;
+}
+
+// item q -> the directed pair (x, y) of F, both below n.  x is tested as position 0 and y as position 1; they become image[0] and
+// image[1], and depth 2 is entered over its pivot's row.  False: a pair that is an edge of the graph (the call is refused), or an x
+// or y that fails.
+template <bool kOrdered, class... Ord>
+__device__ __forceinline__ bool nonedge_item_decode(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G,
+                                                    const uint32_t *__restrict__ pairs, const uint32_t *__restrict__ ent, uint32_t q,
+                                                    uint32_t lane, const Ord &...ord)
+{
+    if (uni(ent[q]) != kDeltaNoEntry) return false;
+    const uint32_t x = uni(pairs[2 * q]), y = uni(pairs[2 * q + 1]);
+    const uint32_t sx = uni(G.adj_start[x]), dx = uni(G.adj_deg[x]), sy = uni(G.adj_start[y]), dy = uni(G.adj_deg[y]);
+    const uint32_t wx = uni(G.bitmap[(uint64_t)P.qv[0] * G.words + (x >> 5)]), wy = uni(G.bitmap[(uint64_t)P.qv[1] * G.words + (y >> 5)]);
+    if (x == y || ((wx >> (x & 31u)) & 1u) == 0 || ((wy >> (y & 31u)) & 1u) == 0) return false;
+    if (uni(G.labels[x]) != P.label[0] || dx < P.degree[0] || uni(G.labels[y]) != P.label[1] || dy < P.degree[1]) return false;
+    S.image[0] = x;
+    S.istart[0] = sx;
+    S.ideg[0] = dx;
+    if constexpr (kOrdered) {
+        uint32_t lo, hi;
+        order_bounds(sets_order(ord...), S, 1, lo, hi);
+        if (y < lo || y >= hi) return false;
+    }
+    S.image[1] = y;
+    S.istart[1] = sy;
+    S.ideg[1] = dy;
+    const uint32_t p = P.pivot[2], ps = uni(S.istart[p]);
+    uint32_t rb = ps, re = ps + uni(S.ideg[p]);
+    if constexpr (kOrdered) {
+        if (sets_order(ord...).trim) {
+            uint32_t lo, hi;
+            order_bounds(sets_order(ord...), S, 2, lo, hi);
+            order_trim(G.nbrs, lo, hi, lane, rb, re);
+        }
+    }
+    S.cbase[2] = rb - 64u;
+    S.end[2] = re;
+    S.mask_lo[2] = 0;
+    S.mask_hi[2] = 0;
     return true;
 }
 

@@ -31,16 +31,9 @@
 // every moment of every launch; the three exits are still the only places where a wave reads the total against the limit.
 // Resources of the eight instantiations and the measurement: profiles/online_delta_counts.txt.
 #include "../../include/gnnpe_online.h"
-#include "gnnpe_refine_delta.hip.h"
-#include "gnnpe_refine_ecount.hip.h"
+#include "gnnpe_refine_delta_counts.hip.h"
 
 namespace gnnpe {
-
-// has k_delta_entries met a pair that is no edge?  Final before a search launch starts.
-__device__ __forceinline__ bool delta_refused(const SetsCounters *ctr)
-{
-    return uni(__hip_atomic_load(&ctr->bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0;
-}
 
 // One kernel, four instantiations, as k_refine_sets: plain, SetsOrder (distinct), SetsNon (induced), both.  nq >= 2.
 template <bool kOrdered, class... Ord>
@@ -169,97 +162,29 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_ecount(SetsPlan P, Sets
     }
 }
 
-// Both entry points after their names: the argument checks, the preparation of gnnpe_refine_sets_delta, the table (the context's
-// own, zeroed on the stream before the first launch, or the caller's, untouched until a search kernel adds to it), the launches, the
-// single wait and what comes back.
-static int delta_counts_call(const char *who, const char *tag, bool edge_table, gnnpe_ctx *c, const char *query_graph_path,
-                             const uint32_t *candidate_bitmap, const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
-                             uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, void *dev_accum, int sign,
-                             double *device_ms)
+// Both entry points after their names: the host's side is delta_counts_call (gnnpe_refine_delta_counts.hip.h), shared with the tables
+// over a set of non-edges; this file's part of it is the kernel a launch starts.
+static int delta_edges_counts_call(const char *who, const char *tag, bool edge_table, gnnpe_ctx *c, const char *query_graph_path,
+                                   const uint32_t *candidate_bitmap, const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit,
+                                   uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, void *dev_accum,
+                                   int sign, double *device_ms)
 {
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && complete && (delta_edges || n_delta == 0), GNNPE_ERR_ARG,
-                  "%s: null argument", who);
-    *answers = 0;
-    *complete = 0;
-    if (dev_counts) *dev_counts = nullptr;
-    if (device_ms) *device_ms = 0.0;
-    GNNPE_REQUIRE(sign == 1 || (sign == -1 && dev_accum), GNNPE_ERR_ARG, "%s: sign must be +1, or -1 with dev_accum (got %d)", who, sign);
-    GNNPE_REQUIRE(!(dev_accum && host_counts), GNNPE_ERR_ARG, "%s: host_counts must be NULL with dev_accum", who);
-    SetsQuery Q;
-    gnnpe_host::StaticGraph q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, &q);
-    if (rc) return rc;
-    DeltaPlans D;
-    if ((rc = delta_plans(who, c, Q, q, delta_edges, n_delta, mode, &D))) return rc;
-    if (limit == 0) return GNNPE_OK;  // nothing is launched, and nothing is complete
-    const uint32_t nq = Q.nq, n = c->n, nqe = (uint32_t)D.qe.size();
-    const uint64_t entries = c->nbr_used;  // offsets[n] of gnnpe_load_csr
-    const size_t cells = edge_table ? (size_t)nqe * entries : (size_t)nq * n, table_bytes = cells * 8;
-    unsigned long long *table = static_cast<unsigned long long *>(dev_accum);
-    if (!dev_accum && cells) {
-        // context-owned, grow-only, of its own: the views of gnnpe_refine_sets_vertex_counts / _edge_counts are not disturbed
-        DevBuf &own = edge_table ? c->q_decounts : c->q_dvcounts;
-        if ((rc = own.reserve(table_bytes))) return rc;
-        table = own.as<unsigned long long>();
-    }
-    if (dev_counts) *dev_counts = table;
-    if (D.nothing) {  // an empty set, no F, a single-vertex query: a zero table is the whole answer; a caller's table stays as it is
-        if (!dev_accum && table_bytes) {
-            GNNPE_HIP_TRY(hipMemsetAsync(table, 0, table_bytes, c->stream));
-            GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
-            if (host_counts) std::fill(host_counts, host_counts + cells, 0ull);
-        }
-        *complete = 1;
-        return GNNPE_OK;
-    }
-    const size_t n_keys = D.keys.size();
-    if ((rc = c->q_work.reserve(SetsWork::kCtrBytes)) || (rc = c->q_bitmap.reserve((size_t)nq * Q.words * 4)) ||
-        (rc = c->q_delta.reserve(DeltaBuf::bytes(n_keys))))
-        return rc;
-    // the words of the plan edges, per launch as the plans are
-    std::vector<EcountEdges> X(edge_table ? nqe : 0);
-    uint32_t flips = 0, backflips = 0;
-    for (size_t k = 0; k < X.size(); k++) {
-        const uint32_t got = ecount_edges_from_plan(D.plans[k].P, &X[k], &flips, &backflips);
-        GNNPE_REQUIRE(got == nqe, GNNPE_ERR_ARG, "%s: the plan of launch %zu has %u query edges, the query %u", who, k, got, nqe);
-    }
-    SetsCounters *ctr = c->q_work.as<SetsCounters>();
-    const DeltaBuf F(c->q_delta, n_keys);
-    const unsigned long long one = sign == 1 ? 1ull : ~0ull;
-    SetsCall call(who, c, device_ms != nullptr);
-    const uint32_t blocks = delta_stage(call, c, Q, D, candidate_bitmap);
-    if (c->sw.debug)
-        fprintf(stderr, "[%s] edges=%zu items=%u launches=%zu blocks=%u pairs=%u nonedges=%u accum=%d sign=%d\n", tag, n_keys, D.n_items,
-                D.plans.size(), blocks, D.plans[0].n_pairs, D.plans[0].n_non, dev_accum != nullptr, sign);
-    if (call.ok() && !dev_accum && table_bytes) call.he = hipMemsetAsync(table, 0, table_bytes, c->stream);  // once per call, before the first launch
-    delta_launches(call, c, D, [&](size_t k, const SetsQuery &K, auto... ord) {
-        if (edge_table)
-            hipLaunchKernelGGL((k_refine_delta_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0,
-                               c->stream, K.P, D.older[k], X[k], D.n_items, F.pairs, F.ent, F.keys, (uint32_t)n_keys,
-                               c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
-                               c->q_bitmap.as<uint32_t>(), Q.words, c->revpos.as<uint32_t>(), (unsigned long long)limit, ctr, table, entries,
-                               one, ord...);
-        else
-            hipLaunchKernelGGL((k_refine_delta_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0,
-                               c->stream, K.P, D.older[k], D.n_items, F.pairs, F.ent, F.keys, (uint32_t)n_keys, c->adj_start.as<uint32_t>(),
-                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
-                               Q.words, (unsigned long long)limit, ctr, table, n, one, ord...);
-    });
-    call.wait(ctr, sizeof(SetsCounters));  // all of it: `bad` is in the second half
-    if (call.ok()) {
-        if (reinterpret_cast<const SetsCounters *>(c->h_pinned)->bad) {
-            set_error("%s: a delta edge is not an edge of the graph", who);
-            call.rc = GNNPE_ERR_ARG;
-        } else {
-            *answers = std::min<uint64_t>(c->h_pinned[0], limit);
-            *complete = c->h_pinned[0] < limit ? 1 : 0;
-            if (c->sw.debug)
-                fprintf(stderr, "[%s] finds=%llu flush_adds=%llu complete=%d\n", tag, (unsigned long long)c->h_pinned[0],
-                        (unsigned long long)c->h_pinned[1], *complete);
-            if (host_counts && *complete && table_bytes) call.he = hipMemcpy(host_counts, table, table_bytes, hipMemcpyDeviceToHost);
-        }
-    }
-    return call.finish(device_ms);
+    return delta_counts_call(
+        who, tag, edge_table, false, &gnnpe_ctx::q_dvcounts, &gnnpe_ctx::q_decounts, c, query_graph_path, candidate_bitmap, delta_edges,
+        n_delta, limit, mode, answers, complete, host_counts, dev_counts, dev_accum, sign, device_ms,
+        [&](gnnpe_ctx *c, const DeltaCountsLaunch &A, const SetsQuery &K, auto... ord) {
+            if (edge_table)
+                hipLaunchKernelGGL((k_refine_delta_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(A.blocks), dim3(kBlock), 0,
+                                   c->stream, K.P, *A.older, *A.X, A.n_items, A.F.pairs, A.F.ent, A.F.keys, A.n_keys,
+                                   c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
+                                   c->q_bitmap.as<uint32_t>(), A.words, c->revpos.as<uint32_t>(), A.limit, A.ctr, A.table, A.entries, A.one,
+                                   ord...);
+            else
+                hipLaunchKernelGGL((k_refine_delta_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(A.blocks), dim3(kBlock), 0,
+                                   c->stream, K.P, *A.older, A.n_items, A.F.pairs, A.F.ent, A.F.keys, A.n_keys, c->adj_start.as<uint32_t>(),
+                                   c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
+                                   A.words, A.limit, A.ctr, A.table, A.n, A.one, ord...);
+        });
 }
 
 }  // namespace gnnpe
@@ -271,8 +196,9 @@ extern "C" int gnnpe_refine_sets_delta_vertex_counts(gnnpe_ctx *c, const char *q
                                                      uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
                                                      void *dev_accum, int sign, double *device_ms)
 {
-    return delta_counts_call("gnnpe_refine_sets_delta_vertex_counts", "refine_delta_vcount", false, c, query_graph_path, candidate_bitmap,
-                             delta_edges, n_delta, limit, mode, answers, complete, host_counts, dev_counts, dev_accum, sign, device_ms);
+    return delta_edges_counts_call("gnnpe_refine_sets_delta_vertex_counts", "refine_delta_vcount", false, c, query_graph_path,
+                                   candidate_bitmap, delta_edges, n_delta, limit, mode, answers, complete, host_counts, dev_counts, dev_accum,
+                                   sign, device_ms);
 }
 
 extern "C" int gnnpe_refine_sets_delta_edge_counts(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
@@ -280,6 +206,7 @@ extern "C" int gnnpe_refine_sets_delta_edge_counts(gnnpe_ctx *c, const char *que
                                                    uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
                                                    void *dev_accum, int sign, double *device_ms)
 {
-    return delta_counts_call("gnnpe_refine_sets_delta_edge_counts", "refine_delta_ecount", true, c, query_graph_path, candidate_bitmap,
-                             delta_edges, n_delta, limit, mode, answers, complete, host_counts, dev_counts, dev_accum, sign, device_ms);
+    return delta_edges_counts_call("gnnpe_refine_sets_delta_edge_counts", "refine_delta_ecount", true, c, query_graph_path,
+                                   candidate_bitmap, delta_edges, n_delta, limit, mode, answers, complete, host_counts, dev_counts, dev_accum,
+                                   sign, device_ms);
 }

@@ -13,6 +13,7 @@
 //     query is connected, so every position >= 2 has a pivot among the earlier positions (possibly position 1).
 //   * AN ITEM IS A DIRECTED PAIR (x, y) OF F, 2 |F| items.  k_delta_entries looks the pairs up with its sense inverted: a pair that
 //     HAS an entry raises `bad` and is skipped by the search kernels, and the host refuses the call after its single wait.  The decode
+//     (nonedge_item_decode, in gnnpe_refine_delta.hip.h: the table kernels of gnnpe_refine_delta_nonedges_counts.hip share it)
 //     tests x as position 0 and y as position 1, wave-uniformly -- bit of C, label, degree, x != y, and in the ordered form the
 //     bounds of position 1 -- makes them image[0] and image[1], and enters depth 2 the way sets_descend enters a depth: over the
 //     pivot's row, cut to the bounds in the ordered form.  The walk starts at depth 2 and ends when depth 2 is exhausted (sets_walk's
@@ -34,47 +35,6 @@
 #include "gnnpe_refine_delta.hip.h"
 
 namespace gnnpe {
-
-// item q -> the directed pair (x, y) of F, both below n.  x is tested as position 0 and y as position 1; they become image[0] and
-// image[1], and depth 2 is entered over its pivot's row.  False: a pair that is an edge of the graph (the call is refused), or an x
-// or y that fails.
-template <bool kOrdered, class... Ord>
-__device__ __forceinline__ bool nonedge_item_decode(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G,
-                                                    const uint32_t *__restrict__ pairs, const uint32_t *__restrict__ ent, uint32_t q,
-                                                    uint32_t lane, const Ord &...ord)
-{
-    if (uni(ent[q]) != kDeltaNoEntry) return false;
-    const uint32_t x = uni(pairs[2 * q]), y = uni(pairs[2 * q + 1]);
-    const uint32_t sx = uni(G.adj_start[x]), dx = uni(G.adj_deg[x]), sy = uni(G.adj_start[y]), dy = uni(G.adj_deg[y]);
-    const uint32_t wx = uni(G.bitmap[(uint64_t)P.qv[0] * G.words + (x >> 5)]), wy = uni(G.bitmap[(uint64_t)P.qv[1] * G.words + (y >> 5)]);
-    if (x == y || ((wx >> (x & 31u)) & 1u) == 0 || ((wy >> (y & 31u)) & 1u) == 0) return false;
-    if (uni(G.labels[x]) != P.label[0] || dx < P.degree[0] || uni(G.labels[y]) != P.label[1] || dy < P.degree[1]) return false;
-    S.image[0] = x;
-    S.istart[0] = sx;
-    S.ideg[0] = dx;
-    if constexpr (kOrdered) {
-        uint32_t lo, hi;
-        order_bounds(sets_order(ord...), S, 1, lo, hi);
-        if (y < lo || y >= hi) return false;
-    }
-    S.image[1] = y;
-    S.istart[1] = sy;
-    S.ideg[1] = dy;
-    const uint32_t p = P.pivot[2], ps = uni(S.istart[p]);
-    uint32_t rb = ps, re = ps + uni(S.ideg[p]);
-    if constexpr (kOrdered) {
-        if (sets_order(ord...).trim) {
-            uint32_t lo, hi;
-            order_bounds(sets_order(ord...), S, 2, lo, hi);
-            order_trim(G.nbrs, lo, hi, lane, rb, re);
-        }
-    }
-    S.cbase[2] = rb - 64u;
-    S.end[2] = re;
-    S.mask_lo[2] = 0;
-    S.mask_hi[2] = 0;
-    return true;
-}
 
 // One kernel, four instantiations, as k_refine_delta: plain (the anchor is the query's only non-adjacent pair), SetsOrder, SetsNon,
 // both.  nq >= 3: a connected query with a non-adjacent pair has a third vertex.

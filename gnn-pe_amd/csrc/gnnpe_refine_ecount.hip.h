@@ -1,5 +1,6 @@
-// gnnpe_refine_ecount.hip.h -- what the kernels that fill a per-edge table share: k_refine_ecount (gnnpe_refine_ecount.hip, E_m(C)) and
-// k_refine_delta_ecount (gnnpe_refine_delta_counts.hip, EDelta_m(C, F)).  The words of the plan edges and how the host derives them
+// gnnpe_refine_ecount.hip.h -- what the kernels that fill a per-edge table share: k_refine_ecount (gnnpe_refine_ecount.hip, E_m(C)),
+// k_refine_delta_ecount (gnnpe_refine_delta_counts.hip, EDelta_m(C, F)) and k_refine_delta_nonedges_ecount
+// (gnnpe_refine_delta_nonedges_counts.hip, EN_m(C, F)).  The words of the plan edges and how the host derives them
 // from a plan, the per-wave state, the entry searches, and the adds of the leaf and of a flush.  The text that explains them is at
 // the head of gnnpe_refine_ecount.hip; a kernel keeps its tallies' bookkeeping and its hooks.
 #pragma once
@@ -92,8 +93,11 @@ __device__ __forceinline__ void ecount_flush_adds(const SetsPlan &P, const Ecoun
 
 // The words of a plan's edges: the query edges by number -- from the plan, where repeats of the query file count once as in
 // gnnpe_host::query_edges -- and for every plan edge (k << 1) | flip, flip = the earlier position's query vertex is b_k.  Returns nqe;
-// *flips counts the flipped plan edges, *backflips those among them that are back edges.
-static inline uint32_t ecount_edges_from_plan(const SetsPlan &P, EcountEdges *X, uint32_t *flips, uint32_t *backflips)
+// *flips counts the flipped plan edges, *backflips those among them that are back edges.  With `anchor_pair` the plan is one of
+// build_match_order_from_pair: positions 0 and 1 are a NON-adjacent pair, position 1 names position 0 as its pivot only so that the
+// plan is well-formed, and that pseudo-pivot is left out -- it is no query edge, and X->pivot[1] stays 0 and is never read.
+static inline uint32_t ecount_edges_from_plan(const SetsPlan &P, EcountEdges *X, uint32_t *flips, uint32_t *backflips,
+                                              bool anchor_pair = false)
 {
     *X = EcountEdges{};
     *flips = *backflips = 0;
@@ -104,7 +108,7 @@ static inline uint32_t ecount_edges_from_plan(const SetsPlan &P, EcountEdges *X,
         return std::make_pair(std::min(a, b), std::max(a, b));
     };
     for (uint32_t d = 1; d < nq; d++) {
-        qe.push_back(norm(P.pivot[d], d));
+        if (d > 1 || !anchor_pair) qe.push_back(norm(P.pivot[d], d));
         for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1]; j++) qe.push_back(norm(P.back[j], d));
     }
     std::sort(qe.begin(), qe.end());
@@ -116,7 +120,7 @@ static inline uint32_t ecount_edges_from_plan(const SetsPlan &P, EcountEdges *X,
         return (uint16_t)((k << 1) | flip);
     };
     for (uint32_t d = 1; d < nq; d++) {
-        X->pivot[d] = word(P.pivot[d], d, flips);
+        if (d > 1 || !anchor_pair) X->pivot[d] = word(P.pivot[d], d, flips);
         for (uint32_t j = P.back_off[d]; j < P.back_off[d + 1]; j++) X->back[j] = word(P.back[j], d, backflips);
     }
     *flips += *backflips;

@@ -1,7 +1,7 @@
 // gnnpe_refine_sets.hip.h -- what the set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip),
 // k_refine_vcount, k_refine_ecount and k_refine_delta (the files of those names), k_refine_delta_vcount and k_refine_delta_ecount
-// (gnnpe_refine_delta_counts.hip), k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip) and the paged k_refine_pages
-// (gnnpe_refine_pages.hip).
+// (gnnpe_refine_delta_counts.hip), k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip), k_refine_delta_nonedges_vcount and
+// k_refine_delta_nonedges_ecount (gnnpe_refine_delta_nonedges_counts.hip) and the paged k_refine_pages (gnnpe_refine_pages.hip).
 //   * All of them, on the device: the plan by position in the matching order, the per-wave search state in LDS and every STEP of the
 //     search: a chunk's lane test, the descent into a survivor, the decode of a first-level item, the single-vertex item.  On the
 //     host the preparation of a query (sets_prepare), the staging of its first-level items (sets_stage_items) and the choice of
@@ -373,7 +373,8 @@ struct SetsNoHook {
 //   down(d, m)          before the descent into the lowest survivor of m at depth d
 // `pending` and `stop` are the kernel's registers, which its leaf passes to sets_found; the walk only reads them.  `last` is the last
 // position, nq - 1, which every kernel holds already.  `first` is the depth the decode has entered and the walk ends below: the
-// literal 1 for every kernel whose item fixes position 0, 2 for k_refine_delta_nonedges, whose item fixes positions 0 and 1.
+// literal 1 for every kernel whose item fixes position 0, 2 for k_refine_delta_nonedges and the two table kernels over non-edges,
+// whose item fixes positions 0 and 1 (so `up` and `down` are never called for depth 1: those kernels flush it themselves).
 template <bool kOrdered, class Test, class Leaf, class Up, class Down, class... Ord>
 __device__ __forceinline__ void sets_walk(const SetsPlan &P, volatile SetsWave &S, const SetsGraph &G, const SetsCounters *ctr,
                                           unsigned long long limit, uint32_t lane, const unsigned long long &pending, const bool &stop, uint32_t last,

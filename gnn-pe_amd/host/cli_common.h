@@ -53,13 +53,14 @@ struct Options {
     // --delta-edges FILE (needs --refine sets; with --matches but not --all-matches, not with the count tables): one data edge
     // `x y` per line; the answer is the matches through at least one of them, each once (gnnpe_refine_sets_delta)
     std::string delta_edges_file;
-    // --delta-nonedges FILE (needs --refine sets and --induced; with --matches but not --all-matches, not with --delta-edges or a
-    // count table): one data vertex pair `x y` per line, none of them an edge; the answer is the induced matches that put a
-    // non-adjacent query pair on at least one of them, each once (gnnpe_refine_sets_delta_nonedges)
+    // --delta-nonedges FILE (needs --refine sets and --induced; with --matches but not --all-matches, not with --delta-edges,
+    // --vertex-counts or --edge-counts): one data vertex pair `x y` per line, none of them an edge; the answer is the induced matches
+    // that put a non-adjacent query pair on at least one of them, each once (gnnpe_refine_sets_delta_nonedges)
     std::string delta_nonedges_file;
-    // --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges; not with each other, --matches or
-    // the count tables): the table of --vertex-counts / --edge-counts over the matches through the delta edges only
-    // (gnnpe_refine_sets_delta_vertex_counts / _edge_counts); -n is a guard as for --vertex-counts
+    // --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges or --delta-nonedges; not with each
+    // other, --matches or the count tables): the table of --vertex-counts / --edge-counts over the matches through the delta edges
+    // only (gnnpe_refine_sets_delta_vertex_counts / _edge_counts), or with --delta-nonedges over the induced matches on those pairs
+    // only (gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts); -n is a guard as for --vertex-counts
     std::string delta_vertex_counts_file, delta_edge_counts_file;
     // --apply-edges FILE (exact -m online / -m filter only): lines `+ x y` / `- x y`, a batch of edge insertions and deletions
     // applied to the loaded data graph on the device before anything is computed from it (gnnpe_csr_apply_edges)
@@ -142,8 +143,8 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
-                   "           [--vertex-counts FILE | --edge-counts FILE | --delta-edges FILE [--delta-vertex-counts FILE |\n"
-                   "           --delta-edge-counts FILE] | --delta-nonedges FILE] [--apply-edges FILE]\n"
+                   "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE)\n"
+                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE]] [--apply-edges FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -157,14 +158,16 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --delta-edges FILE (needs --refine sets; combines with --distinct, --induced and --matches, not with\n"
                    "       --all-matches or the count tables): FILE has one data edge `x y` per line; the answer is the number of matches\n"
                    "       that put a query edge on at least one of them, each match once, and --matches writes those;\n"
-                   "       --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges; combine with\n"
-                   "       --distinct, --induced and --apply-edges, not with each other, --matches, --vertex-counts or --edge-counts) write\n"
-                   "       the file of --vertex-counts / --edge-counts over the matches through the delta edges only.  -n is a guard as\n"
-                   "       for --vertex-counts;\n"
-                   "       --delta-nonedges FILE (needs --refine sets and --induced; combines with --distinct and --matches, not with\n"
-                   "       --delta-edges, --all-matches or a count table): FILE has one pair of data vertices `x y` per line, none of them\n"
-                   "       an edge; the answer is the number of induced matches that put a non-adjacent query pair on at least one of\n"
-                   "       them, each match once -- the matches that inserting these edges destroys -- and --matches writes those;\n"
+                   "       --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges or --delta-nonedges;\n"
+                   "       combine with --distinct, --induced and --apply-edges, not with each other, --matches, --vertex-counts or\n"
+                   "       --edge-counts) write the file of --vertex-counts / --edge-counts over the matches through the delta edges only,\n"
+                   "       or with --delta-nonedges over the induced matches on the listed non-edges only.  -n is a guard as for\n"
+                   "       --vertex-counts;\n"
+                   "       --delta-nonedges FILE (needs --refine sets and --induced; combines with --distinct, --matches,\n"
+                   "       --delta-vertex-counts and --delta-edge-counts, not with --delta-edges, --all-matches, --vertex-counts or\n"
+                   "       --edge-counts): FILE has one pair of data vertices `x y` per line, none of them an edge; the answer is the number\n"
+                   "       of induced matches that put a non-adjacent query pair on at least one of them, each match once -- the matches\n"
+                   "       that inserting these edges destroys -- and --matches writes those;\n"
                    "       --apply-edges FILE (exact mode only: --exact or -l 3): FILE has one line `+ x y` (insert the edge) or `- x y`\n"
                    "       (delete it) per edge; the batch is applied to the data graph on the device and the query runs on the result:\n"
                    "       the metadata block and the rows of --edge-counts / --vertex-counts and of their --delta forms\n"

@@ -242,7 +242,8 @@ struct MatchFile {
 //                            --delta-vertex-counts / --delta-edge-counts FILE gnnpe_refine_sets_delta_vertex_counts / _edge_counts,
 //                            the count tables of those matches
 //   --delta-nonedges FILE    gnnpe_refine_sets_delta_nonedges: the induced matches that put a non-adjacent query pair on one of
-//                            the listed non-edges, each once
+//                            the listed non-edges, each once; with --delta-vertex-counts / --delta-edge-counts FILE
+//                            gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts, the count tables of those matches
 //   none of these            gnnpe_refine_sets_mode
 // The three one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
 struct Refinement {
@@ -262,24 +263,31 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
         return r;
     }
     const uint32_t match_mode = (o.distinct ? GNNPE_MATCH_DISTINCT : 0u) | (o.induced ? GNNPE_MATCH_INDUCED : 0u);
-    const bool through = !o.delta_edges_file.empty();
+    const bool nonedges = !o.delta_nonedges_file.empty(), through = !o.delta_edges_file.empty() || nonedges;
     const struct {
         const char *flag, *what;
         const std::string &path;
         bool edge_table;
     } tables[] = {{"--vertex-counts", "refine_sets_vertex_counts", o.vertex_counts_file, false},
                   {"--edge-counts", "refine_sets_edge_counts", o.edge_counts_file, true},
-                  {"--delta-vertex-counts", "refine_sets_delta_vertex_counts", o.delta_vertex_counts_file, false},
-                  {"--delta-edge-counts", "refine_sets_delta_edge_counts", o.delta_edge_counts_file, true}};
+                  {"--delta-vertex-counts", nonedges ? "refine_sets_delta_nonedges_vertex_counts" : "refine_sets_delta_vertex_counts",
+                   o.delta_vertex_counts_file, false},
+                  {"--delta-edge-counts", nonedges ? "refine_sets_delta_nonedges_edge_counts" : "refine_sets_delta_edge_counts",
+                   o.delta_edge_counts_file, true}};
     for (const auto &t : tables) {
         if (t.path.empty()) continue;
         uint32_t nqe = 0;
         std::vector<uint32_t> qe((size_t)n_qv * n_qv + 2);
         if (t.edge_table) check(ONLINE(gnnpe_host_query_edges)(query, qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
-        const std::vector<uint32_t> edges = through ? read_delta_edges(o.delta_edges_file) : std::vector<uint32_t>();
+        const std::vector<uint32_t> edges =
+            through ? read_delta_edges(nonedges ? o.delta_nonedges_file : o.delta_edges_file) : std::vector<uint32_t>();
         std::vector<uint64_t> table(t.edge_table ? (size_t)nqe * g.offsets[g.n] : (size_t)n_qv * g.n);
         int complete = 0;
-        if (through)
+        if (nonedges)
+            check((t.edge_table ? ONLINE(gnnpe_refine_sets_delta_nonedges_edge_counts) : ONLINE(gnnpe_refine_sets_delta_nonedges_vertex_counts))(
+                      ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers, &complete, table.data(),
+                      nullptr, nullptr, 1, &r.refine_ms), t.what);
+        else if (through)
             check((t.edge_table ? ONLINE(gnnpe_refine_sets_delta_edge_counts) : ONLINE(gnnpe_refine_sets_delta_vertex_counts))(
                       ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers, &complete, table.data(),
                       nullptr, nullptr, 1, &r.refine_ms), t.what);
@@ -316,11 +324,11 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
     }
     const uint64_t cap = o.matches_file.empty() ? 0 : std::min<uint64_t>(limit, 1ull << 20);
     std::vector<uint32_t> rows((size_t)cap * n_qv);
-    if (through) {
+    if (!o.delta_edges_file.empty()) {
         const std::vector<uint32_t> edges = read_delta_edges(o.delta_edges_file);
         check(ONLINE(gnnpe_refine_sets_delta)(ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers,
                                               cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta");
-    } else if (!o.delta_nonedges_file.empty()) {
+    } else if (nonedges) {
         const std::vector<uint32_t> pairs = read_delta_edges(o.delta_nonedges_file);
         check(ONLINE(gnnpe_refine_sets_delta_nonedges)(ctx, query, bitmap.data(), pairs.data(), pairs.size() / 2, limit, match_mode, &r.answers,
                                                        cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta_nonedges");
@@ -547,15 +555,15 @@ int main(int argc, char **argv)
         if (o.refine != "sets") die("--delta-nonedges needs --refine sets");
         if (!o.induced) die("--delta-nonedges needs --induced");
         if (!o.delta_edges_file.empty()) die("--delta-nonedges and --delta-edges exclude each other");
-        if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty() || !o.delta_vertex_counts_file.empty() ||
-            !o.delta_edge_counts_file.empty())
-            die("--delta-nonedges excludes --all-matches, --vertex-counts, --edge-counts, --delta-vertex-counts and --delta-edge-counts");
+        if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty())
+            die("--delta-nonedges excludes --all-matches, --vertex-counts and --edge-counts");
     }
     for (const char *flag : {"--delta-vertex-counts", "--delta-edge-counts"}) {
         const bool edge_table = std::string(flag) == "--delta-edge-counts";
         if ((edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file).empty()) continue;
         if (o.refine != "sets") die(std::string(flag) + " needs --refine sets");
-        if (o.delta_edges_file.empty()) die(std::string(flag) + " needs --delta-edges FILE");
+        if (o.delta_edges_file.empty() && o.delta_nonedges_file.empty())
+            die(std::string(flag) + " needs --delta-edges FILE or --delta-nonedges FILE");
         if (edge_table && !o.delta_vertex_counts_file.empty()) die("--delta-vertex-counts and --delta-edge-counts exclude each other");
         if (!o.matches_file.empty()) die(std::string(flag) + " and --matches exclude each other");
     }

@@ -187,6 +187,25 @@ int gnnpe_host_refine_sets_delta_nonedges(uint32_t n, const uint32_t *offsets, c
                      candidate_bitmap, pairs, n_pairs, limit, mode, answers, nullptr, nullptr, true);
 }
 
+// (the tenth and the eleventh: the tables of those maps)
+int gnnpe_host_refine_sets_delta_nonedges_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                        const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                        const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
+                                                        uint64_t *answers, int *complete, uint64_t *counts)
+{
+    return host_sets("gnnpe_host_refine_sets_delta_nonedges_vertex_counts", gnnpe_host::SetsJob::kVertexTable, true, n, offsets, nbrs, labels,
+                     query_graph_path, candidate_bitmap, pairs, n_pairs, limit, mode, answers, complete, counts, true);
+}
+
+int gnnpe_host_refine_sets_delta_nonedges_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                      const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                      const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
+                                                      uint64_t *answers, int *complete, uint64_t *counts)
+{
+    return host_sets("gnnpe_host_refine_sets_delta_nonedges_edge_counts", gnnpe_host::SetsJob::kEdgeTable, true, n, offsets, nbrs, labels,
+                     query_graph_path, candidate_bitmap, pairs, n_pairs, limit, mode, answers, complete, counts, true);
+}
+
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
 {
     if (!query_graph_path || !n_edges || (!edges && cap)) {

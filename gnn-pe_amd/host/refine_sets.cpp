@@ -223,8 +223,8 @@ int refine_sets_run(const StaticGraph &data, const StaticGraph &query, const uin
     }
     if (complete) *complete = false;
     std::vector<uint64_t> keys;
-    if (job.nonedges && (!job.through || !job.induced || job.table != SetsJob::kNoTable)) {
-        if (err) *err = "the maps through a set of non-edges: an induced job without a table";
+    if (job.nonedges && (!job.through || !job.induced)) {
+        if (err) *err = "the maps through a set of non-edges: an induced job";
         return -2;
     }
     if (job.through && delta_keys_checked(data, job.delta_edges, job.n_delta, job.nonedges, &keys, err) != 0) return -2;

@@ -51,14 +51,15 @@ inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words,
 // In the names of include/gnnpe_online.h:       no table            vertex table   edge table
 //   all of M (through = false)                  R, D, I, ID         V_m(C)         E_m(C)
 //   the maps through F (through = true)         Delta_m(C, F)       VDelta_m(C, F) EDelta_m(C, F)
-//   ... F of non-edges (nonedges = true)        N_m(C, F)           --             --
+//   ... F of non-edges (nonedges = true)        N_m(C, F)           VN_m(C, F)     EN_m(C, F)
 struct SetsJob {
     const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr;
     bool induced = false;
     enum Table { kNoTable, kVertexTable, kEdgeTable } table = kNoTable;
     bool through = false;
-    bool nonedges = false;  // with `through`, `induced` and no table: F holds NON-edges of the graph, and a map counts if it puts a
-                            // non-adjacent query pair (query_nonedges) on one of them -- N_m(C, F) of include/gnnpe_online.h
+    bool nonedges = false;  // with `through` and `induced`: F holds NON-edges of the graph, and a map counts if it puts a
+                            // non-adjacent query pair (query_nonedges) on one of them -- N_m(C, F) of include/gnnpe_online.h; a table
+                            // is filled as for any other job (the rows of the edge table are still the query EDGES)
     const uint32_t *delta_edges = nullptr;  // F: n_delta pairs (x, y), either orientation, repeats tolerated; read where `through`
     uint64_t n_delta = 0;
 };

@@ -339,7 +339,7 @@ int gnnpe_refine_sets_delta(gnnpe_ctx *ctx, const char *query_graph_path, const 
  *     (x, y) of an entry -- the entry indices of G and G' differ; an entry of F has E(G) = 0.
  *   - DELETION IDENTITY, the same modes.  V(G - D) = V(G) - VD(G, D), and the same for E by keys.
  *   - the INDUCED modes: the tables are "the matches on the loaded graph that touch F", nothing more (the caveat of ABI 15; ABI 18
- *     has the count of the other half, not its tables).
+ *     has the count of the other half and ABI 19 its tables, and with both an induced table is maintained exactly).
  *   - a single-vertex query has Delta = 0: the V table is all zeros, the E table is empty as in ABI 14.
  *   - n_delta == 0: the tables are all zeros.
  *
@@ -431,7 +431,7 @@ int gnnpe_refine_sets_delta_edge_counts(gnnpe_ctx *ctx, const char *query_graph_
  *   over one item per directed pair of F, in a matching order that starts at (a_k, b_k) and walks from the third position on; a map
  *   is kept in the launch of its lowest-numbered non-adjacent pair in F only.  Its cost follows N and nqn,
  *   not |M|.  matches, matches_cap, the row layout, *device_ms and the ownership of the buffers are exactly those of
- *   gnnpe_refine_sets_delta; there is no paged form and there are no count tables of Nset. */
+ *   gnnpe_refine_sets_delta; there is no paged form, and the count tables of Nset are ABI 19, below. */
 int gnnpe_host_query_nonedges(const char *query_graph_path, uint32_t *pairs, uint32_t cap, uint32_t *n_pairs);
 int gnnpe_host_refine_sets_delta_nonedges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                           const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *pairs,
@@ -439,6 +439,72 @@ int gnnpe_host_refine_sets_delta_nonedges(uint32_t n, const uint32_t *offsets, c
 int gnnpe_refine_sets_delta_nonedges(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
                                      const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode, uint64_t *answers,
                                      uint32_t *matches, uint64_t matches_cap, double *device_ms);
+
+/* ---- ABI version 19: count tables of the induced matches on a set of non-edges -----------------------------------------------------
+ * The consumers of the count tables -- graphlet degree vectors, local motif counts, edge-orbit counts -- are the INDUCED consumers,
+ * and under the induced modes the tables of ABI 17 are one half of what an edge change does to a table (its caveat).  The functions
+ * below build the other half, the TABLES of Nset_m(C, F) of ABI 18, with the accumulate and sign conventions of ABI 17, so that
+ *     insertion of F:  T -= tables of Nset(G, F);  gnnpe_csr_apply_edges(ctx, F, NULL);  T += tables of Dset(G', F)
+ *     deletion  of D:  T -= tables of Dset(G, D);  gnnpe_csr_apply_edges(ctx, NULL, D);  T += tables of Nset(G', D)
+ * keeps an induced vertex table exact on the device, and nothing per match leaves the device.  For an edge table the same holds by
+ * the key (x, y) of an entry, as in ABI 17; carrying the entries of G to those of G' is the caller's.
+ *
+ * All terms are those of the ABI 12 - 18 texts.  Nset_m(C, F) is the set ABI 18 counts (limit 2^64 - 1); m must contain
+ * GNNPE_MATCH_INDUCED; F is a set of data vertex pairs that are NOT edges of the loaded graph, handed over as in ABI 18.  The query
+ * EDGES (a_k, b_k), k < nqe, are numbered as gnnpe_host_query_edges numbers them -- the rows of the edge table are the query's edges,
+ * not its non-adjacent pairs -- and the entry index j is as in ABI 14.
+ *
+ *   VN_m(C, F)[u][v] = |{ f in Nset : f(u) = v }|                      nq  x n           uint64, row-major
+ *   EN_m(C, F)[k][j] = |{ f in Nset : f(a_k) = x and f(b_k) = y }|     nqe x offsets[n]  uint64, j = (x -> y)
+ *
+ *   - every row of either table sums to |Nset| = N_m(C, F, 2^64 - 1) of ABI 18.
+ *   - summing EN row k over the entries of data row x gives VN[a_k][x].
+ *   - F = all non-edges of G and a query with a non-adjacent pair: VN = V_m(C) and EN = E_m(C) of ABI 13 / 14 in the same mode.
+ *   - INSERTION, the induced modes, the same C on both graphs, G' = G + F with F disjoint from E(G):
+ *     V(G') = V(G) - VN(G, F) + VD(G', F), and the same for E compared by the key (x, y) of an entry; an entry of F has E(G) = 0 and
+ *     EN(G, F) = 0.
+ *   - DELETION, G' = G - D: V(G') = V(G) - VD(G, D) + VN(G', D), and the same for E by keys.
+ *   - MIXED BATCH: exact in two steps, delete then insert, as the ABI 18 text has it for the count.
+ *   - a query without a non-adjacent pair (1 or 2 vertices, K_n), or n_pairs == 0: the V table is all zeros, the E table is all zeros
+ *     (empty for a single-vertex query, as in ABI 14), nothing is launched and *complete = 1.
+ *
+ * limit, *answers and *complete are exactly those of ABI 17 with N in the place of Delta: *answers = min(N, limit); *complete = 1
+ * iff N < limit; with *complete = 0 the table is unspecified and nothing is copied to the host; limit == 0 launches nothing and gives
+ * *complete = 0.  host_counts, dev_counts, dev_accum and sign are exactly those of ABI 17 as well: sign must be 1 without dev_accum,
+ * host_counts must be NULL with it, every cell of a caller's table ends at old + sign * c mod 2^64, a refused call leaves a caller's
+ * table byte for byte as it was, and where nothing is launched it is untouched.
+ *
+ * Refusals are those of gnnpe_refine_sets_delta_nonedges, all GNNPE_ERR_ARG with *answers = 0: a mode without GNNPE_MATCH_INDUCED or
+ * with unknown bits; a loop or an id >= n, refused on the host; a pair that IS an edge, found on the device and reported after the
+ * call's single wait, after which the context stays usable (the host forms find it up front).  The sign and dev_accum refusals of
+ * ABI 17 apply as well.
+ *
+ * gnnpe_host_refine_sets_delta_nonedges_vertex_counts, gnnpe_host_refine_sets_delta_nonedges_edge_counts: the host forms, the
+ *   yardstick.  The unchanged backtracking of gnnpe_host_refine_sets_mode over all of M; at every find the one key test of
+ *   gnnpe_host_refine_sets_delta_nonedges, then the cell increments of gnnpe_host_refine_sets_vertex_counts / _edge_counts.  They
+ *   share nothing with the device search.  counts is the caller's (nq x n, nqe x offsets[n]; NULL is accepted for an empty edge table).
+ * gnnpe_refine_sets_delta_nonedges_vertex_counts, gnnpe_refine_sets_delta_nonedges_edge_counts: the device forms
+ *   (csrc/gnnpe_refine_delta_nonedges_counts.hip): the launches, items and charging rule of gnnpe_refine_sets_delta_nonedges with the
+ *   tallies and flushes of the ABI 17 kernels.  Without dev_accum the table lives in a context-owned, grow-only buffer of its own --
+ *   one for VN, another for EN, neither of them a buffer of ABI 13, 14 or 17, whose device views keep their documented lifetimes --
+ *   zeroed once per call before the first launch, and valid until the next call of the same function on the context or until the
+ *   context's rows are loaded or changed.  *device_ms is as in ABI 17.  There is no paged form. */
+int gnnpe_host_refine_sets_delta_nonedges_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                        const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                        const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
+                                                        uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_host_refine_sets_delta_nonedges_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                      const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                      const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
+                                                      uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_refine_sets_delta_nonedges_vertex_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                   const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
+                                                   uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
+                                                   void *dev_accum, int sign, double *device_ms);
+int gnnpe_refine_sets_delta_nonedges_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                 const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
+                                                 uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
+                                                 void *dev_accum, int sign, double *device_ms);
 
 #ifdef __cplusplus
 }
