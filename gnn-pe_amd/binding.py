@@ -54,6 +54,9 @@ SIGNATURES = {
                                              _u64p]),
     "gnnpe_csr_apply_edges": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u64p, _f64p]),
     "gnnpe_csr_download": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _u64p]),
+    "gnnpe_host_csr_entry_map": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p]),
+    "gnnpe_csr_apply_edges_map": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, C.POINTER(_vp), _f64p]),
+    "gnnpe_csr_carry_entries": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _f64p]),
     "gnnpe_halo_need": (C.c_int, [_vp, C.c_uint32, _u32p, _vp, C.c_uint64, _u64p]),
     "gnnpe_rows_degree": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "gnnpe_rows_pack": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64]),
@@ -128,7 +131,7 @@ SIGNATURES = {
     "gnnpe_emit_calibrate_device": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
-ABI_VERSION = 19  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
+ABI_VERSION = 20  # GNNPE_ABI_VERSION of include/gnnpe_hip.h
 MATCH_DISTINCT, MATCH_INDUCED = 1, 2  # GNNPE_MATCH_* of include/gnnpe_online.h: the mode word of the gnnpe_*_mode functions
 _lib = None
 
@@ -579,6 +582,24 @@ def host_apply_edges(g, insert=None, delete=None):
     return out
 
 
+NO_ENTRY = 0xFFFFFFFF  # GNNPE_NO_ENTRY of include/gnnpe_hip.h
+
+
+def host_entry_map(g_old, g_new):
+    """gnnpe_host_csr_entry_map: for every adjacency entry (x -> y) of g_new the index of the entry (x -> y) in g_old, NO_ENTRY
+    where g_old does not have it, as a uint32 array; both are compact simple CSRs on the same vertices."""
+    lib = load()
+    o0, n0 = _np(g_old["offsets"], np.uint32), _np(g_old["nbrs"], np.uint32)
+    o1, n1 = _np(g_new["offsets"], np.uint32), _np(g_new["nbrs"], np.uint32)
+    if len(o0) != len(o1):
+        raise GnnpeError("host_entry_map: the two graphs have different vertex counts")
+    out = np.zeros(len(n1), np.uint32)
+    rc = lib.gnnpe_host_csr_entry_map(len(o0) - 1, _ptr(o0, _u32p), _ptr(n0, _u32p), _ptr(o1, _u32p), _ptr(n1, _u32p), _ptr(out, _u32p))
+    if rc:
+        raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
+    return out
+
+
 def host_query_symmetry(query_path, pairs_cap=None):
     """gnnpe_host_query_symmetry: (|Aut(Q)| saturated at 2^64 - 1, pairs ndarray [k, 2]); a pair (a, b) asks for f(a) < f(b), and of
     the |Aut(Q)| embeddings of one subgraph exactly one satisfies every pair.  pairs_cap (default: whatever is needed) is the room
@@ -824,6 +845,7 @@ class Engine:
         self._rows_gen = self._ecounts_call = 0  # what an edge-count device view is valid for
         # ... and a view of a delta table, or of a table over non-edges
         self._delta_counts_call = {"vertex": 0, "edge": 0, "nonedges_vertex": 0, "nonedges_edge": 0}
+        self._map_call = 0  # ... and a view of the entry map: every apply_edges / apply_edges_map ends the one before
         self.slab = (0, 0)
         self.total = None
         self._pools = []
@@ -1296,6 +1318,7 @@ class Engine:
         nothing; an empty batch does nothing."""
         ins, dele = _delta_pairs([] if insert is None else insert), _delta_pairs([] if delete is None else delete)
         after, ms = C.c_uint64(), C.c_double()
+        self._map_call += 1  # the entry map of an earlier apply_edges_map is gone
         self._ck(self.lib.gnnpe_csr_apply_edges(self.ctx, _ptr(ins, _u32p) if len(ins) else None, len(ins),
                                                 _ptr(dele, _u32p) if len(dele) else None, len(dele), C.byref(after),
                                                 C.byref(ms) if timing else None))
@@ -1304,6 +1327,48 @@ class Engine:
             self.slab = (0, self.n)
         self.entries = after.value
         return (after.value, ms.value) if timing else after.value
+
+    def apply_edges_map(self, insert=None, delete=None, timing=False):
+        """gnnpe_csr_apply_edges_map: apply_edges that also leaves the batch's entry map on the device.  Returns (entries_before,
+        entries_after, map_view), with the device ms appended with timing=True.  map_view is a view of the context's own uint32
+        buffer, one word per adjacency entry of the new graph: the index of the same entry in the graph of before, NO_ENTRY for
+        an inserted edge (`torch.as_tensor(map_view, device=...)` shares it: int32 words).  It is valid until the next
+        apply_edges_map or apply_edges or until the rows are loaded; entry_map_to_host(map_view) copies it back and refuses a
+        stale view.  A refused batch raises GnnpeError, changes nothing and leaves no map; an empty batch gives the identity map."""
+        ins, dele = _delta_pairs([] if insert is None else insert), _delta_pairs([] if delete is None else delete)
+        before, after, ms, ptr = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_void_p()
+        self._map_call += 1
+        self._ck(self.lib.gnnpe_csr_apply_edges_map(self.ctx, _ptr(ins, _u32p) if len(ins) else None, len(ins),
+                                                    _ptr(dele, _u32p) if len(dele) else None, len(dele), C.byref(before),
+                                                    C.byref(after), C.byref(ptr), C.byref(ms) if timing else None))
+        if len(ins) or len(dele):
+            self._rows_gen += 1  # device views of the count tables are stale
+            self.slab = (0, self.n)
+        self.entries = after.value
+        view = _DevArray(int(ptr.value or 0), (after.value,), "<u4", owner=self)
+        view.valid_for = ("entry_map", self._rows_gen, self._map_call)
+        return (before.value, after.value, view) + ((ms.value,) if timing else ())
+
+    def entry_map_to_host(self, view):
+        """the entry map an apply_edges_map call returned, copied to the host as uint32; a view from before the latest
+        apply_edges_map / apply_edges or from before the rows were loaded is refused: the buffer holds something else by now"""
+        if getattr(view, "owner", None) is not self or getattr(view, "valid_for", None) != ("entry_map", self._rows_gen, self._map_call):
+            raise GnnpeError("stale entry-map view: the map was replaced by a later apply_edges_map call or the graph was loaded or changed")
+        if view.shape[0] == 0:
+            return np.zeros(0, np.uint32)
+        return self.copy_to_host(view.__cuda_array_interface__["data"][0], view.shape[0] * 4).view(np.uint32)
+
+    def carry_entries(self, src, dst, n_rows, elem_bytes=8, timing=False):
+        """gnnpe_csr_carry_entries: a caller's per-entry table moved from the entries of the graph before the last apply_edges_map
+        to those of the graph after it, on the device: dst[r, j'] = src[r, map[j']], 0 at an inserted edge.  src is (n_rows,
+        entries_before), dst (n_rows, entries_after), row-major, cells of elem_bytes = 8 (the count tables) or 4; both are device
+        pointers (an int, a tensor's data_ptr(), or an object with data_ptr()) on the context's device and must not overlap.
+        Without a valid map (none made, a refused batch, apply_edges or a load since) the call raises GnnpeError and launches
+        nothing.  Returns None, the device ms with timing=True."""
+        ms = C.c_double()
+        ptrs = [C.c_void_p(int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)) if p is not None else None for p in (src, dst)]
+        self._ck(self.lib.gnnpe_csr_carry_entries(self.ctx, int(n_rows), int(elem_bytes), ptrs[0], ptrs[1], C.byref(ms) if timing else None))
+        return ms.value if timing else None
 
     def download_csr(self):
         """gnnpe_csr_download: (offsets, nbrs) of the whole graph the context holds, the arrays the edge-count tables index"""

@@ -153,6 +153,12 @@ struct gnnpe_ctx {
     // gnnpe_csr_apply_edges (gnnpe_update.hip): the spare adj_start / adj_deg / nbrs the new graph is built in before they are
     // swapped with the live ones (ping-pong, grow-only), and the batch's keys, ranks and touched rows
     gnnpe::DevBuf upd_start, upd_deg, upd_nbrs, upd_work;
+    // gnnpe_csr_apply_edges_map: the entry map of the last batch (one word per entry of G': its entry in G or GNNPE_NO_ENTRY),
+    // grow-only.  It is valid while map_valid holds and the rows are still those of generation map_gen; map_before / map_after are
+    // the entry counts of G and G' (the strides of gnnpe_csr_carry_entries)
+    gnnpe::DevBuf upd_map;
+    bool map_valid = false;
+    uint64_t map_gen = 0, map_before = 0, map_after = 0;
     // rows longer than 64 entries ("hub" rows of the l=2 enumeration): ids and adjacency ranges; graph-only, rebuilt
     // whenever rows are loaded / appended / dropped
     gnnpe::DevBuf hub_rows, hub_beg, hub_end;

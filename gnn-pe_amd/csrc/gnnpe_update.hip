@@ -1,5 +1,6 @@
 // gnnpe_update.hip -- A BATCH OF EDGE INSERTIONS AND DELETIONS APPLIED TO THE RESIDENT GRAPH: gnnpe_csr_apply_edges and
-// gnnpe_csr_download of include/gnnpe_hip.h (ABI 16).  The step between two gnnpe_refine_sets_delta calls: delta over the
+// gnnpe_csr_download of include/gnnpe_hip.h (ABI 16); gnnpe_csr_apply_edges_map and gnnpe_csr_carry_entries (ABI 20): the same
+// call leaving the entry map of the batch on the device, and the kernel that moves a caller's per-entry table through it.  The step between two gnnpe_refine_sets_delta calls: delta over the
 // deletions, apply, delta over the insertions.
 //
 // Everything runs on the context's stream from the few kilobytes of the batch, with one wait before the decision:
@@ -31,6 +32,9 @@
 //      with the spare ones and the tail of gnnpe_load_csr runs: owned from present, finish_rows (validation, revpos, hub list),
 //      the neighbour labels, the resets, graph_gen++.  The rebuild is whole on purpose: "the state of a fresh load" holds by
 //      construction (DESIGN.md section 3.7 has its share of the time).
+//
+// The entry map (ABI 20) is written by the merge itself, at its three store sites: the streaming part knows the old entry j of the
+// word it moves, the stay-loop of a touched row knows st + p, an insert has none.  k_carry_entries (below) is a gather through it.
 //
 // Transient memory: a second neighbour array (and second adj_start / adj_deg); they stay with the context as the next call's spare.
 #include <hipcub/hipcub.hpp>
@@ -118,13 +122,17 @@ static __global__ void k_update_degrees(uint32_t n, const uint32_t *__restrict__
 static __global__ void k_update_total(uint32_t n, const uint32_t *__restrict__ offs, UpdateCounters *ctr) { ctr->entries_after = offs[n]; }
 
 // The new neighbour array from the old one and the two key lists (the file's head, step 4).  Blocks [0, copy_blocks) stream
-// the stretches between touched rows, the others merge the touched rows, one wave each.
+// the stretches between touched rows, the others merge the touched rows, one wave each.  kMap: every store of a neighbour word
+// also stores the entry map's word for the same new entry (the old entry it came from, GNNPE_NO_ENTRY for an insert), under
+// the same guard; without it `map` is not looked at and the code is the one of before the map existed.
+template <bool kMap>
 __global__ __launch_bounds__(kBlock) void k_csr_merge(uint32_t copy_blocks, uint32_t entries, const uint32_t *__restrict__ adj_start,
                                                      const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
                                                      const uint32_t *__restrict__ new_start, const uint32_t *__restrict__ new_deg,
                                                      uint32_t *__restrict__ new_nbrs, const uint32_t *__restrict__ rows,
                                                      const ukey *__restrict__ ikeys, const ukey *__restrict__ dkeys,
-                                                     const uint32_t *__restrict__ ipos, const UpdateCounters *__restrict__ ctr)
+                                                     const uint32_t *__restrict__ ipos, const UpdateCounters *__restrict__ ctr,
+                                                     uint32_t *__restrict__ map)
 {
     if ((ctr->bad_insert & ctr->bad_delete & ctr->bad_both) != kNoKey) return;  // refused: the degrees mean nothing
     const uint32_t nt = ctr->n_touched, entries_after = ctr->entries_after;
@@ -160,7 +168,10 @@ __global__ __launch_bounds__(kBlock) void k_csr_merge(uint32_t copy_blocks, uint
                 }
                 if (k < nt && j >= r_beg) continue;  // inside a touched row: the row's wave writes it
                 const uint32_t o = j + shift;
-                if (o < entries_after) new_nbrs[o] = nbrs[j];
+                if (o < entries_after) {
+                    new_nbrs[o] = nbrs[j];
+                    if (kMap) map[o] = j;
+                }
             }
         }
         return;
@@ -181,7 +192,10 @@ __global__ __launch_bounds__(kBlock) void k_csr_merge(uint32_t copy_blocks, uint
             const uint32_t ri = key_lower_bound(ikeys, ia, ib, kx | v), rd = key_lower_bound(dkeys, da, db, kx | v);
             if (rd < db && dkeys[rd] == (kx | v)) continue;  // deleted
             const uint32_t o = p + (ri - ia) - (rd - da);
-            if (o < nd) new_nbrs[nst + o] = v;
+            if (o < nd) {
+                new_nbrs[nst + o] = v;
+                if (kMap) map[nst + o] = st + p;
+            }
         }
         for (uint32_t base = ia; base < ib; base += 64) {  // the inserts
             const uint32_t i = base + lane;
@@ -189,7 +203,50 @@ __global__ __launch_bounds__(kBlock) void k_csr_merge(uint32_t copy_blocks, uint
             const ukey key = ikeys[i];
             const uint32_t rd = key_lower_bound(dkeys, da, db, key);
             const uint32_t o = ipos[i] + (i - ia) - (rd - da);
-            if (o < nd) new_nbrs[nst + o] = (uint32_t)key;
+            if (o < nd) {
+                new_nbrs[nst + o] = (uint32_t)key;
+                if (kMap) map[nst + o] = GNNPE_NO_ENTRY;
+            }
+        }
+    }
+}
+
+// the entry map of the empty batch: every entry stays where it is
+static __global__ void k_map_identity(uint32_t entries, uint32_t *__restrict__ map)
+{
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < entries; j += (uint64_t)gridDim.x * blockDim.x) map[j] = (uint32_t)j;
+}
+
+// gnnpe_csr_carry_entries: dst[r][j'] = src[r][map[j']], 0 where the map says GNNPE_NO_ENTRY.  A block takes kCarryTile
+// consecutive new entries per step, lane t the entries a + t, a + kBlock + t, ...: consecutive lanes hold consecutive j', and
+// between two touched rows map[j'] - j' is constant, so the loads of a wave are as consecutive as its stores (one 256- or
+// 512-byte run per wave instruction).  The map words are read once and kept in registers across the n_rows rows; the kCarryTile
+// / kBlock loads of a row are issued before the first store.  No LDS, no scratch.  A map word >= entries_before never occurs in
+// a valid map; it is treated as GNNPE_NO_ENTRY so that no read leaves src.
+constexpr uint32_t kCarryPerLane = 4, kCarryTile = kCarryPerLane * kBlock;
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_carry_entries(uint32_t n_rows, uint32_t entries_before, uint32_t entries_after,
+                                                         const uint32_t *__restrict__ map, const T *__restrict__ src, T *__restrict__ dst)
+{
+    for (uint64_t a = (uint64_t)blockIdx.x * kCarryTile; a < entries_after; a += (uint64_t)gridDim.x * kCarryTile) {
+        uint32_t m[kCarryPerLane];
+#pragma unroll
+        for (uint32_t i = 0; i < kCarryPerLane; i++) {
+            const uint64_t j = a + i * kBlock + threadIdx.x;
+            m[i] = j < entries_after ? map[j] : GNNPE_NO_ENTRY;
+            if (m[i] >= entries_before) m[i] = GNNPE_NO_ENTRY;
+        }
+        for (uint32_t r = 0; r < n_rows; r++) {
+            const T *__restrict__ s = src + (uint64_t)r * entries_before;
+            T *__restrict__ d = dst + (uint64_t)r * entries_after;
+            T v[kCarryPerLane];
+#pragma unroll
+            for (uint32_t i = 0; i < kCarryPerLane; i++) v[i] = m[i] != GNNPE_NO_ENTRY ? s[m[i]] : (T)0;
+#pragma unroll
+            for (uint32_t i = 0; i < kCarryPerLane; i++) {
+                const uint64_t j = a + i * kBlock + threadIdx.x;
+                if (j < entries_after) d[j] = v[i];
+            }
         }
     }
 }
@@ -246,6 +303,30 @@ struct UpdateEvents {
     }
 };
 
+// device_ms of a call that is one launch: events right around it on the stream (nothing is created where device_ms is NULL)
+struct LaunchTimer {
+    UpdateEvents E;
+    double *out = nullptr;
+    int begin(double *device_ms, hipStream_t stream)
+    {
+        if (!(out = device_ms)) return GNNPE_OK;
+        GNNPE_HIP_TRY(hipEventCreate(&E.ev[0]));
+        GNNPE_HIP_TRY(hipEventCreate(&E.ev[1]));
+        GNNPE_HIP_TRY(hipEventRecord(E.ev[0], stream));
+        return GNNPE_OK;
+    }
+    int end(hipStream_t stream)
+    {
+        if (!out) return GNNPE_OK;
+        float ms = 0.f;
+        GNNPE_HIP_TRY(hipEventRecord(E.ev[1], stream));
+        GNNPE_HIP_TRY(hipEventSynchronize(E.ev[1]));
+        GNNPE_HIP_TRY(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
+        *out = ms;
+        return GNNPE_OK;
+    }
+};
+
 }  // namespace gnnpe
 
 using namespace gnnpe;
@@ -257,10 +338,11 @@ static int require_whole_graph(const char *who, gnnpe_ctx *c)
     return GNNPE_OK;
 }
 
-extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges,
-                                     uint64_t n_delete, uint64_t *n_entries_after, double *device_ms)
+// The body of gnnpe_csr_apply_edges and gnnpe_csr_apply_edges_map.  want_map: the merge also writes the entry map into
+// c->upd_map and a success marks it valid for the new rows; the empty batch writes the identity map.
+static int apply_edges(gnnpe_ctx *c, const char *who, bool want_map, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges,
+                       uint64_t n_delete, uint64_t *n_entries_after, double *device_ms)
 {
-    const char *who = "gnnpe_csr_apply_edges";
     GNNPE_REQUIRE(c && (insert_edges || n_insert == 0) && (delete_edges || n_delete == 0), GNNPE_ERR_ARG, "%s: null argument", who);
     if (device_ms) *device_ms = 0.0;
     int rc = require_whole_graph(who, c);
@@ -268,7 +350,23 @@ extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges,
     const uint32_t n = c->n;
     const uint64_t entries = c->nbr_used;
     if (n_entries_after) *n_entries_after = entries;
-    if (n_insert == 0 && n_delete == 0) return GNNPE_OK;  // nothing is launched, nothing changes
+    if (n_insert == 0 && n_delete == 0) {  // nothing changes; without the map nothing is launched
+        if (!want_map) return GNNPE_OK;
+        GNNPE_HIP_TRY(hipSetDevice(c->device));
+        if ((rc = c->upd_map.reserve((entries + 1) * 4))) return rc;
+        LaunchTimer timer;
+        if ((rc = timer.begin(device_ms, c->stream))) return rc;
+        if (entries) {
+            hipLaunchKernelGGL(k_map_identity, dim3(std::min<int>(grid_for(entries), c->num_cus * 8)), dim3(kBlock), 0, c->stream, (uint32_t)entries,
+                               c->upd_map.as<uint32_t>());
+            GNNPE_HIP_TRY(hipGetLastError());
+        }
+        if ((rc = timer.end(c->stream))) return rc;
+        c->map_valid = true;
+        c->map_gen = c->graph_gen;
+        c->map_before = c->map_after = entries;
+        return GNNPE_OK;
+    }
     GNNPE_REQUIRE(n_insert < (1ull << 30) && n_delete < (1ull << 30), GNNPE_ERR_ARG, "%s: %llu + %llu pairs, the key lists are 32-bit", who,
                   (unsigned long long)n_insert, (unsigned long long)n_delete);
     std::vector<ukey> hi, hd;
@@ -293,7 +391,7 @@ extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges,
     const size_t n_rows_cap = std::min<uint64_t>(n, (uint64_t)cap_ins + cap_del);
     const size_t work_bytes = 64 + 3 * 8 * ((size_t)cap_ins + cap_del) + 4 * (size_t)cap_ins + 2 * 4 * ((size_t)n + 1) + 4 * (n_rows_cap + 1) + n + 1;
     if ((rc = c->upd_start.reserve(((size_t)n + 1) * 4)) || (rc = c->upd_deg.reserve(((size_t)n + 1) * 4)) ||
-        (rc = c->upd_nbrs.reserve((most + 1) * 4)) || (rc = c->upd_work.reserve(work_bytes)))
+        (rc = c->upd_nbrs.reserve((most + 1) * 4)) || (rc = c->upd_work.reserve(work_bytes)) || (want_map && (rc = c->upd_map.reserve((most + 1) * 4))))
         return rc;
     DevBuf fresh_revpos, fresh_label;  // a buffer that has to grow: allocated aside, so that a refusal by the device loses nothing
     if ((rc = grow_aside(c->revpos, fresh_revpos, (most + 1) * 4)) || (rc = grow_aside(c->nbr_label, fresh_label, (most + 1) * 4))) return rc;
@@ -338,9 +436,14 @@ extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges,
     // a third of the resident grid streams the stretches; a wave per touched row
     const uint32_t copy_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((entries + kMergeTile - 1) / kMergeTile, (uint64_t)c->num_cus * 8));
     const uint32_t row_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_rows_cap + kBlock / 64 - 1) / (kBlock / 64), (uint64_t)c->num_cus * 16));
-    hipLaunchKernelGGL(k_csr_merge, dim3(copy_blocks + row_blocks), dim3(kBlock), 0, c->stream, copy_blocks, (uint32_t)entries,
-                       c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->upd_start.as<uint32_t>(),
-                       c->upd_deg.as<uint32_t>(), c->upd_nbrs.as<uint32_t>(), rows, ikeys, dkeys, ipos, ctr);
+    if (want_map)
+        hipLaunchKernelGGL(k_csr_merge<true>, dim3(copy_blocks + row_blocks), dim3(kBlock), 0, c->stream, copy_blocks, (uint32_t)entries,
+                           c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->upd_start.as<uint32_t>(),
+                           c->upd_deg.as<uint32_t>(), c->upd_nbrs.as<uint32_t>(), rows, ikeys, dkeys, ipos, ctr, c->upd_map.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_csr_merge<false>, dim3(copy_blocks + row_blocks), dim3(kBlock), 0, c->stream, copy_blocks, (uint32_t)entries,
+                           c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->upd_start.as<uint32_t>(),
+                           c->upd_deg.as<uint32_t>(), c->upd_nbrs.as<uint32_t>(), rows, ikeys, dkeys, ipos, ctr, (uint32_t *)nullptr);
     GNNPE_HIP_TRY(hipGetLastError());
     if (timed) GNNPE_HIP_TRY(hipEventRecord(E.ev[1], c->stream));
     // the call's wait: the decision is taken here, before anything of the context changes
@@ -358,6 +461,12 @@ extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges,
 
     // the swap, then exactly the tail of gnnpe_load_csr
     c->graph_gen++;
+    if (want_map) {  // (the map's words are in place: the wait above was behind the merge)
+        c->map_valid = true;
+        c->map_gen = c->graph_gen;
+        c->map_before = entries;
+        c->map_after = m2;
+    }
     swap_buffers(c->adj_start, c->upd_start);
     swap_buffers(c->adj_deg, c->upd_deg);
     swap_buffers(c->nbrs, c->upd_nbrs);
@@ -394,6 +503,65 @@ extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges,
                     R.n_ins, R.n_del, R.n_touched, (unsigned long long)entries, (unsigned long long)m2, all, build, all - build - rebuild, rebuild);
     }
     return GNNPE_OK;
+}
+
+extern "C" int gnnpe_csr_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges,
+                                     uint64_t n_delete, uint64_t *n_entries_after, double *device_ms)
+{
+    if (c) c->map_valid = false;  // the entry map belongs to gnnpe_csr_apply_edges_map's batch
+    return apply_edges(c, "gnnpe_csr_apply_edges", false, insert_edges, n_insert, delete_edges, n_delete, n_entries_after, device_ms);
+}
+
+extern "C" int gnnpe_csr_apply_edges_map(gnnpe_ctx *c, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges,
+                                         uint64_t n_delete, uint64_t *n_entries_before, uint64_t *n_entries_after, void **dev_map,
+                                         double *device_ms)
+{
+    const char *who = "gnnpe_csr_apply_edges_map";
+    if (dev_map) *dev_map = nullptr;
+    if (c) {
+        c->map_valid = false;  // whatever happens below, the map of an earlier batch is gone
+        if (n_entries_before) *n_entries_before = c->nbr_used;
+        if (n_entries_after) *n_entries_after = c->nbr_used;
+    }
+    GNNPE_REQUIRE(c && dev_map, GNNPE_ERR_ARG, "%s: null argument", who);
+    const int rc = apply_edges(c, who, true, insert_edges, n_insert, delete_edges, n_delete, n_entries_after, device_ms);
+    if (rc) {
+        c->map_valid = false;
+        return rc;
+    }
+    if (n_entries_before) *n_entries_before = c->map_before;
+    *dev_map = c->upd_map.p;
+    return GNNPE_OK;
+}
+
+extern "C" int gnnpe_csr_carry_entries(gnnpe_ctx *c, uint32_t n_rows, uint32_t elem_bytes, const void *dev_src, void *dev_dst, double *device_ms)
+{
+    const char *who = "gnnpe_csr_carry_entries";
+    GNNPE_REQUIRE(c, GNNPE_ERR_ARG, "%s: null argument", who);
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c->map_valid && c->map_gen == c->graph_gen && c->have_graph, GNNPE_ERR_ARG,
+                  "%s: the context has no valid entry map (gnnpe_csr_apply_edges_map makes one; loading or changing the rows ends it)", who);
+    GNNPE_REQUIRE(elem_bytes == 4 || elem_bytes == 8, GNNPE_ERR_ARG, "%s: elem_bytes %u, 4 or 8 expected", who, elem_bytes);
+    const uint64_t before = c->map_before, after = c->map_after;
+    if (n_rows == 0 || after == 0) return GNNPE_OK;
+    const uint64_t src_bytes = (uint64_t)n_rows * before * elem_bytes, dst_bytes = (uint64_t)n_rows * after * elem_bytes;
+    GNNPE_REQUIRE(dev_dst && (dev_src || src_bytes == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    const uintptr_t s = (uintptr_t)dev_src, d = (uintptr_t)dev_dst;
+    GNNPE_REQUIRE(s % elem_bytes == 0 && d % elem_bytes == 0, GNNPE_ERR_ARG, "%s: a table is not aligned to its %u-byte cells", who, elem_bytes);
+    GNNPE_REQUIRE(src_bytes == 0 || s + src_bytes <= d || d + dst_bytes <= s, GNNPE_ERR_ARG, "%s: src and dst overlap", who);
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    LaunchTimer timer;
+    int rc = timer.begin(device_ms, c->stream);
+    if (rc) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((after + kCarryTile - 1) / kCarryTile, (uint64_t)c->num_cus * 8);
+    if (elem_bytes == 8)
+        hipLaunchKernelGGL(k_carry_entries<uint64_t>, dim3(grid), dim3(kBlock), 0, c->stream, n_rows, (uint32_t)before, (uint32_t)after,
+                           c->upd_map.as<uint32_t>(), static_cast<const uint64_t *>(dev_src), static_cast<uint64_t *>(dev_dst));
+    else
+        hipLaunchKernelGGL(k_carry_entries<uint32_t>, dim3(grid), dim3(kBlock), 0, c->stream, n_rows, (uint32_t)before, (uint32_t)after,
+                           c->upd_map.as<uint32_t>(), static_cast<const uint32_t *>(dev_src), static_cast<uint32_t *>(dev_dst));
+    GNNPE_HIP_TRY(hipGetLastError());
+    return timer.end(c->stream);
 }
 
 extern "C" int gnnpe_csr_download(gnnpe_ctx *c, uint32_t *host_offsets, uint32_t *host_nbrs, uint64_t nbrs_cap, uint64_t *n_entries)

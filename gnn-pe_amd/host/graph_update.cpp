@@ -1,5 +1,6 @@
 // graph_update.cpp -- gnnpe_host_csr_apply_edges: sort and de-duplicate the directed keys of the two lists, check them against
-// the rows, merge row by row.  Plain C++; shares nothing with csrc/gnnpe_update.hip.
+// the rows, merge row by row.  gnnpe_host_csr_entry_map: the entries of one CSR among those of another, a two-pointer walk per
+// row.  Plain C++; shares nothing with csrc/gnnpe_update.hip.
 #include "graph_update.h"
 
 #include <algorithm>
@@ -82,6 +83,20 @@ int csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, c
     }
     (*out_offsets)[n] = (uint32_t)out_nbrs->size();
     return 0;
+}
+
+void csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint32_t *old_nbrs, const uint32_t *new_offsets, const uint32_t *new_nbrs,
+                   uint32_t *map)
+{
+    for (uint32_t x = 0; x < n; x++) {
+        uint32_t j = old_offsets[x];
+        const uint32_t end = old_offsets[x + 1];
+        // both rows ascend: the old row's pointer only moves forward
+        for (uint32_t k = new_offsets[x]; k < new_offsets[x + 1]; k++) {
+            while (j < end && old_nbrs[j] < new_nbrs[k]) j++;
+            map[k] = j < end && old_nbrs[j] == new_nbrs[k] ? j : 0xFFFFFFFFu;
+        }
+    }
 }
 
 }  // namespace gnnpe_host

@@ -17,4 +17,9 @@ int csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, c
                     const uint32_t *delete_edges, uint64_t n_delete, std::vector<uint32_t> *out_offsets, std::vector<uint32_t> *out_nbrs,
                     std::string *err);
 
+// map[j'] for every entry j' = (x -> y) of the new CSR: the index of the entry (x -> y) in the old one, 0xFFFFFFFF
+// (GNNPE_NO_ENTRY) where the old row does not have y.  Both are compact simple CSRs on the same n vertices.
+void csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint32_t *old_nbrs, const uint32_t *new_offsets, const uint32_t *new_nbrs,
+                   uint32_t *map);
+
 }  // namespace gnnpe_host

@@ -529,4 +529,15 @@ int gnnpe_host_csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32
     return GNNPE_OK;
 }
 
+int gnnpe_host_csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint32_t *old_nbrs, const uint32_t *new_offsets,
+                             const uint32_t *new_nbrs, uint32_t *map)
+{
+    if (!old_offsets || !new_offsets || (!old_nbrs && old_offsets[n]) || ((!new_nbrs || !map) && new_offsets[n])) {
+        gnnpe::set_error("gnnpe_host_csr_entry_map: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    gnnpe_host::csr_entry_map(n, old_offsets, old_nbrs, new_offsets, new_nbrs, map);
+    return GNNPE_OK;
+}
+
 }  // extern "C"

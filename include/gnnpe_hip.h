@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GNNPE_ABI_VERSION 19
+#define GNNPE_ABI_VERSION 20
 
 #define GNNPE_OK 0
 #define GNNPE_ERR_ARG (-1)     /* bad argument / call order */
@@ -185,6 +185,55 @@ int gnnpe_csr_apply_edges(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint64_t
                           uint64_t *n_entries_after, double *device_ms);
 int gnnpe_csr_download(gnnpe_ctx *ctx, uint32_t *host_offsets, uint32_t *host_nbrs,
                        uint64_t nbrs_cap, uint64_t *n_entries);
+
+/* ---- ABI version 20: the entry map of a batch, and a caller's per-entry table carried through it -----------------------------
+ * A per-edge table (gnnpe_refine_sets_edge_counts and its delta forms of include/gnnpe_online.h, a caller's truss numbers or edge
+ * ids) is indexed by the adjacency entry j of the compact CSR, and gnnpe_csr_apply_edges moves every entry behind the first row it
+ * touches.  These calls keep such a table on the device across a batch: the apply hands out where every entry of G' came from,
+ * the carry moves the table.
+ *
+ * The map.  One uint32 per entry j' = (x -> y) of G': the index j of the entry (x -> y) in G if G has it, GNNPE_NO_ENTRY if it has
+ * not (an inserted edge).  Both CSRs are sorted by (x, y), so the map is strictly increasing over the entries that are not
+ * GNNPE_NO_ENTRY, and its image is exactly the entries of G that are not in D.
+ *
+ * gnnpe_host_csr_entry_map: the host form and the yardstick (host/graph_update.cpp): any two compact simple CSRs on the same n
+ *   vertices, a two-pointer walk per row; map: new_offsets[n] words.  It shares no code with the device form.  A null argument
+ *   returns GNNPE_ERR_ARG.
+ * gnnpe_csr_apply_edges_map: everything gnnpe_csr_apply_edges does -- the same lists, result, state afterwards, refusals and
+ *   transactional guarantee -- and the map, written by the merge kernel beside the neighbour words into a context-owned, grow-only
+ *   device buffer that *dev_map names.  *n_entries_before / *n_entries_after (each may be NULL) are set on every return: on a
+ *   refusal both hold the unchanged graph's entry count.  The map is valid until the next gnnpe_csr_apply_edges_map on the context,
+ *   a plain gnnpe_csr_apply_edges (of any batch), or any other call that loads or changes the context's rows.  A REFUSED batch
+ *   leaves the graph, the generation and the derived state as they were (the ABI 16 guarantee) and leaves the context WITHOUT a
+ *   valid map, *dev_map = NULL: the map of an earlier batch is gone too.  The empty batch (n_insert == n_delete == 0) succeeds,
+ *   leaves the graph and the generation alone as ABI 16 does, and produces the identity map, so a caller's loop needs no special
+ *   case.  *device_ms covers what gnnpe_csr_apply_edges's covers, the map included.
+ * gnnpe_csr_carry_entries: for r < n_rows and j' < entries_after, dst[r][j'] = src[r][map[j']], or 0 where the map says
+ *   GNNPE_NO_ENTRY, through the context's valid map.  src is row-major n_rows x entries_before, dst row-major n_rows x
+ *   entries_after, cells of elem_bytes = 8 (the count tables) or 4 (per-entry ids, truss numbers); both are the caller's device
+ *   memory on the context's device, aligned to their cells.  The work runs on the context's stream; every cell of dst is written
+ *   exactly once, src is not written.  GNNPE_ERR_ARG, with nothing launched: the context has no valid map (none was made, the last
+ *   gnnpe_csr_apply_edges_map was refused, or the rows were loaded or changed since), elem_bytes is neither 4 nor 8, a pointer is
+ *   null or misaligned while there is something to move, or the byte ranges of src and dst overlap.  n_rows == 0 or
+ *   entries_after == 0 succeeds and launches nothing.  The entries of D simply do not appear in dst.
+ *
+ * The loop for an edge table T (E = gnnpe_refine_sets_delta_edge_counts, EN = gnnpe_refine_sets_delta_nonedges_edge_counts, both
+ * with the caller's table as dev_accum; the EN terms in the induced modes only, where a mixed batch takes the two steps one after
+ * the other as the ABI 18 text requires):
+ *     T -= E(G, D);   gnnpe_csr_apply_edges_map(D);  T = carry(T);  T += EN(G', D)
+ *     T -= EN(G, I);  gnnpe_csr_apply_edges_map(I);  T = carry(T);  T += E(G', I)
+ * By the time of the carry the entries of D hold zero in T -- every match through an edge of D was subtracted by E(G, D) -- so
+ * dropping them loses nothing; the entries of I start from the zero the carry writes. */
+#define GNNPE_NO_ENTRY 0xFFFFFFFFu
+
+int gnnpe_host_csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint32_t *old_nbrs,
+                             const uint32_t *new_offsets, const uint32_t *new_nbrs, uint32_t *map);
+int gnnpe_csr_apply_edges_map(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint64_t n_insert,
+                              const uint32_t *delete_edges, uint64_t n_delete,
+                              uint64_t *n_entries_before, uint64_t *n_entries_after,
+                              void **dev_map, double *device_ms);
+int gnnpe_csr_carry_entries(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes,
+                            const void *dev_src, void *dev_dst, double *device_ms);
 
 /* ---- halo exchange helpers (device side of the RCCL all-to-all-v) ----------------- */
 /* List the vertices whose adjacency rows this context needs but does not hold -- every vertex referenced by

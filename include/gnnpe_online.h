@@ -336,7 +336,8 @@ int gnnpe_refine_sets_delta(gnnpe_ctx *ctx, const char *query_graph_path, const 
  *   - F = E(G) and nq >= 2: VD = V_m(C) and ED = E_m(C).
  *   - INSERTION IDENTITY, modes 0 and DISTINCT.  G' = G + F with F disjoint from E(G), the same C: as sets of maps
  *     M(G') = M(G) + Dset(G', F), disjoint.  Hence V(G') = V(G) + VD(G', F), and E(G') = E(G) + ED(G', F) compared by the key
- *     (x, y) of an entry -- the entry indices of G and G' differ; an entry of F has E(G) = 0.
+ *     (x, y) of an entry -- the entry indices of G and G' differ (gnnpe_csr_apply_edges_map of include/gnnpe_hip.h hands out the
+ *     map between them and gnnpe_csr_carry_entries moves a device table through it); an entry of F has E(G) = 0.
  *   - DELETION IDENTITY, the same modes.  V(G - D) = V(G) - VD(G, D), and the same for E by keys.
  *   - the INDUCED modes: the tables are "the matches on the loaded graph that touch F", nothing more (the caveat of ABI 15; ABI 18
  *     has the count of the other half and ABI 19 its tables, and with both an induced table is maintained exactly).
@@ -447,7 +448,9 @@ int gnnpe_refine_sets_delta_nonedges(gnnpe_ctx *ctx, const char *query_graph_pat
  *     insertion of F:  T -= tables of Nset(G, F);  gnnpe_csr_apply_edges(ctx, F, NULL);  T += tables of Dset(G', F)
  *     deletion  of D:  T -= tables of Dset(G, D);  gnnpe_csr_apply_edges(ctx, NULL, D);  T += tables of Nset(G', D)
  * keeps an induced vertex table exact on the device, and nothing per match leaves the device.  For an edge table the same holds by
- * the key (x, y) of an entry, as in ABI 17; carrying the entries of G to those of G' is the caller's.
+ * the key (x, y) of an entry, as in ABI 17; carrying the entries of G to those of G' is the caller's call of
+ * gnnpe_csr_carry_entries after gnnpe_csr_apply_edges_map in place of gnnpe_csr_apply_edges (include/gnnpe_hip.h, ABI 20, with the
+ * loop written out): on the device as well.
  *
  * All terms are those of the ABI 12 - 18 texts.  Nset_m(C, F) is the set ABI 18 counts (limit 2^64 - 1); m must contain
  * GNNPE_MATCH_INDUCED; F is a set of data vertex pairs that are NOT edges of the loaded graph, handed over as in ABI 18.  The query
