@@ -385,6 +385,9 @@ int finish_rows(gnnpe_ctx *c, uint64_t n_new, const uint32_t *dev_new_rows)
         GNNPE_HIP_TRY(hipGetLastError());
         uint64_t bad = 0;
         if ((rc = read_back_u64(c, d_bad, 4, &bad))) return rc;
+        // The ONLY GNNPE_ERR_ARG of this function, and it returns before anything is derived from the new rows (reverse
+        // positions, hub list): gnnpe_rows_append takes GNNPE_ERR_ARG from here as "rows refused, nothing else touched"
+        // and un-installs them.  A later refusal in this function would need a return code of its own.
         GNNPE_REQUIRE((uint32_t)bad == 0xFFFFFFFFu, GNNPE_ERR_ARG,
                       "adjacency row of vertex %u is not a strictly ascending list of ids < n without a self-loop "
                       "(the engine needs a simple graph with sorted rows, as graph.cpp:231-233 leaves them)", (uint32_t)bad);
@@ -2007,6 +2010,11 @@ int gnnpe_halo_need(gnnpe_ctx *c, uint32_t n_ranks, const uint32_t *bounds, void
     int rc = ensure_rank_arrays(c);
     if (rc) return rc;
     const uint32_t n = c->n;
+    // the owner search of k_need_owner is a binary search over these words
+    GNNPE_REQUIRE(bounds[0] == 0 && bounds[n_ranks] == n, GNNPE_ERR_ARG, "gnnpe_halo_need: slab bounds must run from 0 to n");
+    for (uint32_t r = 0; r < n_ranks; r++)
+        GNNPE_REQUIRE(bounds[r] <= bounds[r + 1], GNNPE_ERR_ARG, "gnnpe_halo_need: slab bounds must run from 0 to n (slab %u: [%u, %u))",
+                      r, bounds[r], bounds[r + 1]);
     for (uint32_t r = 0; r < n_ranks; r++) host_counts[r] = 0;
     if (n == 0) return GNNPE_OK;
     // layout of `mark`: mark[n] | key_in[n] | key_out[n] | (aligned) ids_in[n] | ids_out[n]
@@ -2116,14 +2124,33 @@ int gnnpe_rows_append(gnnpe_ctx *c, uint64_t n_rows, const void *dev_ids, const 
     c->graph_gen++;
     int rc;
     // scratch: src_off u64[n_rows+1] | dst_off u64[n_rows+1] | deg u32[n_rows+1] | kept u32[n_rows+1]
-    if ((rc = c->scratch.reserve((n_rows + 1) * 24 + 64))) return rc;
+    if ((rc = c->scratch.reserve((n_rows + 1) * 24 + 64)) || (rc = c->small.reserve(1024))) return rc;
     uint64_t *src_off = c->scratch.as<uint64_t>(), *dst_off = src_off + n_rows + 1;
     uint32_t *deg = reinterpret_cast<uint32_t *>(dst_off + n_rows + 1), *kept = deg + n_rows + 1;
+    // every id must be a vertex whose row is not held yet: k_install_rows indexes the vertex arrays with it, and a row
+    // installed twice (an owned one above all: min_rank would truncate it) loses paths without a word.  The word comes
+    // back with the degree sum, on the same wait.
+    uint32_t *d_bad = c->small.as<uint32_t>() + 8;
+    GNNPE_HIP_TRY(hipMemsetAsync(d_bad, 0xFF, 4, c->stream));
+    hipLaunchKernelGGL(k_check_new_ids, dim3(grid_for(n_rows)), dim3(kBlock), 0, c->stream, n_rows, (const uint32_t *)dev_ids,
+                       c->n, c->present.as<uint8_t>(), d_bad);
+    GNNPE_HIP_TRY(hipGetLastError());
     GNNPE_HIP_TRY(hipMemcpyAsync(deg, dev_deg, n_rows * 4, hipMemcpyDeviceToDevice, c->stream));
     GNNPE_HIP_TRY(hipMemsetAsync(deg + n_rows, 0, 4, c->stream));
     if ((rc = scan_u32_to_u64(c, deg, src_off, n_rows + 1))) return rc;
     uint64_t tot = 0;
+    c->h_pinned[1] = 0;
+    GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned + 1, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = read_back_u64(c, src_off + n_rows, 8, &tot))) return rc;
+    const uint32_t bad_pos = (uint32_t)c->h_pinned[1];
+    if (bad_pos != 0xFFFFFFFFu) {  // (the refusal alone pays a second read-back: the id at that position)
+        uint64_t v = 0;
+        if ((rc = read_back_u64(c, (const uint32_t *)dev_ids + bad_pos, 4, &v))) return rc;
+        GNNPE_REQUIRE((uint32_t)v < c->n, GNNPE_ERR_ARG, "gnnpe_rows_append: row %u is vertex %u, but the graph has %u vertices",
+                      bad_pos, (uint32_t)v, c->n);
+        GNNPE_REQUIRE(false, GNNPE_ERR_ARG, "gnnpe_rows_append: row %u is vertex %u, whose row this context already holds "
+                      "(gnnpe_halo_need lists what is missing)", bad_pos, (uint32_t)v);
+    }
     GNNPE_REQUIRE(tot == n_nbrs, GNNPE_ERR_ARG, "gnnpe_rows_append: degrees sum to %llu but %llu entries given",
                   (unsigned long long)tot, (unsigned long long)n_nbrs);
     uint64_t n_keep = n_nbrs;
@@ -2152,14 +2179,25 @@ int gnnpe_rows_append(gnnpe_ctx *c, uint64_t n_rows, const void *dev_ids, const 
                        (const uint32_t *)dev_ids, roff, c->nbr_used, c->adj_start.as<uint32_t>(),
                        c->adj_deg.as<uint32_t>(), c->present.as<uint8_t>());
     GNNPE_HIP_TRY(hipGetLastError());
-    const uint32_t first_new = c->n_held;
+    const uint32_t first_new = c->n_held, min_rank_was = c->halo_min_rank;
     c->halo_min_rank = std::max(c->halo_min_rank, min_rank);  // these rows lack their entries ranked below min_rank
     c->nbr_used += n_keep;
     c->n_held += (uint32_t)n_rows;
     c->nbr_vde_valid = false;
     c->counted = false;
     // validation, reverse positions and the hub list: graph structure, built when the rows arrive (synchronises)
-    return finish_rows(c, n_rows, c->held.as<uint32_t>() + first_new);
+    rc = finish_rows(c, n_rows, c->held.as<uint32_t>() + first_new);
+    if (rc == GNNPE_ERR_ARG) {
+        // a row was refused (finish_rows names its vertex) before anything was derived from the new rows: take all of
+        // them out again, so that the context holds what it held before the call
+        hipLaunchKernelGGL(k_uninstall_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, c->stream, n_rows,
+                           c->held.as<uint32_t>() + first_new, c->adj_deg.as<uint32_t>(), c->present.as<uint8_t>());
+        c->halo_min_rank = min_rank_was;
+        c->nbr_used -= n_keep;
+        c->n_held = first_new;
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return GNNPE_ERR_HIP;
+    }
+    return rc;
 }
 
 }  // extern "C"

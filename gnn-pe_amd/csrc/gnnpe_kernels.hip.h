@@ -51,6 +51,30 @@ __global__ void k_install_rows(uint64_t n_rows, const uint32_t *__restrict__ ids
     }
 }
 
+// gnnpe_rows_append, before anything is installed: bad[0] = smallest position k whose ids[k] is no vertex (>= n) or
+// names a row the context already holds (owned or halo); untouched when every id is new.  The id is compared with n
+// before it indexes `present`.
+__global__ void k_check_new_ids(uint64_t n_rows, const uint32_t *__restrict__ ids, uint32_t n,
+                                const uint8_t *__restrict__ present, uint32_t *__restrict__ bad)
+{
+    for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n_rows; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t v = ids[k];
+        if (v >= n || present[v]) atomicMin(bad, (uint32_t)k);
+    }
+}
+
+// gnnpe_rows_append, after the validation refused the rows it had installed: they are no rows of the context again
+// (every id was checked against n and `present` before the install, so none of them was held before)
+__global__ void k_uninstall_rows(uint64_t n_rows, const uint32_t *__restrict__ ids, uint32_t *__restrict__ deg,
+                                 uint8_t *__restrict__ present)
+{
+    for (uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; k < n_rows; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t v = ids[k];
+        deg[v] = 0;
+        present[v] = 0;
+    }
+}
+
 __global__ void k_gather_u32(uint64_t cnt, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ table,
                              uint32_t *__restrict__ out)
 {

@@ -240,7 +240,10 @@ int gnnpe_csr_carry_entries(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes
  * a row it holds: after gnnpe_rows_drop_halo these are the neighbours of its slab's start vertices (all that
  * l=2 needs); called again after gnnpe_rows_append they are the rows two hops out (l=3) -- grouped by owning rank: owner r holds the slab
  * [slab_bounds[r], slab_bounds[r+1]) of the processing order.  dev_ids receives the ids (capacity
- * cap entries), host_counts[r] the number per owner.  Ids are ascending inside each group. */
+ * cap entries), host_counts[r] the number per owner.  Ids are ascending inside each group.  A vertex whose row is held
+ * is never listed, so host_counts[own rank] = 0 and a second hop asks for nothing the first one brought.  At most 64
+ * ranks; slab_bounds must run from 0 to n without a step down (empty slabs own nothing), else GNNPE_ERR_ARG before
+ * anything is launched.  More than cap ids: GNNPE_ERR_ARG with the number needed in the message, nothing written. */
 int gnnpe_halo_need(gnnpe_ctx *ctx, uint32_t n_ranks, const uint32_t *host_slab_bounds, void *dev_ids,
                     uint64_t cap, uint64_t *host_counts);
 /* Degrees of requested rows (rows this context holds): dev_deg[k] = deg(dev_ids[k]). */
@@ -251,7 +254,18 @@ int gnnpe_rows_pack(gnnpe_ctx *ctx, uint64_t n_req, const void *dev_ids, void *d
  * the entries whose neighbour comes before processing position min_rank: a rank whose slab starts there never emits a
  * path that ends on one (kept iff rank[c] > rank[s]), so the LAST hop's halo rows can be truncated (l=2: the only hop;
  * l=3: pass 0 for the first hop).  Rows are validated (ids < n, ascending, no self-loop) and their reverse positions
- * and hub flags built here: the halo is graph structure and stays resident across steps. */
+ * and hub flags built here: the halo is graph structure and stays resident across steps.
+ * Refusals (GNNPE_ERR_ARG); after every one of them the context holds exactly the rows it held before the call (this
+ * covers the refusals only: after GNNPE_ERR_HIP the halo is unspecified -- gnnpe_rows_drop_halo, or load again):
+ *   - dev_ids[k] >= n, or a vertex whose row the context already holds, owned or halo (with min_rank > 0 a second copy
+ *     would truncate an owned row and paths would go missing): found on the device before anything is installed, the
+ *     message names the position and the vertex.  An id given TWICE INSIDE ONE CALL is not looked for (that would take
+ *     a second pass over the ids): the caller passes distinct ids, as gnnpe_halo_need lists them.
+ *   - the degrees do not sum to n_nbrs; the neighbour buffer is full; min_rank > 0 before gnnpe_set_order; a context
+ *     loaded by gnnpe_load_csr; more rows than vertices.
+ *   - a row that is not a strictly ascending list of ids < n without the vertex itself: found when the rows are
+ *     validated after the install, the message names the vertex, and ALL rows of the call are taken out again.  The
+ *     caller may append corrected rows, or gnnpe_rows_drop_halo and repeat the exchange. */
 int gnnpe_rows_append(gnnpe_ctx *ctx, uint64_t n_rows, const void *dev_ids, const void *dev_deg,
                       const void *dev_nbrs, uint64_t n_nbrs, uint32_t min_rank);
 
