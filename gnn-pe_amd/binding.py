@@ -57,6 +57,8 @@ SIGNATURES = {
     "gnnpe_host_csr_entry_map": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p]),
     "gnnpe_csr_apply_edges_map": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, C.POINTER(_vp), _f64p]),
     "gnnpe_csr_carry_entries": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _f64p]),
+    "gnnpe_set_vertex_labels": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_labels_download": (C.c_int, [_vp, _u32p]),
     "gnnpe_halo_need": (C.c_int, [_vp, C.c_uint32, _u32p, _vp, C.c_uint64, _u64p]),
     "gnnpe_rows_degree": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "gnnpe_rows_pack": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64]),
@@ -195,6 +197,10 @@ ONLINE_SIGNATURES = {
                                                                  _u64p, C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
     "gnnpe_refine_sets_delta_nonedges_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
                                                                C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
+    "gnnpe_host_refine_sets_delta_vertices": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p, C.c_uint64,
+                                                        C.c_uint64, C.c_uint32, _u64p]),
+    "gnnpe_refine_sets_delta_vertices": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
+                                                   C.c_uint64, _f64p]),
 }
 _online = None
 
@@ -437,9 +443,18 @@ def _delta_pairs(edges):
     return np.ascontiguousarray(e, np.uint32)
 
 
-def _host_sets(entry, g, query_path, bitmap, limit, mode=None, edges=None, shape=None):
+def _vertex_ids(vertices):
+    """S of the vertex-anchored calls as a contiguous uint32 array; ids that do not fit 32 bits are refused here"""
+    v = np.asarray(vertices, np.int64).reshape(-1)
+    if v.size and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+        raise GnnpeError("vertices: vertex ids are uint32")
+    return np.ascontiguousarray(v, np.uint32)
+
+
+def _host_sets(entry, g, query_path, bitmap, limit, mode=None, edges=None, shape=None, vertices=None):
     """One call of a host entry of the set-restricted refinement (include/gnnpe_online.h): g, the bitmap, F where `edges` is
-    given, the mode word unless `mode` is None (the two entries without one), and a zeroed table where `shape` is given.
+    given (S where `vertices` is), the mode word unless `mode` is None (the two entries without one), and a zeroed table where
+    `shape` is given.
     Returns answers, or with a table (answers, complete, counts); a refusal raises GnnpeError with the library's text."""
     lib = load()
     out, done = C.c_uint64(), C.c_int()
@@ -449,6 +464,9 @@ def _host_sets(entry, g, query_path, bitmap, limit, mode=None, edges=None, shape
     if edges is not None:
         e = _delta_pairs(edges)
         args += [_ptr(e, _u32p) if len(e) else None, len(e)]
+    if vertices is not None:
+        s = _vertex_ids(vertices)
+        args += [_ptr(s, _u32p) if len(s) else None, len(s)]
     args += [int(limit)] + ([] if mode is None else [mode]) + [C.byref(out)]
     if shape is not None:
         counts = np.zeros(shape, np.uint64)
@@ -507,6 +525,14 @@ def host_refine_sets_delta(g, query_path, bitmap, edges, limit=2 ** 64 - 1, dist
     of the mode that put at least one query edge on one of `edges` (pairs (x, y), either orientation, repeats tolerated), each
     match once, up to `limit`.  A pair that is no edge of g, a loop or an id outside g raises GnnpeError."""
     return _host_sets("gnnpe_host_refine_sets_delta", g, query_path, bitmap, limit, match_mode(distinct, induced), edges)
+
+
+def host_refine_sets_delta_vertices(g, query_path, bitmap, vertices, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """The matches through a set of data vertices on the host (include/gnnpe_online.h, DeltaV_m(C, S, limit)): the number of
+    matches of the mode with at least one image among `vertices` (ids, repeats tolerated), each match once, up to `limit`.  An id
+    outside g raises GnnpeError."""
+    return _host_sets("gnnpe_host_refine_sets_delta_vertices", g, query_path, bitmap, limit, match_mode(distinct, induced),
+                      vertices=vertices)
 
 
 def host_refine_sets_delta_vertex_counts(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
@@ -1140,6 +1166,21 @@ class Engine:
                                                        _ptr(rows, _u32p) if cap else None, cap, C.byref(ms)))
         return out.value, rows[:min(out.value, cap)], ms.value
 
+    def refine_sets_delta_vertices(self, query_path, bitmap, vertices, limit=2 ** 64 - 1, matches_cap=0, distinct=False, induced=False):
+        """The matches through a set of data vertices on the device (gnnpe_refine_sets_delta_vertices): (answers, rows, device ms).
+        answers = min(limit, the matches of the mode with at least one image among `vertices`), each match once; rows as
+        refine_sets_delta's.  `vertices`: ids of the loaded graph, repeats tolerated; an id the graph does not have is refused."""
+        out, ms = C.c_uint64(), C.c_double()
+        bm, s = _np(bitmap, np.uint32), _vertex_ids(vertices)
+        cap = min(int(matches_cap), int(limit))
+        nq = _bitmap_rows(bm, self.n)
+        rows = np.zeros((cap, nq), np.uint32)
+        self._ck(load_online().gnnpe_refine_sets_delta_vertices(self.ctx, query_path.encode(), _ptr(bm, _u32p),
+                                                                _ptr(s, _u32p) if len(s) else None, len(s), int(limit),
+                                                                match_mode(distinct, induced), C.byref(out),
+                                                                _ptr(rows, _u32p) if cap else None, cap, C.byref(ms)))
+        return out.value, rows[:min(out.value, cap)], ms.value
+
     def refine_sets_delta_nonedges(self, query_path, bitmap, pairs, limit=2 ** 64 - 1, matches_cap=0, distinct=False):
         """The induced matches on a set of non-edges on the device (gnnpe_refine_sets_delta_nonedges): (answers, rows, device ms).
         answers = min(limit, the induced matches -- with distinct=True of the INDUCED | DISTINCT mode -- that put at least one
@@ -1369,6 +1410,28 @@ class Engine:
         ptrs = [C.c_void_p(int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)) if p is not None else None for p in (src, dst)]
         self._ck(self.lib.gnnpe_csr_carry_entries(self.ctx, int(n_rows), int(elem_bytes), ptrs[0], ptrs[1], C.byref(ms) if timing else None))
         return ms.value if timing else None
+
+    def set_vertex_labels(self, vertices, labels, timing=False):
+        """gnnpe_set_vertex_labels: label(vertices[i]) = labels[i] on the whole graph on the device; afterwards the context is as
+        load_csr of the same rows with the new labels leaves it (the rows, the reverse positions and the hub list are not
+        rebuilt).  Returns None, the device ms with timing=True.  A refused call (an id outside the graph, one vertex with two
+        labels) raises GnnpeError and changes nothing; an empty list does nothing."""
+        v, lab = _vertex_ids(vertices), _vertex_ids(labels)
+        if len(v) != len(lab):
+            raise GnnpeError("set_vertex_labels: one label per vertex expected")
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_set_vertex_labels(self.ctx, _ptr(v, _u32p) if len(v) else None, _ptr(lab, _u32p) if len(v) else None,
+                                                  len(v), C.byref(ms) if timing else None))
+        if len(v):
+            self._rows_gen += 1  # device views of the count tables and of the entry map are stale
+            self.slab = (0, self.n)
+        return ms.value if timing else None
+
+    def download_labels(self):
+        """gnnpe_labels_download: the labels of the whole graph the context holds, n uint32"""
+        labels = np.zeros(self.n, np.uint32)
+        self._ck(self.lib.gnnpe_labels_download(self.ctx, _ptr(labels, _u32p)))
+        return labels
 
     def download_csr(self):
         """gnnpe_csr_download: (offsets, nbrs) of the whole graph the context holds, the arrays the edge-count tables index"""

@@ -1,7 +1,7 @@
 // gnnpe_refine_sets.hip.h -- what the set-restricted wave searches share: the one-shot k_refine_sets (gnnpe_refine_sets.hip),
 // k_refine_vcount, k_refine_ecount and k_refine_delta (the files of those names), k_refine_delta_vcount and k_refine_delta_ecount
 // (gnnpe_refine_delta_counts.hip), k_refine_delta_nonedges (gnnpe_refine_delta_nonedges.hip), k_refine_delta_nonedges_vcount and
-// k_refine_delta_nonedges_ecount (gnnpe_refine_delta_nonedges_counts.hip) and the paged k_refine_pages (gnnpe_refine_pages.hip).
+// k_refine_delta_nonedges_ecount (gnnpe_refine_delta_nonedges_counts.hip), k_refine_delta_vertices (the file of that name) and the paged k_refine_pages (gnnpe_refine_pages.hip).
 //   * All of them, on the device: the plan by position in the matching order, the per-wave search state in LDS and every STEP of the
 //     search: a chunk's lane test, the descent into a survivor, the decode of a first-level item, the single-vertex item.  On the
 //     host the preparation of a query (sets_prepare), the staging of its first-level items (sets_stage_items) and the choice of

@@ -37,6 +37,10 @@
 // word it moves, the stay-loop of a touched row knows st + p, an insert has none.  k_carry_entries (below) is a gather through it.
 //
 // Transient memory: a second neighbour array (and second adj_start / adj_deg); they stay with the context as the next call's spare.
+//
+// gnnpe_set_vertex_labels and gnnpe_labels_download (at the end) are the vertex half: new labels on a few vertices, with the rows,
+// the reverse positions and the hub list left standing.  k_set_labels patches labels[v] and, through revpos, the copy of v's label in
+// every neighbour's row; the host then runs the resets of gnnpe_load_csr's tail.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -247,6 +251,29 @@ __global__ __launch_bounds__(kBlock) void k_carry_entries(uint32_t n_rows, uint3
                 const uint64_t j = a + i * kBlock + threadIdx.x;
                 if (j < entries_after) d[j] = v[i];
             }
+        }
+    }
+}
+
+// gnnpe_set_vertex_labels: one wave per changed vertex v (each listed once, ids below n), lanes over its row.  labels[v] = the new
+// label, and for every entry q = (v -> u) of the row the copy of v's label in u's row: the entry (u -> v) sits at
+// adj_start[u] + revpos[q].  Two changed vertices that are neighbours write different words, so nothing is ordered.  A reverse
+// position outside u's row (an entry without its mirror) is skipped: no store leaves the row it belongs to.
+static __global__ __launch_bounds__(kBlock) void k_set_labels(uint32_t count, const uint32_t *__restrict__ verts,
+                                                              const uint32_t *__restrict__ new_labels, const uint32_t *__restrict__ adj_start,
+                                                              const uint32_t *__restrict__ adj_deg, const uint32_t *__restrict__ nbrs,
+                                                              const uint32_t *__restrict__ revpos, uint32_t *__restrict__ labels,
+                                                              uint32_t *__restrict__ nbr_label)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves = gridDim.x * (kBlock / 64);
+    for (uint32_t t = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); t < count; t += waves) {
+        const uint32_t v = verts[t], lab = new_labels[t];
+        const uint32_t st = adj_start[v], d = adj_deg[v];
+        if (lane == 0) labels[v] = lab;
+        for (uint32_t i = lane; i < d; i += 64) {
+            const uint32_t u = nbrs[st + i], r = revpos[st + i];
+            if (r < adj_deg[u]) nbr_label[adj_start[u] + r] = lab;
         }
     }
 }
@@ -562,6 +589,66 @@ extern "C" int gnnpe_csr_carry_entries(gnnpe_ctx *c, uint32_t n_rows, uint32_t e
                            c->upd_map.as<uint32_t>(), static_cast<const uint32_t *>(dev_src), static_cast<uint32_t *>(dev_dst));
     GNNPE_HIP_TRY(hipGetLastError());
     return timer.end(c->stream);
+}
+
+extern "C" int gnnpe_set_vertex_labels(gnnpe_ctx *c, const uint32_t *vertices, const uint32_t *labels, uint64_t count, double *device_ms)
+{
+    const char *who = "gnnpe_set_vertex_labels";
+    GNNPE_REQUIRE(c && ((vertices && labels) || count == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    if (device_ms) *device_ms = 0.0;
+    int rc = require_whole_graph(who, c);
+    if (rc) return rc;
+    if (count == 0) return GNNPE_OK;  // nothing changes and nothing is launched
+    const uint32_t n = c->n;
+    // every (vertex, label) pair once; a vertex with two labels is refused
+    std::vector<ukey> pairs(count);
+    for (uint64_t i = 0; i < count; i++) {
+        GNNPE_REQUIRE(vertices[i] < n, GNNPE_ERR_ARG, "%s: vertex %u is not a vertex of the graph (n = %u)", who, vertices[i], n);
+        pairs[i] = ((ukey)vertices[i] << 32) | labels[i];
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    const size_t k = pairs.size();
+    std::vector<uint32_t> up(2 * k);
+    for (size_t i = 0; i < k; i++) {
+        GNNPE_REQUIRE(i == 0 || (uint32_t)(pairs[i] >> 32) != (uint32_t)(pairs[i - 1] >> 32), GNNPE_ERR_ARG,
+                      "%s: vertex %u is listed with the labels %u and %u", who, (uint32_t)(pairs[i] >> 32), (uint32_t)pairs[i - 1], (uint32_t)pairs[i]);
+        up[i] = (uint32_t)(pairs[i] >> 32);
+        up[k + i] = (uint32_t)pairs[i];
+    }
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->upd_work.reserve(2 * k * 4))) return rc;
+    uint32_t *d_verts = c->upd_work.as<uint32_t>(), *d_labels = d_verts + k;
+    GNNPE_HIP_TRY(hipMemcpyAsync(d_verts, up.data(), 2 * k * 4, hipMemcpyHostToDevice, c->stream));
+    LaunchTimer timer;
+    if ((rc = timer.begin(device_ms, c->stream))) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((k + kBlock / 64 - 1) / (kBlock / 64), (uint64_t)c->num_cus * 16);
+    hipLaunchKernelGGL(k_set_labels, dim3(grid), dim3(kBlock), 0, c->stream, (uint32_t)k, d_verts, d_labels, c->adj_start.as<uint32_t>(),
+                       c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->revpos.as<uint32_t>(), c->labels.as<uint32_t>(),
+                       c->nbr_label.as<uint32_t>());
+    GNNPE_HIP_TRY(hipGetLastError());
+    if ((rc = timer.end(c->stream))) return rc;
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));  // (the host lists go out of scope)
+    // exactly the tail of gnnpe_load_csr; the rows, the reverse positions and the hub list stand
+    c->graph_gen++;
+    c->slab_begin = 0;
+    c->slab_end = n;
+    c->slab_set = false;
+    c->have_order = false;
+    invalidate_derived(c);
+    return GNNPE_OK;
+}
+
+extern "C" int gnnpe_labels_download(gnnpe_ctx *c, uint32_t *host_labels)
+{
+    const char *who = "gnnpe_labels_download";
+    GNNPE_REQUIRE(c && host_labels, GNNPE_ERR_ARG, "%s: null argument", who);
+    int rc = require_whole_graph(who, c);
+    if (rc) return rc;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    if (c->n) GNNPE_HIP_TRY(hipMemcpyAsync(host_labels, c->labels.p, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    return GNNPE_OK;
 }
 
 extern "C" int gnnpe_csr_download(gnnpe_ctx *c, uint32_t *host_offsets, uint32_t *host_nbrs, uint64_t nbrs_cap, uint64_t *n_entries)

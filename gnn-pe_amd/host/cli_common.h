@@ -65,6 +65,13 @@ struct Options {
     // --apply-edges FILE (exact -m online / -m filter only): lines `+ x y` / `- x y`, a batch of edge insertions and deletions
     // applied to the loaded data graph on the device before anything is computed from it (gnnpe_csr_apply_edges)
     std::string apply_edges_file;
+    // --delta-vertices FILE (needs --refine sets; with --distinct, --induced and --matches, not with --delta-edges, --delta-nonedges,
+    // --all-matches or the count tables): one data vertex id per line; the answer is the matches with at least one image among
+    // them, each once (gnnpe_refine_sets_delta_vertices)
+    std::string delta_vertices_file;
+    // --set-labels FILE (exact -m online / -m filter only): lines `v label`, new labels for those data vertices, set on the device
+    // after --apply-edges and before anything is computed from the graph (gnnpe_set_vertex_labels)
+    std::string set_labels_file;
     bool induced = false;   // --induced (needs --refine sets): induced matching, query non-edges on data non-edges (GNNPE_MATCH_INDUCED)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
@@ -144,7 +151,8 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE)\n"
-                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE]] [--apply-edges FILE]\n"
+                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE] | --delta-vertices FILE] [--apply-edges FILE]\n"
+                   "           [--set-labels FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -171,7 +179,12 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --apply-edges FILE (exact mode only: --exact or -l 3): FILE has one line `+ x y` (insert the edge) or `- x y`\n"
                    "       (delete it) per edge; the batch is applied to the data graph on the device and the query runs on the result:\n"
                    "       the metadata block and the rows of --edge-counts / --vertex-counts and of their --delta forms\n"
-                   "       are the updated graph's\n",
+                   "       are the updated graph's;\n"
+                   "       --delta-vertices FILE (needs --refine sets; combines with --distinct, --induced and --matches, not with\n"
+                   "       --delta-edges, --delta-nonedges, --all-matches or the count tables): FILE has one data vertex id per line; the\n"
+                   "       answer is the number of matches with at least one image among them, each match once, and --matches writes those;\n"
+                   "       --set-labels FILE (exact mode only: --exact or -l 3): FILE has one line `v label` per vertex; the labels are set\n"
+                   "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's\n",
                    tool, tool);
             exit(0);
         }
@@ -190,7 +203,8 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         }
         if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges" ||
             a == "--delta-nonedges" ||
-            a == "--apply-edges" || a == "--delta-vertex-counts" || a == "--delta-edge-counts") {
+            a == "--apply-edges" || a == "--delta-vertex-counts" || a == "--delta-edge-counts" || a == "--delta-vertices" ||
+            a == "--set-labels") {
             if (i + 1 >= argc) die(a + " needs a value");
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }
             if (a == "--vertex-counts") { o.vertex_counts_file = argv[++i]; continue; }
@@ -200,6 +214,8 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             if (a == "--delta-vertex-counts") { o.delta_vertex_counts_file = argv[++i]; continue; }
             if (a == "--delta-edge-counts") { o.delta_edge_counts_file = argv[++i]; continue; }
             if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; continue; }
+            if (a == "--delta-vertices") { o.delta_vertices_file = argv[++i]; continue; }
+            if (a == "--set-labels") { o.set_labels_file = argv[++i]; continue; }
             o.refine = argv[++i];
             if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;

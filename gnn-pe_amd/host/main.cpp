@@ -25,6 +25,7 @@
 #include <chrono>
 #include <climits>
 #include <condition_variable>
+#include <map>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -212,6 +213,36 @@ std::vector<uint32_t> read_delta_edges(const std::string &path)
     return pairs;
 }
 
+// S of --delta-vertices: one vertex id per line
+std::vector<uint32_t> read_vertex_list(const std::string &path)
+{
+    std::vector<uint32_t> ids;
+    FILE *vf = fopen(path.c_str(), "r");
+    if (!vf) die("cannot read " + path);
+    for (unsigned long long v;;) {
+        const int got = fscanf(vf, "%llu", &v);
+        if (got == EOF) break;
+        if (got != 1 || v > 0xFFFFFFFFull) die(path + ": one vertex id per line expected");
+        ids.push_back((uint32_t)v);
+    }
+    fclose(vf);
+    return ids;
+}
+
+// the file of --set-labels: one `v label` per line
+void read_label_list(const std::string &path, std::vector<uint32_t> *vs, std::vector<uint32_t> *ls)
+{
+    FILE *lf = fopen(path.c_str(), "r");
+    if (!lf) die("cannot read " + path);
+    unsigned long long v = 0, lab = 0;
+    for (int got; (got = fscanf(lf, "%llu %llu", &v, &lab)) != EOF;) {
+        if (got != 2 || v > 0xFFFFFFFFull || lab > 0xFFFFFFFFull) die(path + ": one `v label` per line expected");
+        vs->push_back((uint32_t)v);
+        ls->push_back((uint32_t)lab);
+    }
+    fclose(lf);
+}
+
 // the file of --matches: one match per line, the images of the query vertices in their order
 struct MatchFile {
     const std::string &path;
@@ -244,8 +275,9 @@ struct MatchFile {
 //   --delta-nonedges FILE    gnnpe_refine_sets_delta_nonedges: the induced matches that put a non-adjacent query pair on one of
 //                            the listed non-edges, each once; with --delta-vertex-counts / --delta-edge-counts FILE
 //                            gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts, the count tables of those matches
+//   --delta-vertices FILE    gnnpe_refine_sets_delta_vertices: the matches with an image among the listed data vertices, each once
 //   none of these            gnnpe_refine_sets_mode
-// The three one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
+// The four one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
 struct Refinement {
     void *online = nullptr;  // the library's handle
     uint64_t answers = 0, n_written = 0, n_pages = 0;
@@ -332,6 +364,10 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
         const std::vector<uint32_t> pairs = read_delta_edges(o.delta_nonedges_file);
         check(ONLINE(gnnpe_refine_sets_delta_nonedges)(ctx, query, bitmap.data(), pairs.data(), pairs.size() / 2, limit, match_mode, &r.answers,
                                                        cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta_nonedges");
+    } else if (!o.delta_vertices_file.empty()) {
+        const std::vector<uint32_t> ids = read_vertex_list(o.delta_vertices_file);
+        check(ONLINE(gnnpe_refine_sets_delta_vertices)(ctx, query, bitmap.data(), ids.data(), ids.size(), limit, match_mode, &r.answers,
+                                                       cap ? rows.data() : nullptr, cap, &r.refine_ms), "refine_sets_delta_vertices");
     } else {
         check(ONLINE(gnnpe_refine_sets_mode)(ctx, query, bitmap.data(), limit, match_mode, &r.answers, cap ? rows.data() : nullptr, cap,
                                              &r.refine_ms), "refine_sets");
@@ -369,9 +405,9 @@ int run_filter(const Options &o)
     if (rc != 0) die(o.data_graph + ": " + err);
     if (exact && o.mode == "online" && !g.simple)  // the refinement counts embeddings in simple graphs only (gnnpe_refine)
         die(o.data_graph + " repeats an edge (duplicate `e` lines): exact -m online (--exact, -l 3) needs a simple graph");
-    // with --apply-edges the metadata block and the plan size are printed once the batch is applied: they describe the graph
-    // the answer is for
-    const bool updating = !o.apply_edges_file.empty();
+    // with --apply-edges or --set-labels the metadata block and the plan size are printed once the batch is applied and the labels
+    // are set: they describe the graph the answer is for
+    const bool updating = !o.apply_edges_file.empty() || !o.set_labels_file.empty();
     if (!updating) fputs(g.metadata_text().c_str(), stdout);
     std::vector<uint32_t> sorted_nodes, membership;
     if (gnnpe_host::read_membership(o.dataset_path + "gnn-pe/membership.txt", g.n, o.partition_num, &sorted_nodes,
@@ -394,11 +430,8 @@ int run_filter(const Options &o)
     if (gnnpe_device_count() <= 0) die("no HIP device: this tool has no CPU fallback");
     gnnpe_ctx *ctx = gnnpe_create(0);
     if (!ctx) die(std::string("gnnpe_create: ") + gnnpe_last_error());
-    const uint32_t n_labels = std::max<uint32_t>(g.labels_count, 1);
-    std::vector<double> table((size_t)n_labels * o.vde_dim);
-    check(gnnpe_host_label_table(n_labels, o.vde_dim, table.data()), "label table");
     check(load_graph_into(ctx, g), "load_csr");
-    if (updating) {  // the whole query runs on the updated graph
+    if (!o.apply_edges_file.empty()) {  // the whole query runs on the updated graph
         std::vector<uint32_t> ins, del;
         FILE *af = fopen(o.apply_edges_file.c_str(), "r");
         if (!af) die("cannot read " + o.apply_edges_file);
@@ -420,9 +453,30 @@ int run_filter(const Options &o)
         g.m = (uint32_t)(entries / 2);
         g.max_degree = 0;
         for (uint32_t v = 0; v < g.n; v++) g.max_degree = std::max(g.max_degree, g.offsets[v + 1] - g.offsets[v]);
+    }
+    if (!o.set_labels_file.empty()) {  // ... and on the relabelled one
+        std::vector<uint32_t> vs, ls;
+        read_label_list(o.set_labels_file, &vs, &ls);
+        check(gnnpe_set_vertex_labels(ctx, vs.data(), ls.data(), vs.size(), nullptr), "--set-labels");
+        // the host copy follows the device, with the label figures of the metadata block (graph.cpp:223)
+        check(gnnpe_labels_download(ctx, g.labels.data()), "labels_download");
+        std::map<uint32_t, uint32_t> freq;
+        uint32_t max_label = 0;
+        for (uint32_t x = 0; x < g.n; x++) {
+            freq[g.labels[x]]++;
+            max_label = std::max(max_label, g.labels[x]);
+        }
+        g.labels_count = std::max<uint32_t>((uint32_t)freq.size(), g.n ? max_label + 1 : 0);
+        g.max_label_frequency = 0;
+        for (const auto &kv : freq) g.max_label_frequency = std::max(g.max_label_frequency, kv.second);
+    }
+    if (updating) {
         fputs(g.metadata_text().c_str(), stdout);
         printf("%u\n", n_qp);
     }
+    const uint32_t n_labels = std::max<uint32_t>(g.labels_count, 1);
+    std::vector<double> table((size_t)n_labels * o.vde_dim);
+    check(gnnpe_host_label_table(n_labels, o.vde_dim, table.data()), "label table");
     check(gnnpe_set_order(ctx, sorted_nodes.data(), membership.data(), o.partition_num), "set_order");
     check(gnnpe_set_label_table(ctx, n_labels, o.vde_dim, table.data()), "set_label_table");
     check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
@@ -558,6 +612,15 @@ int main(int argc, char **argv)
         if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty())
             die("--delta-nonedges excludes --all-matches, --vertex-counts and --edge-counts");
     }
+    if (!o.delta_vertices_file.empty()) {
+        if (o.refine != "sets") die("--delta-vertices needs --refine sets");
+        if (!o.delta_edges_file.empty() || !o.delta_nonedges_file.empty())
+            die("--delta-vertices excludes --delta-edges and --delta-nonedges");
+        if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty() || !o.delta_vertex_counts_file.empty() ||
+            !o.delta_edge_counts_file.empty())
+            die("--delta-vertices excludes --all-matches and the count tables");
+        (void)read_vertex_list(o.delta_vertices_file);  // a malformed file is refused before a GPU is touched
+    }
     for (const char *flag : {"--delta-vertex-counts", "--delta-edge-counts"}) {
         const bool edge_table = std::string(flag) == "--delta-edge-counts";
         if ((edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file).empty()) continue;
@@ -572,6 +635,13 @@ int main(int argc, char **argv)
     if (!o.apply_edges_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
         die("--apply-edges applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
             "made from the graph as it was");
+    if (!o.set_labels_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
+        die("--set-labels applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
+            "made from the graph as it was");
+    if (!o.set_labels_file.empty()) {  // a malformed file is refused before a GPU is touched
+        std::vector<uint32_t> vs, ls;
+        read_label_list(o.set_labels_file, &vs, &ls);
+    }
     if (o.refine == "sets" && !(o.exact || o.path_length == 3))
         die("--refine sets needs complete candidate sets: add --exact or use -l 3 (the reference-mode filter's sets miss "
             "embeddings, and only the start vertex's set may restrict the search there)");

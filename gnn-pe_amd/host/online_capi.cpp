@@ -73,7 +73,7 @@ int gnnpe_host_refine(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs,
 static int host_sets(const char *who, gnnpe_host::SetsJob::Table table, bool through, uint32_t n, const uint32_t *offsets,
                      const uint32_t *nbrs, const uint32_t *labels, const char *query_graph_path, const uint32_t *candidate_bitmap,
                      const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers, int *complete,
-                     uint64_t *counts, bool nonedges = false)
+                     uint64_t *counts, bool nonedges = false, bool vertices = false)
 {
     const bool has_table = table != gnnpe_host::SetsJob::kNoTable;
     if (!offsets || !nbrs || !labels || !query_graph_path || !candidate_bitmap || !answers || (has_table && !complete) ||
@@ -102,10 +102,13 @@ static int host_sets(const char *who, gnnpe_host::SetsJob::Table table, bool thr
     }
     job.induced = (mode & GNNPE_MATCH_INDUCED) != 0;
     job.table = table;
-    job.through = through;
+    job.through = through && !vertices;
     job.nonedges = nonedges;
-    job.delta_edges = delta_edges;
-    job.n_delta = n_delta;
+    job.delta_edges = vertices ? nullptr : delta_edges;
+    job.n_delta = vertices ? 0 : n_delta;
+    job.through_vertices = vertices;  // (S travels in the arguments of F: n_delta ids)
+    job.vertices = vertices ? delta_edges : nullptr;
+    job.n_vertices = vertices ? n_delta : 0;
     std::string err;
     bool done = false;
     if (gnnpe_host::refine_sets_run(g, q, candidate_bitmap, ((uint64_t)n + 31) / 32, limit, job, answers, &done, counts, &err) != 0) {
@@ -204,6 +207,15 @@ int gnnpe_host_refine_sets_delta_nonedges_edge_counts(uint32_t n, const uint32_t
 {
     return host_sets("gnnpe_host_refine_sets_delta_nonedges_edge_counts", gnnpe_host::SetsJob::kEdgeTable, true, n, offsets, nbrs, labels,
                      query_graph_path, candidate_bitmap, pairs, n_pairs, limit, mode, answers, complete, counts, true);
+}
+
+// (the twelfth: S, a set of data vertices, in the place of F)
+int gnnpe_host_refine_sets_delta_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                          const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *vertices,
+                                          uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers)
+{
+    return host_sets("gnnpe_host_refine_sets_delta_vertices", gnnpe_host::SetsJob::kNoTable, true, n, offsets, nbrs, labels, query_graph_path,
+                     candidate_bitmap, vertices, n_vertices, limit, mode, answers, nullptr, nullptr, false, true);
 }
 
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)

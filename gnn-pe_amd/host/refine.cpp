@@ -134,6 +134,22 @@ int build_match_order_from_pair(const StaticGraph &query, uint32_t a, uint32_t b
     return grow_match_order(query, seen, out, err);
 }
 
+int build_match_order_from_vertex(const StaticGraph &query, uint32_t u, MatchOrder *out, std::string *err)
+{
+    const uint32_t nq = query.n;
+    if (!out || u >= nq) {
+        if (err) *err = "build_match_order_from_vertex: u must be a vertex of the query";
+        return -2;
+    }
+    out->order.assign(1, u);
+    out->pivot.assign(1, u);
+    out->back.clear();
+    out->back_off.assign(2, 0);
+    std::vector<uint8_t> seen(nq, 0);
+    seen[u] = 1;
+    return grow_match_order(query, seen, out, err);
+}
+
 int refine_count(const StaticGraph &data, const StaticGraph &query, const std::vector<std::vector<uint32_t>> &cand,
                  uint64_t limit, uint64_t *answers, std::string *err)
 {

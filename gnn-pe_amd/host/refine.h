@@ -40,6 +40,10 @@ int build_match_order_from_edge(const StaticGraph &query, uint32_t a, uint32_t b
 // refused.
 int build_match_order_from_pair(const StaticGraph &query, uint32_t a, uint32_t b, MatchOrder *out, std::string *err);
 
+// The same order anchored at a query VERTEX: order[0] = u, then the rule above with its ties, pivots and back lists (a single-vertex
+// query is that position alone).  u must be a vertex of the query; a disconnected query is refused.
+int build_match_order_from_vertex(const StaticGraph &query, uint32_t u, MatchOrder *out, std::string *err);
+
 // candidates[u] = ascending data vertex ids of query vertex u.  Returns 0 and *answers, or <0 with *err
 // (disconnected query graph, size mismatch).
 int refine_count(const StaticGraph &data, const StaticGraph &query, const std::vector<std::vector<uint32_t>> &candidates,

@@ -26,6 +26,7 @@ struct SetSearch {
     std::vector<std::pair<uint32_t, uint32_t>> qedges;  // query_edges(q), for ecounts
     std::vector<std::pair<uint32_t, uint32_t>> anchors;  // delta: the query pairs looked up in F -- query_edges(q), or query_nonedges(q)
     const std::vector<uint64_t> *delta = nullptr;       // delta: ascending keys (min << 32) | max; a find with no anchor on one is dropped
+    const std::vector<uint8_t> *in_s = nullptr;         // vertices: a byte per data vertex, 1 = in S; a find with no image in S is dropped
 
     bool in_set(uint32_t u, uint32_t v) const { return (bitmap[(size_t)u * words + (v >> 5)] >> (v & 31)) & 1u; }
     bool fits(uint32_t u, uint32_t v) const
@@ -44,6 +45,11 @@ struct SetSearch {
                 bool touches = false;
                 for (size_t k = 0; k < anchors.size() && !touches; k++)
                     touches = std::binary_search(delta->begin(), delta->end(), delta_key(image[anchors[k].first], image[anchors[k].second]));
+                if (!touches) return;
+            }
+            if (in_s) {
+                bool touches = false;
+                for (uint32_t u = 0; u < q.n && !touches; u++) touches = (*in_s)[image[u]] != 0;
                 if (!touches) return;
             }
             count++;
@@ -89,9 +95,10 @@ struct SetSearch {
 }  // namespace
 
 // The walk of refine_sets_run: a table (of job.table's kind, zeroed) is filled at the finds; a find that touches no edge of
-// `delta` (F as ascending keys) is dropped
+// `delta` (F as ascending keys) is dropped, and so is one with no image in `in_s` (S as a byte mask)
 static int refine_sets_walk(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
-                            const SetsJob &job, uint64_t *table, const std::vector<uint64_t> *delta, uint64_t *answers, std::string *err)
+                            const SetsJob &job, uint64_t *table, const std::vector<uint64_t> *delta, const std::vector<uint8_t> *in_s,
+                            uint64_t *answers, std::string *err)
 {
     const uint32_t nq = query.n;
     const auto *pairs = job.pairs;
@@ -109,7 +116,7 @@ static int refine_sets_walk(const StaticGraph &data, const StaticGraph &query, c
                 std::vector<std::vector<uint32_t>>(nq), std::vector<std::vector<uint32_t>>(nq), std::vector<uint32_t>(nq, 0),
                 std::vector<uint8_t>(data.n, 0), 0, limit, vcounts, ecounts,
                 ecounts ? query_edges(query) : std::vector<std::pair<uint32_t, uint32_t>>(),
-                !delta ? std::vector<std::pair<uint32_t, uint32_t>>() : job.nonedges ? query_nonedges(query) : query_edges(query), delta};
+                !delta ? std::vector<std::pair<uint32_t, uint32_t>>() : job.nonedges ? query_nonedges(query) : query_edges(query), delta, in_s};
     for (uint32_t i = 0; i < nq; i++) s.back.emplace_back(mo.back.begin() + mo.back_off[i], mo.back.begin() + mo.back_off[i + 1]);
     // every earlier query vertex but the pivot and the back neighbours is a non-neighbour: tested after the back edges
     for (uint32_t i = 1; job.induced && i < nq; i++)
@@ -192,6 +199,24 @@ int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, s
     return 0;
 }
 
+int delta_vertex_ids(uint32_t n, const uint32_t *vertices, uint64_t n_vertices, std::vector<uint32_t> *ids, std::string *err)
+{
+    ids->clear();
+    if (n_vertices && !vertices) {
+        if (err) *err = "vertices: null argument";
+        return -2;
+    }
+    for (uint64_t i = 0; i < n_vertices; i++)
+        if (vertices[i] >= n) {
+            if (err) *err = "vertex " + std::to_string(i) + " (" + std::to_string(vertices[i]) + "): a vertex id the graph does not have";
+            return -2;
+        }
+    ids->assign(vertices, vertices + n_vertices);
+    std::sort(ids->begin(), ids->end());
+    ids->erase(std::unique(ids->begin(), ids->end()), ids->end());
+    return 0;
+}
+
 // F as ascending keys, each a checked edge of the graph -- or, with `nonedges`, each checked NOT to be one: what a job through F
 // refuses
 static int delta_keys_checked(const StaticGraph &data, const uint32_t *delta_edges, uint64_t n_delta, bool nonedges,
@@ -228,10 +253,22 @@ int refine_sets_run(const StaticGraph &data, const StaticGraph &query, const uin
         return -2;
     }
     if (job.through && delta_keys_checked(data, job.delta_edges, job.n_delta, job.nonedges, &keys, err) != 0) return -2;
+    std::vector<uint32_t> ids;
+    std::vector<uint8_t> in_s;
+    if (job.through_vertices) {
+        if (job.through) {
+            if (err) *err = "a job through a set of edges or through a set of vertices, not both";
+            return -2;
+        }
+        if (delta_vertex_ids(data.n, job.vertices, job.n_vertices, &ids, err) != 0) return -2;
+        in_s.assign(data.n, 0);
+        for (uint32_t v : ids) in_s[v] = 1;
+    }
     if (cells) std::fill(counts, counts + cells, 0ull);
-    // (an empty F drops every find: limit 0, and the walk still refuses what it refuses)
-    const int rc = refine_sets_walk(data, query, bitmap, words, job.through && keys.empty() ? 0 : limit, job, cells ? counts : nullptr,
-                                    job.through ? &keys : nullptr, answers, err);
+    // (an empty F or S drops every find: limit 0, and the walk still refuses what it refuses)
+    const bool nothing = (job.through && keys.empty()) || (job.through_vertices && ids.empty());
+    const int rc = refine_sets_walk(data, query, bitmap, words, nothing ? 0 : limit, job, cells ? counts : nullptr,
+                                    job.through ? &keys : nullptr, job.through_vertices ? &in_s : nullptr, answers, err);
     // the walk stops at `limit` finds: below it, it walked everything (limit 0 walks nothing, and 0 < 0 is false; no F: 0 < limit)
     if (rc == 0 && complete) *complete = *answers < limit;
     return rc;

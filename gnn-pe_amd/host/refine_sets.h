@@ -52,6 +52,7 @@ inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words,
 //   all of M (through = false)                  R, D, I, ID         V_m(C)         E_m(C)
 //   the maps through F (through = true)         Delta_m(C, F)       VDelta_m(C, F) EDelta_m(C, F)
 //   ... F of non-edges (nonedges = true)        N_m(C, F)           VN_m(C, F)     EN_m(C, F)
+//   the maps with an image in S (through_vertices)  DeltaV_m(C, S)   (a table is filled as for any other job; no entry asks for one)
 struct SetsJob {
     const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr;
     bool induced = false;
@@ -62,6 +63,10 @@ struct SetsJob {
                             // is filled as for any other job (the rows of the edge table are still the query EDGES)
     const uint32_t *delta_edges = nullptr;  // F: n_delta pairs (x, y), either orientation, repeats tolerated; read where `through`
     uint64_t n_delta = 0;
+    bool through_vertices = false;  // only the maps with at least one image in S = `vertices`, each once: DeltaV_m(C, S) of
+                                    // include/gnnpe_online.h.  One test at every find against a byte mask of S; not with `through`
+    const uint32_t *vertices = nullptr;  // S: n_vertices ids, repeats tolerated; read where `through_vertices`
+    uint64_t n_vertices = 0;
 };
 
 // The query edges as include/gnnpe_online.h numbers them: (a_k, b_k) with a_k < b_k, lexicographically ascending, each once.
@@ -77,6 +82,10 @@ inline uint64_t delta_key(uint32_t x, uint32_t y) { return ((uint64_t)std::min(x
 // tolerated.  A loop or an id >= n returns <0 with *err; whether a pair is an edge of the graph is not looked at here.
 int delta_edge_keys(uint32_t n, const uint32_t *delta_edges, uint64_t n_delta, std::vector<uint64_t> *keys, std::string *err);
 
+// S of the vertex-anchored calls as ascending ids, each once: vertices holds n_vertices ids, repeats tolerated.  An id >= n returns
+// <0 with *err.
+int delta_vertex_ids(uint32_t n, const uint32_t *vertices, uint64_t n_vertices, std::vector<uint32_t> *ids, std::string *err);
+
 // The cells of a job's table: query.n * data.n, query edges * adjacency entries, or 0 without a table.  A query without an edge
 // has no edge table.
 size_t sets_table_cells(const StaticGraph &data, const StaticGraph &query, SetsJob::Table table);
@@ -90,7 +99,8 @@ size_t sets_table_cells(const StaticGraph &data, const StaticGraph &query, SetsJ
 // edge of the graph (binary search in the data row; with `nonedges` a pair that IS one) -- with counts still untouched; then the table is zeroed; then the walk refuses
 // a bitmap of other than `words` words per row, an ordering pair outside the query and a disconnected query graph, whatever the
 // limit, leaving the zeroed table.  An empty F drops every find: the walk runs with limit 0 and still refuses what it refuses,
-// *answers is 0 and *complete is 0 < limit.
+// *answers is 0 and *complete is 0 < limit.  S of a `through_vertices` job is checked where F is (an id >= data.n, or both flags set, is
+// refused), and an empty S drops every find in the same way.
 int refine_sets_run(const StaticGraph &data, const StaticGraph &query, const uint32_t *bitmap, uint64_t words, uint64_t limit,
                     const SetsJob &job, uint64_t *answers, bool *complete, uint64_t *counts, std::string *err);
 

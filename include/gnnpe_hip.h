@@ -235,6 +235,36 @@ int gnnpe_csr_apply_edges_map(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint
 int gnnpe_csr_carry_entries(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes,
                             const void *dev_src, void *dev_dst, double *device_ms);
 
+/* ---- vertex relabel on the resident graph -----------------------------------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section and gnnpe_refine_sets_delta_vertices of include/gnnpe_online.h only add
+ * symbols.)
+ * gnnpe_csr_apply_edges changes the edges and keeps the labels; these calls are the other half: new labels on a few vertices of the
+ * whole graph the context holds, from the few bytes that name them, where gnnpe_load_csr uploads every row to change four bytes.
+ * It is the middle step of the relabel loop that gnnpe_refine_sets_delta_vertices exists for:
+ *     lost = DeltaV(G, C, S);  gnnpe_set_vertex_labels(ctx, S, labels');  gained = DeltaV(G', C', S);  |M'| = |M| - lost + gained.
+ *
+ * vertices / labels: count uint32 each, label(vertices[i]) becomes labels[i].  The same (vertex, label) pair repeated means it once.
+ *
+ * Result.  The same rows, with the new labels.  State after a successful call: precisely what gnnpe_load_csr(ctx, n, offsets, nbrs,
+ * labels') leaves.  The CSR arrays, the reverse positions and the hub-row list are not touched or rebuilt and the entry indices are
+ * unchanged; the neighbours' labels are patched through the reverse positions (one wave per changed vertex, lanes over its row:
+ * the copy of v's label in the row of each neighbour u is one word, so two changed neighbours write different words).  The graph
+ * generation moves on: open match cursors refuse to go on, and the device tables of ABI 13 / 14 and an entry map end by their own
+ * "rows loaded or changed" wording.  Order and slab are reset and everything derived from the rows or the labels is invalidated as
+ * the loader invalidates it; in particular the next gnnpe_vde checks the labels against the label table again.
+ *
+ * Refusals.  Each leaves the context exactly as it was, generation included; all are decided before the first launch.
+ *   - GNNPE_ERR_ARG: a null pointer with count > 0; an id >= n; one vertex listed with two different labels.
+ *   - GNNPE_ERR_UNSUPPORTED: no whole graph on the device (nothing loaded, or gnnpe_load_rows), or the multigraph state.
+ * count == 0 succeeds, launches nothing and changes nothing: the generation stays, cursors stay valid.
+ * *device_ms (may be NULL) covers the kernel, not the upload of the two lists.
+ * Adding or removing vertices (n changes), slab contexts and multigraph rows are out of scope.
+ *
+ * gnnpe_labels_download: the labels the context holds, n words -- for a caller without a host mirror.  Whole graph only
+ *   (GNNPE_ERR_UNSUPPORTED otherwise). */
+int gnnpe_set_vertex_labels(gnnpe_ctx *ctx, const uint32_t *vertices, const uint32_t *labels, uint64_t count, double *device_ms);
+int gnnpe_labels_download(gnnpe_ctx *ctx, uint32_t *host_labels);
+
 /* ---- halo exchange helpers (device side of the RCCL all-to-all-v) ----------------- */
 /* List the vertices whose adjacency rows this context needs but does not hold -- every vertex referenced by
  * a row it holds: after gnnpe_rows_drop_halo these are the neighbours of its slab's start vertices (all that

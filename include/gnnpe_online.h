@@ -509,6 +509,56 @@ int gnnpe_refine_sets_delta_nonedges_edge_counts(gnnpe_ctx *ctx, const char *que
                                                  uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
                                                  void *dev_accum, int sign, double *device_ms);
 
+/* ---- the matches through a set of data vertices, each once ---------------------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section and gnnpe_set_vertex_labels of include/gnnpe_hip.h only add symbols.)
+ * ABI 15 - 19 are anchored at data EDGES.  "Which matches contain one of these data VERTICES?" is the question behind a vertex
+ * removal, behind a relabel (gnnpe_set_vertex_labels: the matches a new label destroys are asked before it, the ones it creates
+ * after it) and behind an ego query.  For a connected query of two or more vertices it can be emulated by gnnpe_refine_sets_delta
+ * over every edge incident to the set -- 2 deg(s) single-entry items per vertex and one launch per query edge -- and for a
+ * single-vertex query not at all.
+ *
+ * Terms as in the ABI 12 - 15 texts, M_m(C) as in ABI 13, Dset_m(C, F) as in ABI 17.  S is a set of data vertices, handed over as
+ * vertices: n_vertices uint32 ids; repeats are tolerated and mean the vertex once.
+ *
+ *   Sset_m(C, S)          = { f in M_m(C) : f(u) in S for at least one query vertex u }
+ *   DeltaV_m(C, S, limit) = min(limit, |Sset_m(C, S)|)
+ *
+ * Every such map is counted and listed ONCE, however many of its images lie in S.  All four modes are served.
+ *   - S = V: DeltaV = |M_m(C)|.
+ *   - S = {s}: DeltaV = the sum over u of V_m(C)[u][s] (ABI 13).
+ *   - a connected query with nq >= 2: Sset_m(C, S) = Dset_m(C, E(S)), E(S) the edges of G with an endpoint in S (ABI 15 / 17): a
+ *     query vertex has a query neighbour, so an image in S puts a query edge on an edge at S, and the converse is plain.
+ *   - nq = 1: DeltaV = the number of s in S n C(0) that pass the label and degree test.  (The edge-anchored calls give 0 there.)
+ *   - VERTEX REMOVAL.  G' = G minus E(S), nq >= 2, the same C, any mode: |M(G')| = |M(G)| - DeltaV(G, S).  The vertices of S are
+ *     isolated in G' and a connected query asks for degree >= 1; a match that avoids S keeps every adjacency and non-adjacency,
+ *     and the degrees it needs (its deg_Q(u) neighbours of f(u) are images outside S).
+ *   - RELABEL.  G' = G with new labels on the vertices of S, and C and C' agree on every vertex outside S (a label bitmap of each
+ *     graph does).  In any mode, as sets of maps M(G', C') = (M(G, C) - Sset(G, C, S)) + Sset(G', C', S), the union disjoint:
+ *     |M(G', C')| = |M(G, C)| - DeltaV(G, C, S) + DeltaV(G', C', S).  A map that avoids S sees the same labels, sets, rows and
+ *     degrees in both graphs.
+ *   - n_vertices == 0, limit == 0 or an empty C(u): the answer is 0 and nothing is launched.
+ *
+ * Refusals, all GNNPE_ERR_ARG with *answers = 0 unless gnnpe_refine_sets_mode names another code:
+ *   - an id >= n: checked on the host before anything is launched.
+ *   - everything else exactly as gnnpe_refine_sets_mode: the whole simple graph on the device, a connected query of 1..32
+ *     vertices, no multigraph state, no unknown mode bits.
+ *   There is no refusal on the device: a vertex has nothing to look up.
+ *
+ * gnnpe_host_refine_sets_delta_vertices: the host form, the yardstick.  The backtracking of gnnpe_host_refine_sets_mode, unchanged,
+ *   over all of M with one test at every find (is an image in S: a byte mask).  It shares nothing with the device form's search.
+ * gnnpe_refine_sets_delta_vertices: the device form (csrc/gnnpe_refine_delta_vertices.hip): one launch per query vertex u over the
+ *   first-level chunks of the start candidates S n C(u), in a matching order that starts at u; a map is kept in the launch of its
+ *   lowest-numbered query vertex with an image in S only.  Its cost follows DeltaV and nq, not |M|.
+ *   matches, matches_cap, the row layout, limit, *device_ms and the ownership of the buffers are exactly those of
+ *   gnnpe_refine_sets_delta.  There is no paged form, and no count tables of Sset yet (the follow-up, as ABI 17 followed ABI 15);
+ *   adding or removing vertices (n changes), slab contexts and multigraph rows are out of scope. */
+int gnnpe_host_refine_sets_delta_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                          const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *vertices,
+                                          uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers);
+int gnnpe_refine_sets_delta_vertices(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                     const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers,
+                                     uint32_t *matches, uint64_t matches_cap, double *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
