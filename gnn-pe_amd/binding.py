@@ -201,6 +201,15 @@ ONLINE_SIGNATURES = {
                                                         C.c_uint64, C.c_uint32, _u64p]),
     "gnnpe_refine_sets_delta_vertices": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, _u32p,
                                                    C.c_uint64, _f64p]),
+    "gnnpe_host_refine_sets_delta_vertices_vertex_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p,
+                                                                      C.c_uint64, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int),
+                                                                      _u64p]),
+    "gnnpe_host_refine_sets_delta_vertices_edge_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, _u32p,
+                                                                    C.c_uint64, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p]),
+    "gnnpe_refine_sets_delta_vertices_vertex_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                                 _u64p, C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
+    "gnnpe_refine_sets_delta_vertices_edge_counts": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
+                                                               C.POINTER(C.c_int), _u64p, C.POINTER(_vp), _vp, C.c_int, _f64p]),
 }
 _online = None
 
@@ -533,6 +542,22 @@ def host_refine_sets_delta_vertices(g, query_path, bitmap, vertices, limit=2 ** 
     outside g raises GnnpeError."""
     return _host_sets("gnnpe_host_refine_sets_delta_vertices", g, query_path, bitmap, limit, match_mode(distinct, induced),
                       vertices=vertices)
+
+
+def host_refine_sets_delta_vertices_vertex_counts(g, query_path, bitmap, vertices, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """The per-vertex table of the matches through a set of data vertices on the host (include/gnnpe_online.h, VV_m(C, S)):
+    (answers, complete, counts) as host_refine_sets_vertex_counts, over the matches host_refine_sets_delta_vertices counts only;
+    answers = min(DeltaV, limit), complete = DeltaV < limit.  `vertices` as for host_refine_sets_delta_vertices."""
+    bm, n = _np(bitmap, np.uint32), len(g["offsets"]) - 1
+    return _host_sets("gnnpe_host_refine_sets_delta_vertices_vertex_counts", g, query_path, bm, limit, match_mode(distinct, induced),
+                      shape=(_bitmap_rows(bm, n), n), vertices=vertices)
+
+
+def host_refine_sets_delta_vertices_edge_counts(g, query_path, bitmap, vertices, limit=2 ** 64 - 1, distinct=False, induced=False):
+    """The per-edge table of the matches through a set of data vertices on the host (include/gnnpe_online.h, EV_m(C, S)): (answers,
+    complete, counts) as host_refine_sets_edge_counts, over the matches host_refine_sets_delta_vertices counts only."""
+    return _host_sets("gnnpe_host_refine_sets_delta_vertices_edge_counts", g, query_path, bitmap, limit, match_mode(distinct, induced),
+                      shape=_edge_table_shape(g, query_path), vertices=vertices)
 
 
 def host_refine_sets_delta_vertex_counts(g, query_path, bitmap, edges, limit=2 ** 64 - 1, distinct=False, induced=False):
@@ -870,7 +895,8 @@ class Engine:
         self.entries = 0  # adjacency entries of the CSR given to load_csr: the width of the edge-count tables
         self._rows_gen = self._ecounts_call = 0  # what an edge-count device view is valid for
         # ... and a view of a delta table, or of a table over non-edges
-        self._delta_counts_call = {"vertex": 0, "edge": 0, "nonedges_vertex": 0, "nonedges_edge": 0}
+        self._delta_counts_call = {"vertex": 0, "edge": 0, "nonedges_vertex": 0, "nonedges_edge": 0, "vertices_vertex": 0,
+                                   "vertices_edge": 0}
         self._map_call = 0  # ... and a view of the entry map: every apply_edges / apply_edges_map ends the one before
         self.slab = (0, 0)
         self.total = None
@@ -1198,7 +1224,7 @@ class Engine:
         return out.value, rows[:min(out.value, cap)], ms.value
 
     def _refine_sets_delta_counts(self, kind, shape, query_path, bitmap, edges, limit, distinct, induced, device, accum, sign):
-        e = _delta_pairs(edges)
+        e = _vertex_ids(edges) if kind.startswith("vertices_") else _delta_pairs(edges)  # (S travels where F does)
         if accum is None:
             self._delta_counts_call[kind] += 1
         got = self._sets_table(f"gnnpe_refine_sets_delta_{kind}_counts", shape, query_path, bitmap, limit, distinct, induced, device, e,
@@ -1251,6 +1277,28 @@ class Engine:
         table being (nqe, entries) uint64."""
         shape = (len(host_query_edges(query_path)), self.entries)
         return self._refine_sets_delta_counts("nonedges_edge", shape, query_path, bitmap, pairs, limit, distinct, True, device, accum, sign)
+
+    def refine_sets_delta_vertices_vertex_counts(self, query_path, bitmap, vertices, limit=2 ** 64 - 1, distinct=False, induced=False,
+                                                 device=False, accum=None, sign=1):
+        """The per-vertex table of the matches through a set of data vertices on the device
+        (gnnpe_refine_sets_delta_vertices_vertex_counts): (answers, complete, counts, device ms) as refine_sets_vertex_counts, over
+        the matches refine_sets_delta_vertices counts only.  device, accum and sign exactly as for refine_sets_delta_vertex_counts:
+        a device=True view is of the context's own table for this call, valid until the next such call or until the rows are
+        loaded or changed, and delta_counts_to_host(counts) copies it back.  A table is maintained across a relabel by
+        -VV(G, C, S), set_vertex_labels, +VV(G', C', S)."""
+        bm = _np(bitmap, np.uint32)
+        return self._refine_sets_delta_counts("vertices_vertex", (_bitmap_rows(bm, self.n), self.n), query_path, bm, vertices, limit,
+                                              distinct, induced, device, accum, sign)
+
+    def refine_sets_delta_vertices_edge_counts(self, query_path, bitmap, vertices, limit=2 ** 64 - 1, distinct=False, induced=False,
+                                               device=False, accum=None, sign=1):
+        """The per-edge table of the matches through a set of data vertices on the device
+        (gnnpe_refine_sets_delta_vertices_edge_counts): (answers, complete, counts, device ms) as refine_sets_edge_counts, over the
+        matches refine_sets_delta_vertices counts only.  device, accum and sign as for refine_sets_delta_vertices_vertex_counts, the
+        caller's table being (nqe, entries) uint64; a single-vertex query has no table (a view of address 0 and no rows)."""
+        shape = (len(host_query_edges(query_path)), self.entries)
+        return self._refine_sets_delta_counts("vertices_edge", shape, query_path, bitmap, vertices, limit, distinct, induced, device, accum,
+                                              sign)
 
     def _counts_view_to_host(self, view, stamp, stale):
         """a device table of this context copied to the host as uint64, unless its valid_for is not `stamp` any more"""

@@ -57,17 +57,18 @@ struct Options {
     // --vertex-counts or --edge-counts): one data vertex pair `x y` per line, none of them an edge; the answer is the induced matches
     // that put a non-adjacent query pair on at least one of them, each once (gnnpe_refine_sets_delta_nonedges)
     std::string delta_nonedges_file;
-    // --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges or --delta-nonedges; not with each
+    // --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges, --delta-nonedges or --delta-vertices; not with each
     // other, --matches or the count tables): the table of --vertex-counts / --edge-counts over the matches through the delta edges
     // only (gnnpe_refine_sets_delta_vertex_counts / _edge_counts), or with --delta-nonedges over the induced matches on those pairs
-    // only (gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts); -n is a guard as for --vertex-counts
+    // only (gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts), or with --delta-vertices over the matches with an image
+    // among those vertices only (gnnpe_refine_sets_delta_vertices_vertex_counts / _edge_counts); -n is a guard as for --vertex-counts
     std::string delta_vertex_counts_file, delta_edge_counts_file;
     // --apply-edges FILE (exact -m online / -m filter only): lines `+ x y` / `- x y`, a batch of edge insertions and deletions
     // applied to the loaded data graph on the device before anything is computed from it (gnnpe_csr_apply_edges)
     std::string apply_edges_file;
     // --delta-vertices FILE (needs --refine sets; with --distinct, --induced and --matches, not with --delta-edges, --delta-nonedges,
-    // --all-matches or the count tables): one data vertex id per line; the answer is the matches with at least one image among
-    // them, each once (gnnpe_refine_sets_delta_vertices)
+    // --all-matches, --vertex-counts or --edge-counts): one data vertex id per line; the answer is the matches with at least one image
+    // among them, each once (gnnpe_refine_sets_delta_vertices); --delta-vertex-counts / --delta-edge-counts write their tables
     std::string delta_vertices_file;
     // --set-labels FILE (exact -m online / -m filter only): lines `v label`, new labels for those data vertices, set on the device
     // after --apply-edges and before anything is computed from the graph (gnnpe_set_vertex_labels)
@@ -150,8 +151,8 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "           [--gpus N] [--transport rccl|copy] [--chunk PATHS] [--index] [--sidecars] [--timing] [--allow-large]\n"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
-                   "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE)\n"
-                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE] | --delta-vertices FILE] [--apply-edges FILE]\n"
+                   "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE | --delta-vertices FILE)\n"
+                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE]] [--apply-edges FILE]\n"
                    "           [--set-labels FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
@@ -166,11 +167,12 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --delta-edges FILE (needs --refine sets; combines with --distinct, --induced and --matches, not with\n"
                    "       --all-matches or the count tables): FILE has one data edge `x y` per line; the answer is the number of matches\n"
                    "       that put a query edge on at least one of them, each match once, and --matches writes those;\n"
-                   "       --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges or --delta-nonedges;\n"
+                   "       --delta-vertex-counts FILE, --delta-edge-counts FILE (need --refine sets and --delta-edges or --delta-nonedges\n"
+                   "       or --delta-vertices;\n"
                    "       combine with --distinct, --induced and --apply-edges, not with each other, --matches, --vertex-counts or\n"
                    "       --edge-counts) write the file of --vertex-counts / --edge-counts over the matches through the delta edges only,\n"
-                   "       or with --delta-nonedges over the induced matches on the listed non-edges only.  -n is a guard as for\n"
-                   "       --vertex-counts;\n"
+                   "       or with --delta-nonedges over the induced matches on the listed non-edges only, or with --delta-vertices over\n"
+                   "       the matches with an image among the listed vertices only.  -n is a guard as for --vertex-counts;\n"
                    "       --delta-nonedges FILE (needs --refine sets and --induced; combines with --distinct, --matches,\n"
                    "       --delta-vertex-counts and --delta-edge-counts, not with --delta-edges, --all-matches, --vertex-counts or\n"
                    "       --edge-counts): FILE has one pair of data vertices `x y` per line, none of them an edge; the answer is the number\n"
@@ -180,8 +182,9 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       (delete it) per edge; the batch is applied to the data graph on the device and the query runs on the result:\n"
                    "       the metadata block and the rows of --edge-counts / --vertex-counts and of their --delta forms\n"
                    "       are the updated graph's;\n"
-                   "       --delta-vertices FILE (needs --refine sets; combines with --distinct, --induced and --matches, not with\n"
-                   "       --delta-edges, --delta-nonedges, --all-matches or the count tables): FILE has one data vertex id per line; the\n"
+                   "       --delta-vertices FILE (needs --refine sets; combines with --distinct, --induced, --matches, --delta-vertex-counts\n"
+                   "       and --delta-edge-counts, not with --delta-edges, --delta-nonedges, --all-matches, --vertex-counts or\n"
+                   "       --edge-counts): FILE has one data vertex id per line; the\n"
                    "       answer is the number of matches with at least one image among them, each match once, and --matches writes those;\n"
                    "       --set-labels FILE (exact mode only: --exact or -l 3): FILE has one line `v label` per vertex; the labels are set\n"
                    "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's\n",

@@ -275,7 +275,9 @@ struct MatchFile {
 //   --delta-nonedges FILE    gnnpe_refine_sets_delta_nonedges: the induced matches that put a non-adjacent query pair on one of
 //                            the listed non-edges, each once; with --delta-vertex-counts / --delta-edge-counts FILE
 //                            gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts, the count tables of those matches
-//   --delta-vertices FILE    gnnpe_refine_sets_delta_vertices: the matches with an image among the listed data vertices, each once
+//   --delta-vertices FILE    gnnpe_refine_sets_delta_vertices: the matches with an image among the listed data vertices, each once;
+//                            with --delta-vertex-counts / --delta-edge-counts FILE gnnpe_refine_sets_delta_vertices_vertex_counts /
+//                            _edge_counts, the count tables of those matches
 //   none of these            gnnpe_refine_sets_mode
 // The four one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
 struct Refinement {
@@ -296,15 +298,22 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
     }
     const uint32_t match_mode = (o.distinct ? GNNPE_MATCH_DISTINCT : 0u) | (o.induced ? GNNPE_MATCH_INDUCED : 0u);
     const bool nonedges = !o.delta_nonedges_file.empty(), through = !o.delta_edges_file.empty() || nonedges;
+    const bool vertices = !o.delta_vertices_file.empty();
     const struct {
         const char *flag, *what;
         const std::string &path;
         bool edge_table;
     } tables[] = {{"--vertex-counts", "refine_sets_vertex_counts", o.vertex_counts_file, false},
                   {"--edge-counts", "refine_sets_edge_counts", o.edge_counts_file, true},
-                  {"--delta-vertex-counts", nonedges ? "refine_sets_delta_nonedges_vertex_counts" : "refine_sets_delta_vertex_counts",
+                  {"--delta-vertex-counts",
+                   vertices   ? "refine_sets_delta_vertices_vertex_counts"
+                   : nonedges ? "refine_sets_delta_nonedges_vertex_counts"
+                              : "refine_sets_delta_vertex_counts",
                    o.delta_vertex_counts_file, false},
-                  {"--delta-edge-counts", nonedges ? "refine_sets_delta_nonedges_edge_counts" : "refine_sets_delta_edge_counts",
+                  {"--delta-edge-counts",
+                   vertices   ? "refine_sets_delta_vertices_edge_counts"
+                   : nonedges ? "refine_sets_delta_nonedges_edge_counts"
+                              : "refine_sets_delta_edge_counts",
                    o.delta_edge_counts_file, true}};
     for (const auto &t : tables) {
         if (t.path.empty()) continue;
@@ -315,7 +324,12 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
             through ? read_delta_edges(nonedges ? o.delta_nonedges_file : o.delta_edges_file) : std::vector<uint32_t>();
         std::vector<uint64_t> table(t.edge_table ? (size_t)nqe * g.offsets[g.n] : (size_t)n_qv * g.n);
         int complete = 0;
-        if (nonedges)
+        if (vertices) {
+            const std::vector<uint32_t> ids = read_vertex_list(o.delta_vertices_file);
+            check((t.edge_table ? ONLINE(gnnpe_refine_sets_delta_vertices_edge_counts) : ONLINE(gnnpe_refine_sets_delta_vertices_vertex_counts))(
+                      ctx, query, bitmap.data(), ids.data(), ids.size(), limit, match_mode, &r.answers, &complete, table.data(), nullptr,
+                      nullptr, 1, &r.refine_ms), t.what);
+        } else if (nonedges)
             check((t.edge_table ? ONLINE(gnnpe_refine_sets_delta_nonedges_edge_counts) : ONLINE(gnnpe_refine_sets_delta_nonedges_vertex_counts))(
                       ctx, query, bitmap.data(), edges.data(), edges.size() / 2, limit, match_mode, &r.answers, &complete, table.data(),
                       nullptr, nullptr, 1, &r.refine_ms), t.what);
@@ -616,17 +630,16 @@ int main(int argc, char **argv)
         if (o.refine != "sets") die("--delta-vertices needs --refine sets");
         if (!o.delta_edges_file.empty() || !o.delta_nonedges_file.empty())
             die("--delta-vertices excludes --delta-edges and --delta-nonedges");
-        if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty() || !o.delta_vertex_counts_file.empty() ||
-            !o.delta_edge_counts_file.empty())
-            die("--delta-vertices excludes --all-matches and the count tables");
+        if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty())
+            die("--delta-vertices excludes --all-matches, --vertex-counts and --edge-counts");
         (void)read_vertex_list(o.delta_vertices_file);  // a malformed file is refused before a GPU is touched
     }
     for (const char *flag : {"--delta-vertex-counts", "--delta-edge-counts"}) {
         const bool edge_table = std::string(flag) == "--delta-edge-counts";
         if ((edge_table ? o.delta_edge_counts_file : o.delta_vertex_counts_file).empty()) continue;
         if (o.refine != "sets") die(std::string(flag) + " needs --refine sets");
-        if (o.delta_edges_file.empty() && o.delta_nonedges_file.empty())
-            die(std::string(flag) + " needs --delta-edges FILE or --delta-nonedges FILE");
+        if (o.delta_edges_file.empty() && o.delta_nonedges_file.empty() && o.delta_vertices_file.empty())
+            die(std::string(flag) + " needs --delta-edges FILE or --delta-nonedges FILE or --delta-vertices FILE");
         if (edge_table && !o.delta_vertex_counts_file.empty()) die("--delta-vertex-counts and --delta-edge-counts exclude each other");
         if (!o.matches_file.empty()) die(std::string(flag) + " and --matches exclude each other");
     }

@@ -218,6 +218,30 @@ int gnnpe_host_refine_sets_delta_vertices(uint32_t n, const uint32_t *offsets, c
                      candidate_bitmap, vertices, n_vertices, limit, mode, answers, nullptr, nullptr, false, true);
 }
 
+// (the thirteenth and the fourteenth: the tables of those maps, VV_m(C, S) and EV_m(C, S); these two clear *answers and *complete
+// before the null checks as well, so that every refusal leaves 0 in them)
+int gnnpe_host_refine_sets_delta_vertices_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                        const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                        const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                        uint64_t *answers, int *complete, uint64_t *counts)
+{
+    if (answers) *answers = 0;
+    if (complete) *complete = 0;
+    return host_sets("gnnpe_host_refine_sets_delta_vertices_vertex_counts", gnnpe_host::SetsJob::kVertexTable, true, n, offsets, nbrs, labels,
+                     query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, answers, complete, counts, false, true);
+}
+
+int gnnpe_host_refine_sets_delta_vertices_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                      const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                      const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                      uint64_t *answers, int *complete, uint64_t *counts)
+{
+    if (answers) *answers = 0;
+    if (complete) *complete = 0;
+    return host_sets("gnnpe_host_refine_sets_delta_vertices_edge_counts", gnnpe_host::SetsJob::kEdgeTable, true, n, offsets, nbrs, labels,
+                     query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, answers, complete, counts, false, true);
+}
+
 int gnnpe_host_query_edges(const char *query_graph_path, uint32_t *edges, uint32_t cap, uint32_t *n_edges)
 {
     if (!query_graph_path || !n_edges || (!edges && cap)) {

@@ -52,7 +52,7 @@ inline std::vector<uint32_t> set_members(const uint32_t *bitmap, uint64_t words,
 //   all of M (through = false)                  R, D, I, ID         V_m(C)         E_m(C)
 //   the maps through F (through = true)         Delta_m(C, F)       VDelta_m(C, F) EDelta_m(C, F)
 //   ... F of non-edges (nonedges = true)        N_m(C, F)           VN_m(C, F)     EN_m(C, F)
-//   the maps with an image in S (through_vertices)  DeltaV_m(C, S)   (a table is filled as for any other job; no entry asks for one)
+//   the maps with an image in S (through_vertices)  DeltaV_m(C, S)  VV_m(C, S)     EV_m(C, S)
 struct SetsJob {
     const std::vector<std::pair<uint32_t, uint32_t>> *pairs = nullptr;
     bool induced = false;

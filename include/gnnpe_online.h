@@ -550,14 +550,74 @@ int gnnpe_refine_sets_delta_nonedges_edge_counts(gnnpe_ctx *ctx, const char *que
  *   first-level chunks of the start candidates S n C(u), in a matching order that starts at u; a map is kept in the launch of its
  *   lowest-numbered query vertex with an image in S only.  Its cost follows DeltaV and nq, not |M|.
  *   matches, matches_cap, the row layout, limit, *device_ms and the ownership of the buffers are exactly those of
- *   gnnpe_refine_sets_delta.  There is no paged form, and no count tables of Sset yet (the follow-up, as ABI 17 followed ABI 15);
- *   adding or removing vertices (n changes), slab contexts and multigraph rows are out of scope. */
+ *   gnnpe_refine_sets_delta.  There is no paged form; the count tables of Sset are the next section; adding or removing vertices
+ *   (n changes), slab contexts and multigraph rows are out of scope. */
 int gnnpe_host_refine_sets_delta_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                           const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *vertices,
                                           uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers);
 int gnnpe_refine_sets_delta_vertices(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
                                      const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers,
                                      uint32_t *matches, uint64_t matches_cap, double *device_ms);
+
+/* ---- count tables of the matches through a set of data vertices -------------------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section only adds symbols.)
+ * The consumers of the ABI 13 and 14 tables keep tables on the device, not rows.  With ABI 17, 19 and 20 such a table stays exact
+ * across edge insertions and deletions; the functions below do the same for a relabel and for a vertex removal, what
+ * gnnpe_refine_sets_delta_vertices does for the plain count:
+ *     T -= tables of Sset(G, C, S);  gnnpe_set_vertex_labels(ctx, S, new labels);  T += tables of Sset(G', C', S)
+ * and the same around a removal of E(S) through gnnpe_csr_apply_edges[_map].  Nothing per match leaves the device.
+ *
+ * Sset_m(C, S) and the hand-over of S are as in the section above, the query edges (a_k, b_k), k < nqe, those of
+ * gnnpe_host_query_edges, the entry index j as in ABI 14.
+ *
+ *   VV_m(C, S)[u][v] = |{ f in Sset : f(u) = v }|                      nq  x n           uint64, row-major
+ *   EV_m(C, S)[k][j] = |{ f in Sset : f(a_k) = x and f(b_k) = y }|     nqe x offsets[n]  uint64, j = (x -> y)
+ *
+ *   - every row of either table sums to |Sset| = DeltaV_m(C, S, 2^64 - 1); summing EV row k over the entries of data row x gives
+ *     VV[a_k][x].
+ *   - S = V: VV = V_m(C) and EV = E_m(C), the tables of ABI 13 / 14.
+ *   - a connected query with nq >= 2: VV(C, S) = VD(C, E(S)) and EV(C, S) = ED(C, E(S)), the tables of ABI 17.
+ *   - nq = 1: VV[0][s] = 1 for the s in S n C(0) that pass the label and degree test and 0 elsewhere; EV is empty as in ABI 14.
+ *   - RELABEL, any mode, C and C' agreeing outside S: V(G', C') = V(G, C) - VV(G, C, S) + VV(G', C', S), and the same for E with the
+ *     same entry indices, because a relabel moves no entry.
+ *   - REMOVAL, G' = G - E(S), nq >= 2, the same C: V(G') = V(G) - VV(G, S); for E the same by the key (x, y) of an entry, or through
+ *     gnnpe_csr_apply_edges_map and gnnpe_csr_carry_entries (include/gnnpe_hip.h).
+ *
+ * limit, *answers, *complete, host_counts, dev_counts, dev_accum and sign are exactly those of ABI 17 with DeltaV in the place of
+ * Delta: *answers = min(DeltaV, limit); *complete = 1 iff DeltaV < limit; with *complete = 0 the table is unspecified and nothing is
+ * copied to the host; limit == 0 launches nothing and gives *complete = 0; an empty C(u), an empty S or no vertex of S in any set
+ * launches nothing: a context-owned table is all zeros, a caller's table is untouched, *complete = 1.  sign must be 1 without
+ * dev_accum, host_counts must be NULL with dev_accum, and every cell of a caller's table ends at old + sign * c mod 2^64.
+ *
+ * gnnpe_host_refine_sets_delta_vertices_vertex_counts, gnnpe_host_refine_sets_delta_vertices_edge_counts: the host forms, the
+ *   yardstick: the backtracking of gnnpe_host_refine_sets_delta_vertices with the cell increments of
+ *   gnnpe_host_refine_sets_vertex_counts / _edge_counts at every find that counts.  counts is the caller's (NULL is accepted for an
+ *   empty edge table).
+ * gnnpe_refine_sets_delta_vertices_vertex_counts, gnnpe_refine_sets_delta_vertices_edge_counts: the device forms
+ *   (csrc/gnnpe_refine_delta_vertices_counts.hip): the launches, items and charging rule of gnnpe_refine_sets_delta_vertices with the
+ *   tallies and flushes of the ABI 13 / 14 kernels.  Refusals are those of gnnpe_refine_sets_delta_vertices plus the sign and
+ *   dev_accum refusals of ABI 17.  An id >= n is refused on the host before anything is launched, and there is no refusal on the
+ *   device: a refused call leaves a caller's table byte for byte as it was.  Without dev_accum the table lives in a context-owned,
+ *   grow-only buffer of its own -- one for VV, another for EV, neither a buffer of ABI 13, 14, 17 or 19, whose device views keep
+ *   their documented lifetimes -- zeroed once per call on the stream before the first launch, inside *device_ms, and valid until the
+ *   next call of the same function on the context or until the context's rows are loaded or changed.  A single-vertex query has
+ *   no edge table: the edge call gives *answers = DeltaV and *dev_counts = NULL.  There is no paged form. */
+int gnnpe_host_refine_sets_delta_vertices_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                        const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                        const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                        uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_host_refine_sets_delta_vertices_edge_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                                      const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                      const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                      uint64_t *answers, int *complete, uint64_t *counts);
+int gnnpe_refine_sets_delta_vertices_vertex_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                   const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                   uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
+                                                   void *dev_accum, int sign, double *device_ms);
+int gnnpe_refine_sets_delta_vertices_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                 const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                 uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
+                                                 void *dev_accum, int sign, double *device_ms);
 
 #ifdef __cplusplus
 }
