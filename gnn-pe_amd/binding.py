@@ -162,6 +162,9 @@ ONLINE_SIGNATURES = {
     "gnnpe_host_refine_sets_mode": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p]),
     "gnnpe_refine_sets_mode": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, _u32p, C.c_uint64, _f64p]),
     "gnnpe_refine_pages_open_mode": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "gnnpe_refine_pages_open_delta": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "gnnpe_refine_pages_open_delta_nonedges": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    "gnnpe_refine_pages_open_delta_vertices": (C.c_int, [_vp, C.c_char_p, _u32p, _u32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "gnnpe_host_refine_sets_vertex_counts": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, C.c_uint32,
                                                        _u64p, C.POINTER(C.c_int), _u64p]),
     "gnnpe_refine_sets_vertex_counts": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, C.c_uint32, _u64p, C.POINTER(C.c_int), _u64p,
@@ -823,13 +826,19 @@ class MatchCursor:
 
     INFO_FIELDS = ("pages", "rows", "suspended_waves", "items_left", "slots")
 
-    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False):
+    def __init__(self, eng, query_path, bitmap, page_rows, limit=2 ** 64 - 1, device=False, distinct=False, induced=False, anchor=None):
         self.eng, self.lib, self.h = eng, load_online(), None
         bm = _np(bitmap, np.uint32)
         self.page_rows, self.device = int(page_rows), bool(device)
         self.done = False
         h = C.c_void_p()
-        if induced:
+        if anchor is not None:
+            # a delta cursor: anchor = (suffix of gnnpe_refine_pages_open_delta, F as pairs or S as ids)
+            sfx, ids = anchor
+            eng._ck(getattr(self.lib, "gnnpe_refine_pages_open_delta" + sfx)(eng.ctx, query_path.encode(), _ptr(bm, _u32p),
+                                                                            _ptr(ids, _u32p) if len(ids) else None, len(ids), int(limit),
+                                                                            self.page_rows, match_mode(distinct, induced), C.byref(h)))
+        elif induced:
             eng._ck(self.lib.gnnpe_refine_pages_open_mode(eng.ctx, query_path.encode(), _ptr(bm, _u32p), int(limit), self.page_rows,
                                                           match_mode(distinct, induced), C.byref(h)))
         else:
@@ -1331,6 +1340,37 @@ class Engine:
         """Generator over the pages of a MatchCursor: every embedding inside the sets exactly once, up to `limit`, at most
         page_rows per page (an empty last page is not yielded).  The cursor is closed when the generator ends or is dropped."""
         cur = MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct, induced=induced)
+        try:
+            done = False
+            while not done:
+                rows, done = cur.next()
+                if rows.shape[0]:
+                    yield rows
+        finally:
+            cur.close()
+
+    def open_delta_cursor(self, query_path, bitmap, page_rows, *, edges=None, nonedges=None, vertices=None, limit=2 ** 64 - 1, device=False,
+                          distinct=False, induced=False):
+        """A MatchCursor over the delta matches: with `edges` the matches refine_sets_delta counts (gnnpe_refine_pages_open_delta),
+        with `nonedges` the ones refine_sets_delta_nonedges counts (gnnpe_refine_pages_open_delta_nonedges; the mode is induced
+        whatever `induced` says, as there), with `vertices` the ones refine_sets_delta_vertices counts
+        (gnnpe_refine_pages_open_delta_vertices).  Exactly one of the three is given.  Every match comes out once across the
+        pages; changing the graph invalidates the cursor, so a deletion's cursor is drained before the batch is applied and an
+        insertion's is opened after it."""
+        given = [(sfx, a) for sfx, a in (("", edges), ("_nonedges", nonedges), ("_vertices", vertices)) if a is not None]
+        if len(given) != 1:
+            raise GnnpeError("open_delta_cursor: exactly one of edges, nonedges and vertices must be given")
+        sfx, a = given[0]
+        ids = _vertex_ids(a) if sfx == "_vertices" else _delta_pairs(a)
+        return MatchCursor(self, query_path, bitmap, page_rows, limit=limit, device=device, distinct=distinct,
+                           induced=induced or sfx == "_nonedges", anchor=(sfx, ids))
+
+    def delta_pages(self, query_path, bitmap, page_rows, *, edges=None, nonedges=None, vertices=None, limit=2 ** 64 - 1, device=False,
+                    distinct=False, induced=False):
+        """Generator over the pages of open_delta_cursor's cursor: every delta match exactly once, up to `limit`, at most page_rows
+        per page (an empty last page is not yielded).  The cursor is closed when the generator ends or is dropped."""
+        cur = self.open_delta_cursor(query_path, bitmap, page_rows, edges=edges, nonedges=nonedges, vertices=vertices, limit=limit,
+                                     device=device, distinct=distinct, induced=induced)
         try:
             done = False
             while not done:

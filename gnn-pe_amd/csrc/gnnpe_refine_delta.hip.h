@@ -207,15 +207,17 @@ static inline int delta_plans(const char *who, gnnpe_ctx *c, const SetsQuery &Q,
 // The staging of a call whose buffers (q_work, q_bitmap, q_delta) are reserved, on the context's stream: F and the bitmap go up, the
 // counters are zeroed, ev0 is recorded and k_delta_entries looks the pairs up -- each must be an edge of the graph, or with
 // `nonedges` none of them may be.  Returns the blocks of a search launch: a resident grid, or as many waves as there are items.
+// (A cursor hands in its own reserved buffers in the place of the context's: `work` begins with the counter block.)
 static inline uint32_t delta_stage(SetsCall &call, gnnpe_ctx *c, const SetsQuery &Q, const DeltaPlans &D, const uint32_t *bitmap,
-                                   bool nonedges = false)
+                                   bool nonedges = false, const DevBuf *work = nullptr, const DevBuf *bm = nullptr, const DevBuf *fset = nullptr)
 {
     const size_t n_keys = D.keys.size();
-    SetsCounters *ctr = c->q_work.as<SetsCounters>();
-    const DeltaBuf F(c->q_delta, n_keys);
+    SetsCounters *ctr = (work ? *work : c->q_work).as<SetsCounters>();
+    const DeltaBuf F(fset ? *fset : c->q_delta, n_keys);
+    void *d_bitmap = (bm ? *bm : c->q_bitmap).p;
     if (call.ok()) call.he = hipMemcpyAsync(F.keys, D.keys.data(), n_keys * 8, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemcpyAsync(F.pairs, D.pairs.data(), n_keys * 16, hipMemcpyHostToDevice, c->stream);
-    if (call.ok()) call.he = hipMemcpyAsync(c->q_bitmap.p, bitmap, (size_t)Q.nq * Q.words * 4, hipMemcpyHostToDevice, c->stream);
+    if (call.ok()) call.he = hipMemcpyAsync(d_bitmap, bitmap, (size_t)Q.nq * Q.words * 4, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemsetAsync(ctr, 0, SetsWork::kCtrBytes, c->stream);
     if (call.ok() && call.ev0) call.he = hipEventRecord(call.ev0, c->stream);
     call.launch([&] {

@@ -97,8 +97,11 @@ static inline int vertices_plans(const char *who, gnnpe_ctx *c, const char *quer
 
 // context-owned, grow-only: the work areas of every launch, the bitmap, S (its bitmap, then its ids), the scan's temporary storage
 // for the longest list -- all before the first launch (an entry reserves its rows or its table beside them)
-static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V)
+// (a cursor hands in its own buffers in the place of the context's q_work, q_bitmap, q_delta and q_tmp)
+static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V, DevBuf *work = nullptr, DevBuf *bm = nullptr, DevBuf *fset = nullptr,
+                                   DevBuf *tmp = nullptr)
 {
+    DevBuf &b_work = work ? *work : c->q_work, &b_bm = bm ? *bm : c->q_bitmap, &b_set = fset ? *fset : c->q_delta, &b_tmp = tmp ? *tmp : c->q_tmp;
     const uint32_t nq = V->Q.nq;
     const uint64_t words = V->Q.words;
     size_t tmp_bytes = 0;
@@ -108,10 +111,10 @@ static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V)
         tmp_bytes = std::max(tmp_bytes, tb);
     }
     int rc;
-    if ((rc = c->q_work.reserve(VerticesWork::bytes(V->cand_all.size(), V->L.size()))) || (rc = c->q_bitmap.reserve((size_t)nq * words * 4)) ||
-        (rc = c->q_delta.reserve((words + V->ids.size()) * 4)) || (nq > 1 && (rc = c->q_tmp.reserve(tmp_bytes))))
+    if ((rc = b_work.reserve(VerticesWork::bytes(V->cand_all.size(), V->L.size()))) || (rc = b_bm.reserve((size_t)nq * words * 4)) ||
+        (rc = b_set.reserve((words + V->ids.size()) * 4)) || (nq > 1 && (rc = b_tmp.reserve(tmp_bytes))))
         return rc;
-    V->sbits = c->q_delta.as<uint32_t>();
+    V->sbits = b_set.as<uint32_t>();
     V->d_ids = V->sbits + words;
     return GNNPE_OK;
 }
@@ -119,15 +122,15 @@ static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V)
 // the uploads, the zeroed counters, the start of the timed span, then inside it the zeroing of `zero` (a context-owned table; may
 // be null) and S as a bitmap
 static inline void vertices_stage(SetsCall &call, gnnpe_ctx *c, const VerticesPlans &V, const uint32_t *candidate_bitmap, void *zero = nullptr,
-                                  size_t zero_bytes = 0)
+                                  size_t zero_bytes = 0, const DevBuf *work = nullptr, const DevBuf *bm = nullptr)
 {
     const size_t n_cand_all = V.cand_all.size(), n_ids = V.ids.size();
     const uint64_t words = V.Q.words;
-    const VerticesWork W(c->q_work, n_cand_all, V.L.size());
+    const VerticesWork W(work ? *work : c->q_work, n_cand_all, V.L.size());
     uint32_t *sbits = V.sbits, *d_ids = V.d_ids;
     if (call.ok()) call.he = hipMemcpyAsync(W.cand, V.cand_all.data(), n_cand_all * 4, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemcpyAsync(d_ids, V.ids.data(), n_ids * 4, hipMemcpyHostToDevice, c->stream);
-    if (call.ok()) call.he = hipMemcpyAsync(c->q_bitmap.p, candidate_bitmap, (size_t)V.Q.nq * words * 4, hipMemcpyHostToDevice, c->stream);
+    if (call.ok()) call.he = hipMemcpyAsync((bm ? *bm : c->q_bitmap).p, candidate_bitmap, (size_t)V.Q.nq * words * 4, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemsetAsync(W.ctr, 0, SetsWork::kCtrBytes, c->stream);
     if (call.ok() && call.ev0) call.he = hipEventRecord(call.ev0, c->stream);
     if (call.ok() && zero_bytes) call.he = hipMemsetAsync(zero, 0, zero_bytes, c->stream);  // once per call, before the first launch

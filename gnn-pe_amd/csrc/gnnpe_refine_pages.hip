@@ -29,7 +29,7 @@
 // (gnnpe_refine_pages_open_distinct) has 58 VGPRs and no scratch; slot and LDS are the same.  The two induced instantiations
 // (gnnpe_refine_pages_open_mode with GNNPE_MATCH_INDUCED): profiles/online_induced.txt.
 #include "../../include/gnnpe_online.h"
-#include "gnnpe_refine_sets.hip.h"
+#include "gnnpe_refine_pages.hip.h"
 
 namespace gnnpe {
 
@@ -40,13 +40,6 @@ struct PagesCounters {  // one 32-byte block, copied back once per page
 };
 static_assert(sizeof(PagesCounters) == SetsWork::kCtrBytes, "the counters of the work buffer");
 constexpr size_t kPagesPerLaunchBytes = 16;  // the part of PagesCounters zeroed before every launch
-
-constexpr uint32_t kWaveWords = sizeof(SetsWave) / 4;  // 7 arrays of kSetsMaxQ words: word a * kSetsMaxQ + i belongs to depth i
-
-struct PagesSlot {  // saved state of one wave
-    uint32_t valid, depth, item, pad;
-    uint32_t w[kWaveWords];  // the SetsWave words of depths 0 .. depth
-};
 
 // One kernel, four instantiations.  k_refine_pages<false> is the plain search: the parameter pack is empty, nothing below that is
 // `if constexpr (kOrdered)` exists (here and in the shared steps), and the code is what it was before the ordered form existed.
@@ -199,21 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_pages(SetsPlan P, uint32_t n_
 
 using namespace gnnpe;
 
-// A cursor owns everything its launches write or read besides the graph: two cursors, the one-shot gnnpe_refine_sets and the
-// filters interleave freely on one context.
-struct gnnpe_match_cursor {
-    gnnpe_ctx *c = nullptr;
-    uint64_t graph_gen = 0;  // the context's graph when the cursor was opened
-    SetsQuery Q;             // (its host copy of the start candidates is dropped once they are on the device)
-    uint32_t n_items = 0, blocks = 0;
-    uint64_t limit = 0, page_rows = 0, page_cap = 0;  // page_cap: rows the page buffer holds, min(page_rows, limit)
-    uint64_t delivered = 0, pages = 0;
-    uint32_t suspended = 0, ticket = 0;  // of the last page
-    bool done = false;
-    DevBuf work, bitmap, slots, page, tmp;  // work: SetsWork
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
-
+// The cursor object is in gnnpe_refine_pages.hip.h: the delta cursors of gnnpe_refine_delta_pages.hip are served by the calls below too.
 extern "C" {
 
 void gnnpe_refine_pages_close(gnnpe_match_cursor *cur)
@@ -223,6 +202,7 @@ void gnnpe_refine_pages_close(gnnpe_match_cursor *cur)
     (void)hipStreamSynchronize(cur->c->stream);
     if (cur->ev0) (void)hipEventDestroy(cur->ev0);
     if (cur->ev1) (void)hipEventDestroy(cur->ev1);
+    if (cur->h_ctrs) (void)hipHostFree(cur->h_ctrs);
     delete cur;  // the buffers free themselves
 }
 
@@ -313,6 +293,7 @@ int gnnpe_refine_pages_next(gnnpe_match_cursor *cur, uint32_t *host_rows, uint64
     GNNPE_REQUIRE(cur->graph_gen == c->graph_gen && c->have_graph && c->rows_identity && !c->multigraph, GNNPE_ERR_ARG,
                   "gnnpe_refine_pages_next: the context's graph was loaded or changed after the cursor was opened; close the cursor");
     GNNPE_HIP_TRY(hipSetDevice(c->device));
+    if (cur->anchor_kind) return gnnpe_delta_pages_next(cur, host_rows, n_rows, done, device_ms);
     const uint64_t rows_now = std::min(cur->page_rows, cur->limit - cur->delivered);  // >= 1: a met limit sets done
     const SetsQuery &Q = cur->Q;
     const SetsWork W(cur->work, Q.n_cand);
@@ -366,7 +347,7 @@ int gnnpe_refine_pages_info(gnnpe_match_cursor *cur, uint64_t info[5])
     info[0] = cur->pages;
     info[1] = cur->delivered;
     info[2] = cur->suspended;
-    info[3] = cur->n_items - std::min(cur->ticket, cur->n_items);
+    info[3] = cur->anchor_kind ? cur->items_left : cur->n_items - std::min(cur->ticket, cur->n_items);
     info[4] = (uint64_t)cur->blocks * kSetsWavesPerBlock;
     return GNNPE_OK;
 }

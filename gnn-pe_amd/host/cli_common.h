@@ -70,6 +70,11 @@ struct Options {
     // --all-matches, --vertex-counts or --edge-counts): one data vertex id per line; the answer is the matches with at least one image
     // among them, each once (gnnpe_refine_sets_delta_vertices); --delta-vertex-counts / --delta-edge-counts write their tables
     std::string delta_vertices_file;
+    // --delta-pages ROWS (needs --matches and one of --delta-edges, --delta-nonedges, --delta-vertices; not with --delta-vertex-counts
+    // or --delta-edge-counts): every match of the delta up to -n into --matches, ROWS per page through a delta cursor
+    // (gnnpe_refine_pages_open_delta, _open_delta_nonedges, _open_delta_vertices)
+    bool delta_pages_given = false;
+    uint64_t delta_pages = 0;
     // --set-labels FILE (exact -m online / -m filter only): lines `v label`, new labels for those data vertices, set on the device
     // after --apply-edges and before anything is computed from the graph (gnnpe_set_vertex_labels)
     std::string set_labels_file;
@@ -152,7 +157,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       %s -f <dataset dir/> -d <data.graph> -q <query.graph> -m online|filter [-l 2|3] [--exact] [--timing]\n"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE | --delta-vertices FILE)\n"
-                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE]] [--apply-edges FILE]\n"
+                   "           [--delta-vertex-counts FILE | --delta-edge-counts FILE | --delta-pages ROWS]] [--apply-edges FILE]\n"
                    "           [--set-labels FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
@@ -229,6 +234,14 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             o.match_page = strtoull(argv[++i], &end, 10);
             if (*end || end == argv[i] || o.match_page == 0) die("--match-page must be an integer of at least 1");
             o.match_page_given = true;
+            continue;
+        }
+        if (a == "--delta-pages") {
+            if (i + 1 >= argc) die(a + " needs a value");
+            char *end = nullptr;
+            o.delta_pages = strtoull(argv[++i], &end, 10);
+            if (*end || end == argv[i] || o.delta_pages == 0) die("--delta-pages must be an integer of at least 1");
+            o.delta_pages_given = true;
             continue;
         }
         if (a == "--all-matches") { o.all_matches = true; continue; }

@@ -278,6 +278,8 @@ struct MatchFile {
 //   --delta-vertices FILE    gnnpe_refine_sets_delta_vertices: the matches with an image among the listed data vertices, each once;
 //                            with --delta-vertex-counts / --delta-edge-counts FILE gnnpe_refine_sets_delta_vertices_vertex_counts /
 //                            _edge_counts, the count tables of those matches
+//   --delta-pages ROWS       with one of the three --delta-* anchors: every match of the delta up to -n into --matches, ROWS per page
+//                            through a delta cursor (gnnpe_refine_pages_open_delta, _open_delta_nonedges, _open_delta_vertices)
 //   none of these            gnnpe_refine_sets_mode
 // The four one-shot counts also write --matches, at most min(-n, 2^20) of them.  For a table -n is a guard: it is exact only below it.
 struct Refinement {
@@ -351,6 +353,36 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
         const uint64_t page = std::min<uint64_t>(o.match_page, std::max<uint64_t>(limit, 1));
         gnnpe_match_cursor *cur = nullptr;
         check(ONLINE(gnnpe_refine_pages_open_mode)(ctx, query, bitmap.data(), limit, page, match_mode, &cur), "refine_pages_open");
+        const auto pages_next = ONLINE(gnnpe_refine_pages_next);
+        MatchFile mf(o.matches_file, n_qv);
+        std::vector<uint32_t> rows((size_t)page * n_qv);
+        for (int done = 0; !done;) {
+            uint64_t got = 0;
+            double page_ms = 0.0;
+            check(pages_next(cur, rows.data(), &got, &done, &page_ms), "refine_pages_next");
+            mf.write(rows, got);
+            r.answers += got;
+            r.refine_ms += page_ms;
+            r.n_pages++;
+        }
+        ONLINE(gnnpe_refine_pages_close)(cur);
+        mf.close();
+        r.n_written = r.answers;
+        return r;
+    }
+    if (o.delta_pages_given) {  // the delta through a cursor, one page on the host at a time
+        const uint64_t page = std::min<uint64_t>(o.delta_pages, std::max<uint64_t>(limit, 1));
+        gnnpe_match_cursor *cur = nullptr;
+        if (vertices) {
+            const std::vector<uint32_t> ids = read_vertex_list(o.delta_vertices_file);
+            check(ONLINE(gnnpe_refine_pages_open_delta_vertices)(ctx, query, bitmap.data(), ids.data(), ids.size(), limit, page, match_mode, &cur),
+                  "refine_pages_open_delta_vertices");
+        } else {
+            const std::vector<uint32_t> pairs = read_delta_edges(nonedges ? o.delta_nonedges_file : o.delta_edges_file);
+            check((nonedges ? ONLINE(gnnpe_refine_pages_open_delta_nonedges) : ONLINE(gnnpe_refine_pages_open_delta))(
+                      ctx, query, bitmap.data(), pairs.data(), pairs.size() / 2, limit, page, match_mode, &cur),
+                  nonedges ? "refine_pages_open_delta_nonedges" : "refine_pages_open_delta");
+        }
         const auto pages_next = ONLINE(gnnpe_refine_pages_next);
         MatchFile mf(o.matches_file, n_qv);
         std::vector<uint32_t> rows((size_t)page * n_qv);
@@ -540,7 +572,7 @@ int run_filter(const Options &o)
             printf("Automorphisms: %llu\n", (unsigned long long)aut);
         }
         if (o.induced) exact_json += "\"induced\": true, ";
-        if (o.timing && sets && o.all_matches)
+        if (o.timing && sets && (o.all_matches || o.delta_pages_given))
             fprintf(stderr, "{%s\"refine\": \"sets\", \"matches_written\": %llu, \"match_pages\": %llu, \"paths\": %llu, "
                             "\"query_paths\": %u, \"filter_device_ms\": %.3f, \"refine_ms\": %.3f, \"end_to_end_s\": %.3f}\n",
                     exact_json.c_str(), (unsigned long long)r.n_written, (unsigned long long)r.n_pages, (unsigned long long)P, n_qp, ms,
@@ -633,6 +665,13 @@ int main(int argc, char **argv)
         if (o.all_matches || !o.vertex_counts_file.empty() || !o.edge_counts_file.empty())
             die("--delta-vertices excludes --all-matches, --vertex-counts and --edge-counts");
         (void)read_vertex_list(o.delta_vertices_file);  // a malformed file is refused before a GPU is touched
+    }
+    if (o.delta_pages_given) {
+        if (o.delta_edges_file.empty() && o.delta_nonedges_file.empty() && o.delta_vertices_file.empty())
+            die("--delta-pages needs --delta-edges FILE or --delta-nonedges FILE or --delta-vertices FILE");
+        if (o.matches_file.empty()) die("--delta-pages needs --matches FILE");
+        if (!o.delta_vertex_counts_file.empty() || !o.delta_edge_counts_file.empty())
+            die("--delta-pages excludes --delta-vertex-counts and --delta-edge-counts");
     }
     for (const char *flag : {"--delta-vertex-counts", "--delta-edge-counts"}) {
         const bool edge_table = std::string(flag) == "--delta-edge-counts";

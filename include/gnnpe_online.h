@@ -307,7 +307,7 @@ int gnnpe_refine_sets_edge_counts(gnnpe_ctx *ctx, const char *query_graph_path, 
  *   - *device_ms (may be NULL) covers the kernels, not the uploads.
  *   - the buffers are context-owned and grow-only; an allocation the device refuses returns its error and leaves the context
  *     usable.
- *   - there is no paged (cursor) form of this call. */
+ *   - the rows come page by page through gnnpe_refine_pages_open_delta (the last section). */
 int gnnpe_host_refine_sets_delta(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                  const char *query_graph_path, const uint32_t *candidate_bitmap,
                                  const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode,
@@ -432,7 +432,8 @@ int gnnpe_refine_sets_delta_edge_counts(gnnpe_ctx *ctx, const char *query_graph_
  *   over one item per directed pair of F, in a matching order that starts at (a_k, b_k) and walks from the third position on; a map
  *   is kept in the launch of its lowest-numbered non-adjacent pair in F only.  Its cost follows N and nqn,
  *   not |M|.  matches, matches_cap, the row layout, *device_ms and the ownership of the buffers are exactly those of
- *   gnnpe_refine_sets_delta; there is no paged form, and the count tables of Nset are ABI 19, below. */
+ *   gnnpe_refine_sets_delta; the rows come page by page through gnnpe_refine_pages_open_delta_nonedges (the last section), and the
+ *   count tables of Nset are ABI 19, below. */
 int gnnpe_host_query_nonedges(const char *query_graph_path, uint32_t *pairs, uint32_t cap, uint32_t *n_pairs);
 int gnnpe_host_refine_sets_delta_nonedges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                           const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *pairs,
@@ -491,7 +492,8 @@ int gnnpe_refine_sets_delta_nonedges(gnnpe_ctx *ctx, const char *query_graph_pat
  *   tallies and flushes of the ABI 17 kernels.  Without dev_accum the table lives in a context-owned, grow-only buffer of its own --
  *   one for VN, another for EN, neither of them a buffer of ABI 13, 14 or 17, whose device views keep their documented lifetimes --
  *   zeroed once per call before the first launch, and valid until the next call of the same function on the context or until the
- *   context's rows are loaded or changed.  *device_ms is as in ABI 17.  There is no paged form. */
+ *   context's rows are loaded or changed.  *device_ms is as in ABI 17.  A table has no rows to page; the rows of Nset come page by
+ *   page through gnnpe_refine_pages_open_delta_nonedges (the last section). */
 int gnnpe_host_refine_sets_delta_nonedges_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                                         const char *query_graph_path, const uint32_t *candidate_bitmap,
                                                         const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
@@ -550,7 +552,8 @@ int gnnpe_refine_sets_delta_nonedges_edge_counts(gnnpe_ctx *ctx, const char *que
  *   first-level chunks of the start candidates S n C(u), in a matching order that starts at u; a map is kept in the launch of its
  *   lowest-numbered query vertex with an image in S only.  Its cost follows DeltaV and nq, not |M|.
  *   matches, matches_cap, the row layout, limit, *device_ms and the ownership of the buffers are exactly those of
- *   gnnpe_refine_sets_delta.  There is no paged form; the count tables of Sset are the next section; adding or removing vertices
+ *   gnnpe_refine_sets_delta.  The rows come page by page through gnnpe_refine_pages_open_delta_vertices (the last section); the
+ *   count tables of Sset are the next section; adding or removing vertices
  *   (n changes), slab contexts and multigraph rows are out of scope. */
 int gnnpe_host_refine_sets_delta_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                           const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *vertices,
@@ -601,7 +604,8 @@ int gnnpe_refine_sets_delta_vertices(gnnpe_ctx *ctx, const char *query_graph_pat
  *   grow-only buffer of its own -- one for VV, another for EV, neither a buffer of ABI 13, 14, 17 or 19, whose device views keep
  *   their documented lifetimes -- zeroed once per call on the stream before the first launch, inside *device_ms, and valid until the
  *   next call of the same function on the context or until the context's rows are loaded or changed.  A single-vertex query has
- *   no edge table: the edge call gives *answers = DeltaV and *dev_counts = NULL.  There is no paged form. */
+ *   no edge table: the edge call gives *answers = DeltaV and *dev_counts = NULL.  A table has no rows to page; the rows of Sset
+ *   come page by page through gnnpe_refine_pages_open_delta_vertices (the last section). */
 int gnnpe_host_refine_sets_delta_vertices_vertex_counts(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                                         const char *query_graph_path, const uint32_t *candidate_bitmap,
                                                         const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
@@ -618,6 +622,63 @@ int gnnpe_refine_sets_delta_vertices_edge_counts(gnnpe_ctx *ctx, const char *que
                                                  const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
                                                  uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts,
                                                  void *dev_accum, int sign, double *device_ms);
+
+/* ---- paged cursors over the delta matches: edges, non-edges and vertices ---------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section only adds symbols.)
+ * A one-shot delta call (gnnpe_refine_sets_delta, _delta_nonedges, _delta_vertices) keeps min(answers, matches_cap) rows and the
+ * rest are gone; a delta of 10^9 rows cannot be handed over at once.  The three functions below open the gnnpe_match_cursor of ABI 10
+ * over the same sets, and gnnpe_refine_pages_next, _device_ptr, _info and _close serve these cursors as they serve ABI 10's: a
+ * continuous-query subscriber, a join against the device page or a writer takes the delta page by page.
+ *
+ * WHAT COMES OUT.  The set of a cursor is Dset_m(C, F) (gnnpe_refine_pages_open_delta; ABI 17), Nset_m(C, F)
+ * (gnnpe_refine_pages_open_delta_nonedges; ABI 18) or Sset_m(C, S) (gnnpe_refine_pages_open_delta_vertices; the vertices section),
+ * with F, the pairs and S handed over as in the one-shot call of the same anchor.  Across the pages of a cursor every map of the set
+ * comes out exactly once, whatever page_rows is: min(|set|, limit) rows in total, every page except the last exactly page_rows rows.
+ * *done, the empty last page, the row layout (column = query vertex id), host_rows == NULL and *device_ms are exactly those of
+ * ABI 10.  The order of the rows is unspecified, and so is which maps come out when `limit` cuts.
+ *
+ * CHARGING.  A map comes out once however many of its query edges, non-adjacent pairs or images land in F or S: the charging rules
+ * of the one-shot kernels are used as they are (a map belongs to the launch of its lowest-numbered query edge or non-adjacent pair
+ * in F, or of its lowest-numbered query vertex with an image in S).  No match is walked or tested twice because of a page end:
+ * the ABI 10 guarantee, which here holds across the launches of the different anchors as well.
+ *
+ * MODES, REFUSALS.  Those of the one-shot call of the same anchor; every refusal sets *cursor = NULL.
+ *   - page_rows == 0: refused, as in ABI 10.
+ *   - the non-edge form: a mode without GNNPE_MATCH_INDUCED is refused.
+ *   - a loop or an id >= n: GNNPE_ERR_ARG on the host before anything is launched.
+ *   - a pair of F that is not an edge (edge form), or that is an edge (non-edge form): found on the device during open, inside the
+ *     one wait open has anyway; GNNPE_ERR_ARG with the one-shot call's message, no cursor is handed out, the context stays usable.
+ *   - NOTHING TO LAUNCH: where the one-shot call launches nothing -- limit 0, an empty C(u), an empty F or S, no vertex of S in any
+ *     set, a single-vertex query under an edge anchor, a query without a non-adjacent pair -- open succeeds and hands out a cursor
+ *     that is done before its first page.  The pairs are then not looked up, as the one-shot calls document.
+ *
+ * OWNERSHIP.  The cursor owns all its device memory: its copy of the bitmap; F as keys, pairs and entries, or S as a bitmap; the
+ * candidate lists and item offsets of every launch; counters, suspend slots and one page.  It touches none of the context's buffers
+ * of the one-shot calls.  Cursors of any kind, the one-shot delta calls, the count-table calls and the filters may therefore
+ * interleave on one context between two pages.  The host arrays may be freed once open returns.
+ *
+ * LIFETIME.  As in ABI 10; gnnpe_csr_apply_edges[_map] and gnnpe_set_vertex_labels (include/gnnpe_hip.h) change the graph and so
+ * invalidate an open delta cursor as well: next returns GNNPE_ERR_ARG and launches nothing, close still works.  For the caller's
+ * update loop this means: the cursor over Dset(G, D) of a DELETION batch D is drained before the deletion is applied (it lists
+ * matches of G), and the cursor over Dset(G', I) of an INSERTION batch I is opened after the insertion is applied (it lists matches
+ * of G'); the same holds for Nset around the opposite change, and for Sset around a relabel or a removal.
+ *
+ * INFO.  info[5] keeps its five fields.  "First-level items not yet taken" counts the current launch and all later launches of the
+ * cursor; "waves suspended" counts the suspend slots that hold a state.  After *done the third and fourth are 0.
+ *
+ * Device form (csrc/gnnpe_refine_delta_pages.hip): one launch per anchor as in the one-shot calls, under the suspend and resume of
+ * ABI 10.  A page that runs from one anchor's launch into the next costs ONE host wait: the launches of the first unfinished anchor
+ * and of all later ones are queued back to back, and a launch that finds the page full returns at once.
+ * Paged forms of the count tables (no rows), slab contexts and multigraph rows are out of scope. */
+int gnnpe_refine_pages_open_delta(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                  const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint64_t page_rows, uint32_t mode,
+                                  gnnpe_match_cursor **cursor);
+int gnnpe_refine_pages_open_delta_nonedges(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                           const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint64_t page_rows, uint32_t mode,
+                                           gnnpe_match_cursor **cursor);
+int gnnpe_refine_pages_open_delta_vertices(gnnpe_ctx *ctx, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                           const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint64_t page_rows,
+                                           uint32_t mode, gnnpe_match_cursor **cursor);
 
 #ifdef __cplusplus
 }
