@@ -59,6 +59,11 @@ SIGNATURES = {
     "gnnpe_csr_carry_entries": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _f64p]),
     "gnnpe_set_vertex_labels": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _f64p]),
     "gnnpe_labels_download": (C.c_int, [_vp, _u32p]),
+    "gnnpe_host_csr_apply_vertices": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint64, _u32p, _u32p, C.c_uint64,
+                                                _u32p, _u32p, _u32p, _u64p]),
+    "gnnpe_csr_apply_vertices": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u32p, _u64p, _u64p, C.POINTER(_vp), C.POINTER(_vp),
+                                           _f64p]),
+    "gnnpe_csr_carry_vertices": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _f64p]),
     "gnnpe_halo_need": (C.c_int, [_vp, C.c_uint32, _u32p, _vp, C.c_uint64, _u64p]),
     "gnnpe_rows_degree": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "gnnpe_rows_pack": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64]),
@@ -652,6 +657,33 @@ def host_entry_map(g_old, g_new):
     if rc:
         raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
     return out
+
+
+NO_VERTEX = 0xFFFFFFFF  # GNNPE_NO_VERTEX of include/gnnpe_hip.h
+
+
+def host_apply_vertices(g, remove=None, add_labels=None):
+    """gnnpe_host_csr_apply_vertices: (g2, vertex_map).  g2 is the graph dict of g without the vertices of `remove` (ids of g,
+    repeats tolerated) and their edges, the survivors in their order under new ids, and with one vertex per label of add_labels
+    appended, each with an empty row.  vertex_map[v'] is the id in g of vertex v' of g2, NO_VERTEX for an added one.  An id
+    outside g or a batch that leaves no vertex raises GnnpeError."""
+    lib = load()
+    o, nb, lab = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    rem, add = _vertex_ids([] if remove is None else remove), _vertex_ids([] if add_labels is None else add_labels)
+    n = len(o) - 1
+    room = n + len(add)  # n' is at most this
+    out_o, out_nb, out_lab, vmap = np.zeros(room + 1, np.uint32), np.zeros(len(nb), np.uint32), np.zeros(room, np.uint32), np.zeros(room, np.uint32)
+    n2, after = C.c_uint32(), C.c_uint64()
+    rc = lib.gnnpe_host_csr_apply_vertices(n, _ptr(o, _u32p), _ptr(nb, _u32p), _ptr(lab, _u32p), _ptr(rem, _u32p) if len(rem) else None, len(rem),
+                                           _ptr(add, _u32p) if len(add) else None, len(add), _ptr(out_o, _u32p), _ptr(out_nb, _u32p),
+                                           len(out_nb), _ptr(out_lab, _u32p), _ptr(vmap, _u32p), C.byref(n2), C.byref(after))
+    if rc:
+        raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
+    out = dict(g)
+    out["n"] = int(n2.value)
+    out["offsets"], out["nbrs"] = out_o[:n2.value + 1].copy(), out_nb[:after.value].copy()
+    out["labels"] = out_lab[:n2.value].copy()
+    return out, vmap[:n2.value].copy()
 
 
 def host_query_symmetry(query_path, pairs_cap=None):
@@ -1497,6 +1529,57 @@ class Engine:
         ms = C.c_double()
         ptrs = [C.c_void_p(int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)) if p is not None else None for p in (src, dst)]
         self._ck(self.lib.gnnpe_csr_carry_entries(self.ctx, int(n_rows), int(elem_bytes), ptrs[0], ptrs[1], C.byref(ms) if timing else None))
+        return ms.value if timing else None
+
+    def apply_vertices(self, remove=None, add_labels=None, entry_map=False, timing=False):
+        """gnnpe_csr_apply_vertices: the vertices of `remove` (ids of the graph on the device, repeats tolerated) leave with their
+        edges, the survivors keep their order under new ids, one vertex per label of add_labels is appended with an empty row;
+        afterwards the context is as load_csr of the new graph's compact CSR leaves it.  Returns (n_after, entries_before,
+        entries_after, vertex_map_view, entry_map_view), with the device ms appended with timing=True.  The views are of the
+        context's own uint32 buffers: vertex_map_view holds the old id of every new vertex (NO_VERTEX for an added one),
+        entry_map_view (None without entry_map=True) the old index of every adjacency entry of the new graph; both are valid until
+        the next apply_vertices or until the rows are loaded or changed (the entry map also until the next apply_edges[_map]);
+        vertex_map_to_host / entry_map_to_host copy them back and refuse a stale view.  carry_vertices, and with entry_map=True
+        carry_entries, move the caller's tables through them.  A refused batch raises GnnpeError, changes nothing and leaves no
+        map; an empty batch changes nothing and gives identity maps."""
+        rem, add = _vertex_ids([] if remove is None else remove), _vertex_ids([] if add_labels is None else add_labels)
+        n2, before, after, ms, vptr, eptr = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_double(), C.c_void_p(), C.c_void_p()
+        self._map_call += 1  # the maps of an earlier batch are gone
+        self._ck(self.lib.gnnpe_csr_apply_vertices(self.ctx, _ptr(rem, _u32p) if len(rem) else None, len(rem),
+                                                   _ptr(add, _u32p) if len(add) else None, len(add), C.byref(n2), C.byref(before),
+                                                   C.byref(after), C.byref(vptr), C.byref(eptr) if entry_map else None,
+                                                   C.byref(ms) if timing else None))
+        if len(rem) or len(add):
+            self._rows_gen += 1  # device views of the count tables are stale
+            self.total = None
+        self.n = int(n2.value)
+        self.entries = after.value
+        self.slab = (0, self.n)
+        vview = _DevArray(int(vptr.value or 0), (self.n,), "<u4", owner=self)
+        vview.valid_for = ("vertex_map", self._rows_gen, self._map_call)
+        eview = None
+        if entry_map:
+            eview = _DevArray(int(eptr.value or 0), (after.value,), "<u4", owner=self)
+            eview.valid_for = ("entry_map", self._rows_gen, self._map_call)
+        return (self.n, before.value, after.value, vview, eview) + ((ms.value,) if timing else ())
+
+    def vertex_map_to_host(self, view):
+        """the vertex map an apply_vertices call returned, copied to the host as uint32; a stale view is refused as
+        entry_map_to_host refuses one"""
+        if getattr(view, "owner", None) is not self or getattr(view, "valid_for", None) != ("vertex_map", self._rows_gen, self._map_call):
+            raise GnnpeError("stale vertex-map view: the map was replaced by a later apply_vertices call or the graph was loaded or changed")
+        return self.copy_to_host(view.__cuda_array_interface__["data"][0], view.shape[0] * 4).view(np.uint32)
+
+    def carry_vertices(self, src, dst, n_rows, elem_bytes=8, timing=False):
+        """gnnpe_csr_carry_vertices: a caller's per-vertex table moved from the vertices of the graph before the last
+        apply_vertices to those of the graph after it, on the device: dst[r, v'] = src[r, vertex_map[v']], 0 at an added vertex.
+        src is (n_rows, n_before), dst (n_rows, n_after), row-major, cells of elem_bytes = 8 (the count tables) or 4; device
+        pointers as carry_entries takes them, not overlapping.  Without a valid vertex map (none made, a refused batch, the rows
+        loaded or changed since -- apply_edges included) the call raises GnnpeError and launches nothing.  Returns None, the
+        device ms with timing=True."""
+        ms = C.c_double()
+        ptrs = [C.c_void_p(int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)) if p is not None else None for p in (src, dst)]
+        self._ck(self.lib.gnnpe_csr_carry_vertices(self.ctx, int(n_rows), int(elem_bytes), ptrs[0], ptrs[1], C.byref(ms) if timing else None))
         return ms.value if timing else None
 
     def set_vertex_labels(self, vertices, labels, timing=False):

@@ -159,6 +159,13 @@ struct gnnpe_ctx {
     gnnpe::DevBuf upd_map;
     bool map_valid = false;
     uint64_t map_gen = 0, map_before = 0, map_after = 0;
+    // gnnpe_csr_apply_vertices (gnnpe_update_vertices.hip): the vertex map of the last batch (one word per vertex of G': its id in G
+    // or GNNPE_NO_VERTEX), grow-only, valid as the entry map is; vmap_before / vmap_after are n and n' (the strides of
+    // gnnpe_csr_carry_vertices).  upd_labels / upd_present: the spare label and presence arrays of G', swapped with the live ones as
+    // the spare start / degree / neighbour arrays above are (a batch may grow n: DevBuf::reserve keeps no contents)
+    gnnpe::DevBuf upd_vmap, upd_labels, upd_present;
+    bool vmap_valid = false;
+    uint64_t vmap_gen = 0, vmap_before = 0, vmap_after = 0;
     // rows longer than 64 entries ("hub" rows of the l=2 enumeration): ids and adjacency ranges; graph-only, rebuilt
     // whenever rows are loaded / appended / dropped
     gnnpe::DevBuf hub_rows, hub_beg, hub_end;

@@ -46,14 +46,9 @@
 #include <algorithm>
 
 #include "gnnpe_common.h"
+#include "gnnpe_update.hip.h"
 
 namespace gnnpe {
-
-// gnnpe_kernels.hip.h (compiled into gnnpe_engine.hip): used as they are
-__global__ void k_offsets_to_start_deg(uint32_t n, const uint32_t *__restrict__ offs, uint32_t *__restrict__ start,
-                                       uint32_t *__restrict__ deg, uint8_t *__restrict__ present);
-__global__ void k_gather_u32(uint64_t cnt, const uint32_t *__restrict__ idx, const uint32_t *__restrict__ table,
-                             uint32_t *__restrict__ out);
 
 typedef unsigned long long ukey;
 constexpr ukey kNoKey = ~0ull;
@@ -215,12 +210,6 @@ __global__ __launch_bounds__(kBlock) void k_csr_merge(uint32_t copy_blocks, uint
     }
 }
 
-// the entry map of the empty batch: every entry stays where it is
-static __global__ void k_map_identity(uint32_t entries, uint32_t *__restrict__ map)
-{
-    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < entries; j += (uint64_t)gridDim.x * blockDim.x) map[j] = (uint32_t)j;
-}
-
 // gnnpe_csr_carry_entries: dst[r][j'] = src[r][map[j']], 0 where the map says GNNPE_NO_ENTRY.  A block takes kCarryTile
 // consecutive new entries per step, lane t the entries a + t, a + kBlock + t, ...: consecutive lanes hold consecutive j', and
 // between two touched rows map[j'] - j' is constant, so the loads of a wave are as consecutive as its stores (one 256- or
@@ -278,15 +267,6 @@ static __global__ __launch_bounds__(kBlock) void k_set_labels(uint32_t count, co
     }
 }
 
-static void swap_buffers(DevBuf &a, DevBuf &b)
-{
-    std::swap(a.p, b.p);
-    std::swap(a.bytes, b.bytes);
-}
-
-// room for `need` bytes without losing what `live` holds if the device refuses: a buffer that has to grow is allocated in `fresh`
-static int grow_aside(const DevBuf &live, DevBuf &fresh, size_t need) { return need <= live.bytes ? GNNPE_OK : fresh.reserve(need); }
-
 // pairs -> the two directed keys of each; a loop or an id >= n is refused
 static int directed_keys(const char *who, const char *what, uint32_t n, const uint32_t *edges, uint64_t n_edges, std::vector<ukey> *keys)
 {
@@ -319,51 +299,9 @@ static int sort_unique(gnnpe_ctx *c, ukey *in, ukey *tmp, ukey *out, uint32_t co
     return GNNPE_OK;
 }
 
-// device_ms and, with GNNPE_DEBUG=1, its parts: [0] after the uploads, [1] after the merge, [2] after the wait and the decision
-// (before the rebuild's first copy), [3] after the rebuild
-struct UpdateEvents {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~UpdateEvents()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-// device_ms of a call that is one launch: events right around it on the stream (nothing is created where device_ms is NULL)
-struct LaunchTimer {
-    UpdateEvents E;
-    double *out = nullptr;
-    int begin(double *device_ms, hipStream_t stream)
-    {
-        if (!(out = device_ms)) return GNNPE_OK;
-        GNNPE_HIP_TRY(hipEventCreate(&E.ev[0]));
-        GNNPE_HIP_TRY(hipEventCreate(&E.ev[1]));
-        GNNPE_HIP_TRY(hipEventRecord(E.ev[0], stream));
-        return GNNPE_OK;
-    }
-    int end(hipStream_t stream)
-    {
-        if (!out) return GNNPE_OK;
-        float ms = 0.f;
-        GNNPE_HIP_TRY(hipEventRecord(E.ev[1], stream));
-        GNNPE_HIP_TRY(hipEventSynchronize(E.ev[1]));
-        GNNPE_HIP_TRY(hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
-        *out = ms;
-        return GNNPE_OK;
-    }
-};
-
 }  // namespace gnnpe
 
 using namespace gnnpe;
-
-static int require_whole_graph(const char *who, gnnpe_ctx *c)
-{
-    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
-    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
-    return GNNPE_OK;
-}
 
 // The body of gnnpe_csr_apply_edges and gnnpe_csr_apply_edges_map.  want_map: the merge also writes the entry map into
 // c->upd_map and a success marks it valid for the new rows; the empty batch writes the identity map.
@@ -561,15 +499,12 @@ extern "C" int gnnpe_csr_apply_edges_map(gnnpe_ctx *c, const uint32_t *insert_ed
     return GNNPE_OK;
 }
 
-extern "C" int gnnpe_csr_carry_entries(gnnpe_ctx *c, uint32_t n_rows, uint32_t elem_bytes, const void *dev_src, void *dev_dst, double *device_ms)
+// The body of gnnpe_csr_carry_entries and gnnpe_csr_carry_vertices: the same gather, through the entry map or the vertex map
+// (`before` / `after`: the columns of src / dst; a map word of 0xFFFFFFFF -- GNNPE_NO_ENTRY, GNNPE_NO_VERTEX -- gives 0).
+static int carry_through(gnnpe_ctx *c, const char *who, const uint32_t *map, uint64_t before, uint64_t after, uint32_t n_rows, uint32_t elem_bytes,
+                         const void *dev_src, void *dev_dst, double *device_ms)
 {
-    const char *who = "gnnpe_csr_carry_entries";
-    GNNPE_REQUIRE(c, GNNPE_ERR_ARG, "%s: null argument", who);
-    if (device_ms) *device_ms = 0.0;
-    GNNPE_REQUIRE(c->map_valid && c->map_gen == c->graph_gen && c->have_graph, GNNPE_ERR_ARG,
-                  "%s: the context has no valid entry map (gnnpe_csr_apply_edges_map makes one; loading or changing the rows ends it)", who);
     GNNPE_REQUIRE(elem_bytes == 4 || elem_bytes == 8, GNNPE_ERR_ARG, "%s: elem_bytes %u, 4 or 8 expected", who, elem_bytes);
-    const uint64_t before = c->map_before, after = c->map_after;
     if (n_rows == 0 || after == 0) return GNNPE_OK;
     const uint64_t src_bytes = (uint64_t)n_rows * before * elem_bytes, dst_bytes = (uint64_t)n_rows * after * elem_bytes;
     GNNPE_REQUIRE(dev_dst && (dev_src || src_bytes == 0), GNNPE_ERR_ARG, "%s: null argument", who);
@@ -583,12 +518,34 @@ extern "C" int gnnpe_csr_carry_entries(gnnpe_ctx *c, uint32_t n_rows, uint32_t e
     const uint32_t grid = (uint32_t)std::min<uint64_t>((after + kCarryTile - 1) / kCarryTile, (uint64_t)c->num_cus * 8);
     if (elem_bytes == 8)
         hipLaunchKernelGGL(k_carry_entries<uint64_t>, dim3(grid), dim3(kBlock), 0, c->stream, n_rows, (uint32_t)before, (uint32_t)after,
-                           c->upd_map.as<uint32_t>(), static_cast<const uint64_t *>(dev_src), static_cast<uint64_t *>(dev_dst));
+                           map, static_cast<const uint64_t *>(dev_src), static_cast<uint64_t *>(dev_dst));
     else
         hipLaunchKernelGGL(k_carry_entries<uint32_t>, dim3(grid), dim3(kBlock), 0, c->stream, n_rows, (uint32_t)before, (uint32_t)after,
-                           c->upd_map.as<uint32_t>(), static_cast<const uint32_t *>(dev_src), static_cast<uint32_t *>(dev_dst));
+                           map, static_cast<const uint32_t *>(dev_src), static_cast<uint32_t *>(dev_dst));
     GNNPE_HIP_TRY(hipGetLastError());
     return timer.end(c->stream);
+}
+
+extern "C" int gnnpe_csr_carry_entries(gnnpe_ctx *c, uint32_t n_rows, uint32_t elem_bytes, const void *dev_src, void *dev_dst, double *device_ms)
+{
+    const char *who = "gnnpe_csr_carry_entries";
+    GNNPE_REQUIRE(c, GNNPE_ERR_ARG, "%s: null argument", who);
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c->map_valid && c->map_gen == c->graph_gen && c->have_graph, GNNPE_ERR_ARG,
+                  "%s: the context has no valid entry map (gnnpe_csr_apply_edges_map makes one; loading or changing the rows ends it)", who);
+    return carry_through(c, who, c->upd_map.as<uint32_t>(), c->map_before, c->map_after, n_rows, elem_bytes, dev_src, dev_dst, device_ms);
+}
+
+// (the vertex map of csrc/gnnpe_update_vertices.hip; the kernel is k_carry_entries: a vertex table has n columns where an entry
+// table has offsets[n])
+extern "C" int gnnpe_csr_carry_vertices(gnnpe_ctx *c, uint32_t n_rows, uint32_t elem_bytes, const void *dev_src, void *dev_dst, double *device_ms)
+{
+    const char *who = "gnnpe_csr_carry_vertices";
+    GNNPE_REQUIRE(c, GNNPE_ERR_ARG, "%s: null argument", who);
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c->vmap_valid && c->vmap_gen == c->graph_gen && c->have_graph, GNNPE_ERR_ARG,
+                  "%s: the context has no valid vertex map (gnnpe_csr_apply_vertices makes one; loading or changing the rows ends it)", who);
+    return carry_through(c, who, c->upd_vmap.as<uint32_t>(), c->vmap_before, c->vmap_after, n_rows, elem_bytes, dev_src, dev_dst, device_ms);
 }
 
 extern "C" int gnnpe_set_vertex_labels(gnnpe_ctx *c, const uint32_t *vertices, const uint32_t *labels, uint64_t count, double *device_ms)

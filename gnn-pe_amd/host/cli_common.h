@@ -78,6 +78,9 @@ struct Options {
     // --set-labels FILE (exact -m online / -m filter only): lines `v label`, new labels for those data vertices, set on the device
     // after --apply-edges and before anything is computed from the graph (gnnpe_set_vertex_labels)
     std::string set_labels_file;
+    // --apply-vertices FILE (exact -m online / -m filter only): lines `- v` / `+ label`, a batch of vertex removals and additions
+    // applied to the loaded data graph on the device before --apply-edges and --set-labels (gnnpe_csr_apply_vertices)
+    std::string apply_vertices_file;
     bool induced = false;   // --induced (needs --refine sets): induced matching, query non-edges on data non-edges (GNNPE_MATCH_INDUCED)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
@@ -158,7 +161,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE | --delta-vertices FILE)\n"
                    "           [--delta-vertex-counts FILE | --delta-edge-counts FILE | --delta-pages ROWS]] [--apply-edges FILE]\n"
-                   "           [--set-labels FILE]\n"
+                   "           [--set-labels FILE] [--apply-vertices FILE]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -192,7 +195,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --edge-counts): FILE has one data vertex id per line; the\n"
                    "       answer is the number of matches with at least one image among them, each match once, and --matches writes those;\n"
                    "       --set-labels FILE (exact mode only: --exact or -l 3): FILE has one line `v label` per vertex; the labels are set\n"
-                   "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's\n",
+                   "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's\n"
+                   "       --apply-vertices FILE (exact mode only: --exact or -l 3): FILE has one line `- v` (remove vertex v with its edges;\n"
+                   "       the survivors keep their order under new ids) or `+ label` (append a vertex with that label and no edges) per\n"
+                   "       change; applied on the device first, so that --apply-edges, --set-labels and --delta-vertices name the new ids\n",
                    tool, tool);
             exit(0);
         }
@@ -212,7 +218,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges" ||
             a == "--delta-nonedges" ||
             a == "--apply-edges" || a == "--delta-vertex-counts" || a == "--delta-edge-counts" || a == "--delta-vertices" ||
-            a == "--set-labels") {
+            a == "--set-labels" || a == "--apply-vertices") {
             if (i + 1 >= argc) die(a + " needs a value");
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }
             if (a == "--vertex-counts") { o.vertex_counts_file = argv[++i]; continue; }
@@ -224,6 +230,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; continue; }
             if (a == "--delta-vertices") { o.delta_vertices_file = argv[++i]; continue; }
             if (a == "--set-labels") { o.set_labels_file = argv[++i]; continue; }
+            if (a == "--apply-vertices") { o.apply_vertices_file = argv[++i]; continue; }
             o.refine = argv[++i];
             if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;

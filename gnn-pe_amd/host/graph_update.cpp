@@ -1,6 +1,7 @@
 // graph_update.cpp -- gnnpe_host_csr_apply_edges: sort and de-duplicate the directed keys of the two lists, check them against
 // the rows, merge row by row.  gnnpe_host_csr_entry_map: the entries of one CSR among those of another, a two-pointer walk per
-// row.  Plain C++; shares nothing with csrc/gnnpe_update.hip.
+// row.  gnnpe_host_csr_apply_vertices: a table of new ids, then the rows of the survivors copied entry by entry.  Plain C++; shares
+// nothing with csrc/gnnpe_update.hip or csrc/gnnpe_update_vertices.hip.
 #include "graph_update.h"
 
 #include <algorithm>
@@ -97,6 +98,56 @@ void csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint32_t *old_
             map[k] = j < end && old_nbrs[j] == new_nbrs[k] ? j : 0xFFFFFFFFu;
         }
     }
+}
+
+int csr_apply_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels, const uint32_t *remove,
+                       uint64_t n_remove, const uint32_t *add_labels, uint64_t n_add, std::vector<uint32_t> *out_offsets,
+                       std::vector<uint32_t> *out_nbrs, std::vector<uint32_t> *out_labels, std::vector<uint32_t> *vertex_map, std::string *err)
+{
+    // new id of every vertex, 0xFFFFFFFF for a removed one: a running count of the survivors
+    std::vector<uint32_t> id((size_t)n, 0);
+    for (uint64_t i = 0; i < n_remove; i++) {
+        if (remove[i] >= n) {
+            *err = "vertex " + std::to_string(remove[i]) + " is not a vertex of the graph (n = " + std::to_string(n) + ")";
+            return -1;
+        }
+        id[remove[i]] = 0xFFFFFFFFu;
+    }
+    uint64_t kept = 0;
+    for (uint32_t v = 0; v < n; v++)
+        if (id[v] != 0xFFFFFFFFu) id[v] = (uint32_t)kept++;
+    const uint64_t after = kept + n_add;
+    if (after == 0) {
+        *err = "the batch leaves no vertex";
+        return -1;
+    }
+    if (after >= 0xFFFFFFFFull) {
+        *err = std::to_string(after) + " vertices exceed 32-bit ids";
+        return -5;
+    }
+    out_offsets->clear();
+    out_nbrs->clear();
+    out_labels->clear();
+    vertex_map->clear();
+    for (uint32_t v = 0; v < n; v++) {
+        if (id[v] == 0xFFFFFFFFu) continue;
+        out_offsets->push_back((uint32_t)out_nbrs->size());
+        out_labels->push_back(labels[v]);
+        vertex_map->push_back(v);
+        for (uint32_t j = offsets[v]; j < offsets[v + 1]; j++)
+            if (id[nbrs[j]] != 0xFFFFFFFFu) out_nbrs->push_back(id[nbrs[j]]);
+    }
+    for (uint64_t i = 0; i < n_add; i++) {
+        out_offsets->push_back((uint32_t)out_nbrs->size());
+        out_labels->push_back(add_labels[i]);
+        vertex_map->push_back(0xFFFFFFFFu);
+    }
+    out_offsets->push_back((uint32_t)out_nbrs->size());
+    if (out_nbrs->size() + after >= (1ull << 32)) {
+        *err = std::to_string(out_nbrs->size()) + " entries + " + std::to_string(after) + " vertices exceed 32-bit addressing";
+        return -5;
+    }
+    return 0;
 }
 
 }  // namespace gnnpe_host

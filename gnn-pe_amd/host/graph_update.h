@@ -22,4 +22,12 @@ int csr_apply_edges(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, c
 void csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint32_t *old_nbrs, const uint32_t *new_offsets, const uint32_t *new_nbrs,
                    uint32_t *map);
 
+// The host form of gnnpe_csr_apply_vertices: the vertices of `remove` (ids < n, repeats tolerated) leave with their edges, the
+// survivors keep their order under new ids, one vertex per word of add_labels is appended with an empty row.  vertex_map: the old
+// id of every new vertex, 0xFFFFFFFF (GNNPE_NO_VERTEX) for an added one.  0, or -1 (an id >= n, no vertex left: *err says which) /
+// -5 (n' >= 2^32 - 1 or entries' + n' >= 2^32); the outputs of a refused batch mean nothing.
+int csr_apply_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels, const uint32_t *remove,
+                       uint64_t n_remove, const uint32_t *add_labels, uint64_t n_add, std::vector<uint32_t> *out_offsets,
+                       std::vector<uint32_t> *out_nbrs, std::vector<uint32_t> *out_labels, std::vector<uint32_t> *vertex_map, std::string *err);
+
 }  // namespace gnnpe_host

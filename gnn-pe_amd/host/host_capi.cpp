@@ -540,4 +540,35 @@ int gnnpe_host_csr_entry_map(uint32_t n, const uint32_t *old_offsets, const uint
     return GNNPE_OK;
 }
 
+int gnnpe_host_csr_apply_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels, const uint32_t *remove,
+                                  uint64_t n_remove, const uint32_t *add_labels, uint64_t n_add, uint32_t *out_offsets, uint32_t *out_nbrs,
+                                  uint64_t out_cap, uint32_t *out_labels, uint32_t *vertex_map, uint32_t *n_after, uint64_t *n_entries_after)
+{
+    if (!offsets || (!nbrs && offsets[n]) || (!labels && n) || (!remove && n_remove) || (!add_labels && n_add) || !out_offsets || !out_labels ||
+        !vertex_map || !n_after || !n_entries_after || (!out_nbrs && out_cap)) {
+        gnnpe::set_error("gnnpe_host_csr_apply_vertices: null argument");
+        return GNNPE_ERR_ARG;
+    }
+    *n_after = 0;
+    *n_entries_after = 0;
+    std::vector<uint32_t> off, nb, lab, vmap;
+    std::string err;
+    const int rc = gnnpe_host::csr_apply_vertices(n, offsets, nbrs, labels, remove, n_remove, add_labels, n_add, &off, &nb, &lab, &vmap, &err);
+    if (rc != 0) {
+        gnnpe::set_error("gnnpe_host_csr_apply_vertices: %s", err.c_str());
+        return rc == -5 ? GNNPE_ERR_RANGE : GNNPE_ERR_ARG;
+    }
+    *n_after = (uint32_t)lab.size();
+    *n_entries_after = nb.size();
+    if (nb.size() > out_cap) {
+        gnnpe::set_error("gnnpe_host_csr_apply_vertices: %zu entries, room for %llu", nb.size(), (unsigned long long)out_cap);
+        return GNNPE_ERR_ARG;
+    }
+    memcpy(out_offsets, off.data(), off.size() * 4);
+    if (!nb.empty()) memcpy(out_nbrs, nb.data(), nb.size() * 4);
+    memcpy(out_labels, lab.data(), lab.size() * 4);
+    memcpy(vertex_map, vmap.data(), vmap.size() * 4);
+    return GNNPE_OK;
+}
+
 }  // extern "C"

@@ -243,6 +243,20 @@ void read_label_list(const std::string &path, std::vector<uint32_t> *vs, std::ve
     fclose(lf);
 }
 
+// the file of --apply-vertices: one `- v` (remove the vertex) or `+ label` (add a vertex with that label) per line
+void read_vertex_batch(const std::string &path, std::vector<uint32_t> *remove, std::vector<uint32_t> *add_labels)
+{
+    FILE *vf = fopen(path.c_str(), "r");
+    if (!vf) die("cannot read " + path);
+    char sign = 0;
+    unsigned long long x = 0;
+    for (int got; (got = fscanf(vf, " %c %llu", &sign, &x)) != EOF;) {
+        if (got != 2 || (sign != '+' && sign != '-') || x > 0xFFFFFFFFull) die(path + ": one `- v` or `+ label` per line expected");
+        (sign == '+' ? add_labels : remove)->push_back((uint32_t)x);
+    }
+    fclose(vf);
+}
+
 // the file of --matches: one match per line, the images of the query vertices in their order
 struct MatchFile {
     const std::string &path;
@@ -451,9 +465,9 @@ int run_filter(const Options &o)
     if (rc != 0) die(o.data_graph + ": " + err);
     if (exact && o.mode == "online" && !g.simple)  // the refinement counts embeddings in simple graphs only (gnnpe_refine)
         die(o.data_graph + " repeats an edge (duplicate `e` lines): exact -m online (--exact, -l 3) needs a simple graph");
-    // with --apply-edges or --set-labels the metadata block and the plan size are printed once the batch is applied and the labels
-    // are set: they describe the graph the answer is for
-    const bool updating = !o.apply_edges_file.empty() || !o.set_labels_file.empty();
+    // with --apply-vertices, --apply-edges or --set-labels the metadata block and the plan size are printed once the batches are
+    // applied and the labels are set: they describe the graph the answer is for
+    const bool updating = !o.apply_vertices_file.empty() || !o.apply_edges_file.empty() || !o.set_labels_file.empty();
     if (!updating) fputs(g.metadata_text().c_str(), stdout);
     std::vector<uint32_t> sorted_nodes, membership;
     if (gnnpe_host::read_membership(o.dataset_path + "gnn-pe/membership.txt", g.n, o.partition_num, &sorted_nodes,
@@ -477,6 +491,58 @@ int run_filter(const Options &o)
     gnnpe_ctx *ctx = gnnpe_create(0);
     if (!ctx) die(std::string("gnnpe_create: ") + gnnpe_last_error());
     check(load_graph_into(ctx, g), "load_csr");
+    // the host copy follows the device (g.n is set by the caller): the count tables below are indexed by the entries of the CSR the
+    // context holds
+    auto follow_rows = [&](uint64_t entries) {
+        g.offsets.assign((size_t)g.n + 1, 0);
+        g.neighbors.assign(entries, 0);
+        check(gnnpe_csr_download(ctx, g.offsets.data(), g.neighbors.data(), entries, &entries), "csr_download");
+        g.m = (uint32_t)(entries / 2);
+        g.max_degree = 0;
+        for (uint32_t v = 0; v < g.n; v++) g.max_degree = std::max(g.max_degree, g.offsets[v + 1] - g.offsets[v]);
+    };
+    // ... with the label figures of the metadata block (graph.cpp:223)
+    auto follow_labels = [&]() {
+        g.labels.assign(g.n, 0);
+        check(gnnpe_labels_download(ctx, g.labels.data()), "labels_download");
+        std::map<uint32_t, uint32_t> freq;
+        uint32_t max_label = 0;
+        for (uint32_t x = 0; x < g.n; x++) {
+            freq[g.labels[x]]++;
+            max_label = std::max(max_label, g.labels[x]);
+        }
+        g.labels_count = std::max<uint32_t>((uint32_t)freq.size(), g.n ? max_label + 1 : 0);
+        g.max_label_frequency = 0;
+        for (const auto &kv : freq) g.max_label_frequency = std::max(g.max_label_frequency, kv.second);
+    };
+    if (!o.apply_vertices_file.empty()) {  // first: an edge file may name the new ids
+        std::vector<uint32_t> rem, add;
+        read_vertex_batch(o.apply_vertices_file, &rem, &add);
+        uint32_t n2 = 0;
+        uint64_t entries = 0;
+        void *dev_vmap = nullptr;
+        check(gnnpe_csr_apply_vertices(ctx, rem.data(), rem.size(), add.data(), add.size(), &n2, nullptr, &entries, &dev_vmap, nullptr, nullptr),
+              "--apply-vertices");
+        std::vector<uint32_t> vmap(n2);
+        check(gnnpe_copy_to_host(ctx, vmap.data(), dev_vmap, (uint64_t)n2 * 4), "vertex map");
+        // order and membership through the vertex map: the survivors in their old order, the added vertices behind them in partition 0
+        // (exact mode's candidate sets do not depend on the order)
+        std::vector<uint32_t> new_id(g.n, GNNPE_NO_VERTEX), order, member(n2, 0);
+        for (uint32_t v = 0; v < n2; v++)
+            if (vmap[v] != GNNPE_NO_VERTEX) {
+                new_id[vmap[v]] = v;
+                member[v] = membership[vmap[v]];
+            }
+        for (uint32_t v : sorted_nodes)
+            if (new_id[v] != GNNPE_NO_VERTEX) order.push_back(new_id[v]);
+        for (uint32_t v = 0; v < n2; v++)
+            if (vmap[v] == GNNPE_NO_VERTEX) order.push_back(v);
+        sorted_nodes.swap(order);
+        membership.swap(member);
+        g.n = n2;
+        follow_rows(entries);
+        follow_labels();
+    }
     if (!o.apply_edges_file.empty()) {  // the whole query runs on the updated graph
         std::vector<uint32_t> ins, del;
         FILE *af = fopen(o.apply_edges_file.c_str(), "r");
@@ -493,28 +559,13 @@ int run_filter(const Options &o)
         fclose(af);
         uint64_t entries = 0;
         check(gnnpe_csr_apply_edges(ctx, ins.data(), ins.size() / 2, del.data(), del.size() / 2, &entries, nullptr), "--apply-edges");
-        // the host copy follows the device: the count tables below are indexed by the entries of the CSR the context holds
-        g.neighbors.assign(entries, 0);
-        check(gnnpe_csr_download(ctx, g.offsets.data(), g.neighbors.data(), entries, &entries), "csr_download");
-        g.m = (uint32_t)(entries / 2);
-        g.max_degree = 0;
-        for (uint32_t v = 0; v < g.n; v++) g.max_degree = std::max(g.max_degree, g.offsets[v + 1] - g.offsets[v]);
+        follow_rows(entries);
     }
     if (!o.set_labels_file.empty()) {  // ... and on the relabelled one
         std::vector<uint32_t> vs, ls;
         read_label_list(o.set_labels_file, &vs, &ls);
         check(gnnpe_set_vertex_labels(ctx, vs.data(), ls.data(), vs.size(), nullptr), "--set-labels");
-        // the host copy follows the device, with the label figures of the metadata block (graph.cpp:223)
-        check(gnnpe_labels_download(ctx, g.labels.data()), "labels_download");
-        std::map<uint32_t, uint32_t> freq;
-        uint32_t max_label = 0;
-        for (uint32_t x = 0; x < g.n; x++) {
-            freq[g.labels[x]]++;
-            max_label = std::max(max_label, g.labels[x]);
-        }
-        g.labels_count = std::max<uint32_t>((uint32_t)freq.size(), g.n ? max_label + 1 : 0);
-        g.max_label_frequency = 0;
-        for (const auto &kv : freq) g.max_label_frequency = std::max(g.max_label_frequency, kv.second);
+        follow_labels();
     }
     if (updating) {
         fputs(g.metadata_text().c_str(), stdout);
@@ -690,6 +741,13 @@ int main(int argc, char **argv)
     if (!o.set_labels_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
         die("--set-labels applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
             "made from the graph as it was");
+    if (!o.apply_vertices_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
+        die("--apply-vertices applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
+            "made from the graph as it was");
+    if (!o.apply_vertices_file.empty()) {  // a malformed file is refused before a GPU is touched
+        std::vector<uint32_t> rem, add;
+        read_vertex_batch(o.apply_vertices_file, &rem, &add);
+    }
     if (!o.set_labels_file.empty()) {  // a malformed file is refused before a GPU is touched
         std::vector<uint32_t> vs, ls;
         read_label_list(o.set_labels_file, &vs, &ls);

@@ -258,12 +258,98 @@ int gnnpe_csr_carry_entries(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes
  *   - GNNPE_ERR_UNSUPPORTED: no whole graph on the device (nothing loaded, or gnnpe_load_rows), or the multigraph state.
  * count == 0 succeeds, launches nothing and changes nothing: the generation stays, cursors stay valid.
  * *device_ms (may be NULL) covers the kernel, not the upload of the two lists.
- * Adding or removing vertices (n changes), slab contexts and multigraph rows are out of scope.
+ * Slab contexts and multigraph rows are out of scope (adding or removing vertices: the next section).
  *
  * gnnpe_labels_download: the labels the context holds, n words -- for a caller without a host mirror.  Whole graph only
  *   (GNNPE_ERR_UNSUPPORTED otherwise). */
 int gnnpe_set_vertex_labels(gnnpe_ctx *ctx, const uint32_t *vertices, const uint32_t *labels, uint64_t count, double *device_ms);
 int gnnpe_labels_download(gnnpe_ctx *ctx, uint32_t *host_labels);
+
+/* ---- vertex removals and additions on the resident graph ------------------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section only adds symbols.)
+ * The one change the edge batches and the relabel cannot make is to the vertex set: a caller whose graph gains one vertex had to
+ * rebuild the whole CSR and call gnnpe_load_csr, losing every per-vertex and per-edge table it keeps on the device.  These calls
+ * apply a BATCH of vertex removals R and additions A to the whole graph the context holds, from the few words that describe it.
+ *
+ * The batch.  remove: n_remove ids of the current graph, a repeated id means the vertex once.  add_labels: the labels of the n_add
+ * vertices to add, in order.  Either list may be NULL where its count is 0.
+ *
+ * Result.  G' has n' = n - |R| + |A| vertices.  A surviving vertex v gets the id v - |{r in R : r < v}|: survivors keep their
+ * relative order.  Added vertex i gets the id n - |R| + i, the label add_labels[i] and an EMPTY row; its edges arrive through a
+ * following gnnpe_csr_apply_edges, which may name the new ids.  Every edge with an end in R is gone, every other edge stands under
+ * the new ids.  G' is the COMPACT CSR that G' alone determines: rows back to back, each strictly ascending; its entry indices are
+ * those of gnnpe_csr_download and of the host form.
+ *
+ * Two maps describe the batch.
+ *   - The vertex map: one uint32 per vertex v' of G': the old id of v', or GNNPE_NO_VERTEX for an added vertex.
+ *   - The entry map: one uint32 per entry j' of G': the index of that entry in G.  No entry is new, so it never holds
+ *     GNNPE_NO_ENTRY; it is strictly increasing, and its image is the entries of G with both ends outside R.
+ *
+ * gnnpe_host_csr_apply_vertices: the host form and the yardstick (host/graph_update.cpp): a table of new ids, the survivors' rows
+ *   copied entry by entry.  It shares no code with the device form.  out_offsets: n' + 1 words; out_labels and vertex_map: n' words
+ *   (n - |R| + n_add: the caller knows R); out_nbrs: out_cap words -- too few returns GNNPE_ERR_ARG with *n_after and
+ *   *n_entries_after set (offsets[n] entries always suffice).  The same refusals as the device form (no context, so no UNSUPPORTED;
+ *   a null output pointer is GNNPE_ERR_ARG); nothing is written on a refusal but the two counts.
+ *
+ * gnnpe_csr_apply_vertices: the device form (csrc/gnnpe_update_vertices.hip).
+ *   State after success: precisely what gnnpe_load_csr(ctx, n', offsets', nbrs', labels') leaves.  The graph generation moves on,
+ *   so open match cursors refuse to go on; the reverse positions, the hub-row list and the neighbours' labels are rebuilt by the
+ *   loader's own tail; order, slab and everything derived from the rows are reset as the loader resets them; the device tables of
+ *   gnnpe_refine_sets_vertex_counts / _edge_counts end by their "rows loaded or changed".
+ *   *n_after, *n_entries_before, *n_entries_after (each may be NULL) are set on every return; on a refusal they hold the unchanged
+ *   graph's counts.
+ *   Maps.  The vertex map is always produced, into a context-owned grow-only buffer; dev_vertex_map may be NULL if the caller does
+ *   not want the pointer.  The entry map is produced only where dev_entry_map is not NULL, into the slot of
+ *   gnnpe_csr_apply_edges_map: gnnpe_csr_carry_entries then works after this call exactly as after that one.  With dev_entry_map ==
+ *   NULL the context is left without a valid entry map, as a plain gnnpe_csr_apply_edges leaves it.  Both maps are valid until the
+ *   next gnnpe_csr_apply_vertices (of any batch and any outcome) or any other call that loads or changes the context's rows; the
+ *   entry map also ends at the next gnnpe_csr_apply_edges / _map.  On a refusal both pointers are NULL and the maps of an earlier
+ *   batch are gone.
+ *   The empty batch (n_remove == n_add == 0) succeeds, leaves graph and generation alone (cursors stay valid) and produces identity
+ *   maps where maps were asked for, so a caller's loop needs no special case.
+ *   Refusals.  Each leaves the context as it was -- the same graph, the same generation (open cursors go on), derived state kept:
+ *   the new arrays are built in spare buffers and swapped in only on success.
+ *     - GNNPE_ERR_ARG, on the host before anything is launched: a null list with a count > 0, an id >= n, n' == 0.
+ *     - GNNPE_ERR_UNSUPPORTED: no whole graph on the device (nothing loaded, or gnnpe_load_rows), or the multigraph state.
+ *     - GNNPE_ERR_RANGE: n' >= 2^32 - 1 (on the host before anything is launched), or entries' + n' >= 2^32 (entries' is known
+ *       only after the compaction: decided in the call's single wait, with nothing but spare buffers written).
+ *     - an allocation the device refuses before the swap returns its error and leaves the context usable and unchanged: whatever
+ *       has to grow with n' (start, degree, label, presence and ownership arrays) is allocated aside and swapped in on success.
+ *       The rebuild after the swap is gnnpe_load_csr's own tail and fails as that does (see gnnpe_csr_apply_edges).
+ *   *device_ms (may be NULL) covers everything between the upload of the two lists and the end of the rebuild, not the uploads.
+ *   Transient memory: as gnnpe_csr_apply_edges (the same spare arrays), a spare label array, one flag byte per entry of G.
+ *
+ * gnnpe_csr_carry_vertices: for r < n_rows and v' < n', dst[r][v'] = src[r][vertex_map[v']], or 0 where the map says
+ *   GNNPE_NO_VERTEX, through the context's valid vertex map.  src is row-major n_rows x n, dst row-major n_rows x n', cells of
+ *   elem_bytes = 8 (the count tables) or 4; both are the caller's device memory on the context's device, aligned to their cells.
+ *   The work runs on the context's stream; every cell of dst is written exactly once, src is not written.  GNNPE_ERR_ARG, with
+ *   nothing launched, as gnnpe_csr_carry_entries: the context has no valid vertex map (none was made, the last
+ *   gnnpe_csr_apply_vertices was refused, or the rows were loaded or changed since -- a following gnnpe_csr_apply_edges included:
+ *   carry the vertex tables before the edges of the new vertices are inserted), elem_bytes is neither 4 nor 8, a pointer is null or
+ *   misaligned while there is something to move, or the byte ranges overlap.  n_rows == 0 succeeds and launches nothing.
+ *   This is what keeps a gnnpe_refine_sets_vertex_counts table on the device across the batch.
+ *
+ * The loops, for candidate sets C, C' that agree on the survivors (the caller carries its bitmap columns through the vertex map;
+ * DeltaV = gnnpe_refine_sets_delta_vertices, VV / EV its count tables with the caller's table as dev_accum and sign = -1 / +1):
+ *   removal:  lost = DeltaV(G, C, R);  VV -= VV(G, C, R);  EV -= EV(G, C, R);  gnnpe_csr_apply_vertices(R);
+ *             VV = carry_vertices(VV);  EV = carry_entries(EV);  |M'| = |M| - lost.
+ *             By the time of the carry the columns of R and the entries at R hold zero, so dropping them loses nothing.
+ *   growth:   gnnpe_csr_apply_vertices(A);  VV = carry_vertices(VV);  EV = carry_entries(EV);  gnnpe_csr_apply_edges_map(I);
+ *             EV = carry_entries(EV);  gained = Delta(G', C', I) (gnnpe_refine_sets_delta), its tables added.  An added vertex
+ *             without edges matches a single-vertex query only: DeltaV(G', C', A) counts those.
+ * Slab contexts and multigraph rows are out of scope. */
+#define GNNPE_NO_VERTEX 0xFFFFFFFFu
+
+int gnnpe_host_csr_apply_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                                  const uint32_t *remove, uint64_t n_remove, const uint32_t *add_labels, uint64_t n_add,
+                                  uint32_t *out_offsets, uint32_t *out_nbrs, uint64_t out_cap, uint32_t *out_labels,
+                                  uint32_t *vertex_map, uint32_t *n_after, uint64_t *n_entries_after);
+int gnnpe_csr_apply_vertices(gnnpe_ctx *ctx, const uint32_t *remove, uint64_t n_remove,
+                             const uint32_t *add_labels, uint64_t n_add,
+                             uint32_t *n_after, uint64_t *n_entries_before, uint64_t *n_entries_after,
+                             void **dev_vertex_map, void **dev_entry_map, double *device_ms);
+int gnnpe_csr_carry_vertices(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes,
+                             const void *dev_src, void *dev_dst, double *device_ms);
 
 /* ---- halo exchange helpers (device side of the RCCL all-to-all-v) ----------------- */
 /* List the vertices whose adjacency rows this context needs but does not hold -- every vertex referenced by

@@ -553,8 +553,8 @@ int gnnpe_refine_sets_delta_nonedges_edge_counts(gnnpe_ctx *ctx, const char *que
  *   lowest-numbered query vertex with an image in S only.  Its cost follows DeltaV and nq, not |M|.
  *   matches, matches_cap, the row layout, limit, *device_ms and the ownership of the buffers are exactly those of
  *   gnnpe_refine_sets_delta.  The rows come page by page through gnnpe_refine_pages_open_delta_vertices (the last section); the
- *   count tables of Sset are the next section; adding or removing vertices
- *   (n changes), slab contexts and multigraph rows are out of scope. */
+ *   count tables of Sset are the next section; adding or removing vertices is gnnpe_csr_apply_vertices of include/gnnpe_hip.h
+ *   (the removal loop: lost = DeltaV(G, C, R), apply, |M'| = |M| - lost); slab contexts and multigraph rows are out of scope. */
 int gnnpe_host_refine_sets_delta_vertices(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
                                           const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *vertices,
                                           uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers);
