@@ -116,6 +116,11 @@ SIGNATURES = {
                                               C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_f64p)]),
     "gnnpe_filter_candidates_exact": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double,
                                                 _u32p, _f64p]),
+    "gnnpe_filter_support_exact": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double, _vp,
+                                             _f64p]),
+    "gnnpe_filter_support_exact_delta": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double,
+                                                   _u32p, C.c_uint64, C.c_int, _vp, _f64p]),
+    "gnnpe_filter_support_bitmap": (C.c_int, [_vp, C.c_uint32, _vp, _u32p, _f64p]),
     "gnnpe_build_index_device": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.POINTER(_vp), _u64p,
                                            C.POINTER(C.c_int32)]),
     "gnnpe_build_index": (C.c_int, [_vp, C.c_uint32, C.c_char_p]),
@@ -458,6 +463,13 @@ def _delta_pairs(edges):
     if e.size and (e.min() < 0 or e.max() > 0xFFFFFFFF):
         raise GnnpeError("delta edges: vertex ids are uint32")
     return np.ascontiguousarray(e, np.uint32)
+
+
+def _table_ptr(table):
+    """device address of a caller's table: a torch tensor or anything with data_ptr(), or the address itself"""
+    if table is None:
+        return None
+    return C.c_void_p(int(table.data_ptr()) if hasattr(table, "data_ptr") else int(table))
 
 
 def _vertex_ids(vertices):
@@ -931,6 +943,7 @@ class Engine:
         self.ctx = self.lib.gnnpe_create(int(device))
         if not self.ctx:
             raise GnnpeError("gnnpe_create: " + self.lib.gnnpe_last_error().decode())
+        self.device_index = int(device)
         self.n = 0
         self.e = 0
         self.entries = 0  # adjacency entries of the CSR given to load_csr: the width of the edge-count tables
@@ -1133,16 +1146,58 @@ class Engine:
     def filter_candidates_exact(self, plan, eps=1e-6):
         """Exact-mode filter.  plan: dict from host_query_plan_exact (each path once: the library adds the reverses).
         Returns (bitmap [n_query_vertices x ceil(n/32)] uint32, device ms)."""
-        nv, l = int(plan["n_vertices"]), int(plan["l"])
+        l, counts, v, lb, d, pde, nv = self._exact_plan_args(plan)
+        bm = np.zeros((nv, (self.n + 31) // 32), np.uint32)
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_filter_candidates_exact(self.ctx, l, counts, _ptr(v, _u32p), _ptr(lb, _u32p), _ptr(d, _u32p),
+                                                        _ptr(pde, _f64p), nv, float(eps), _ptr(bm, _u32p), C.byref(ms)))
+        return bm, ms.value
+
+    @staticmethod
+    def _exact_plan_args(plan):
+        """the flat arrays of a plan dict from host_query_plan_exact, as the exact filter and the support calls take them"""
         parts = [plan[k] for k in ("main", "tri", "single")]
         counts = (C.c_uint32 * 3)(*[len(p["vids"]) for p in parts])
         v, lb, d = (np.ascontiguousarray(np.concatenate([np.asarray(p[k], np.uint32).ravel() for p in parts]))
                     for k in ("vids", "labels", "degrees"))
         pde = np.ascontiguousarray(np.concatenate([np.asarray(p["pde"], np.float64).ravel() for p in parts]))
-        bm = np.zeros((nv, (self.n + 31) // 32), np.uint32)
+        return int(plan["l"]), counts, v, lb, d, pde, int(plan["n_vertices"])
+
+    def filter_support_exact(self, plan, eps=1e-6, table=None):
+        """gnnpe_filter_support_exact: the support table S of the exact filter on the graph the context holds, (table, device ms).
+        table[u, v] = the directed data paths (and single-vertex tests) that support bit v of row u of filter_candidates_exact,
+        (n_query_vertices, n) uint64 held as int64 words on the device.  table: a torch device tensor, an object with data_ptr() or
+        a device address to overwrite (it is returned as given); None allocates a torch tensor on the context's device.  Needs
+        load_csr, the label table and vde() since the last change of the graph; no order."""
+        l, counts, v, lb, d, pde, nv = self._exact_plan_args(plan)
+        if table is None:
+            import torch
+            table = torch.zeros((nv, self.n), dtype=torch.int64, device=f"cuda:{self.device_index}")
+            torch.cuda.synchronize(table.device)  # the library writes on the context's stream
         ms = C.c_double()
-        self._ck(self.lib.gnnpe_filter_candidates_exact(self.ctx, l, counts, _ptr(v, _u32p), _ptr(lb, _u32p), _ptr(d, _u32p),
-                                                        _ptr(pde, _f64p), nv, float(eps), _ptr(bm, _u32p), C.byref(ms)))
+        self._ck(self.lib.gnnpe_filter_support_exact(self.ctx, l, counts, _ptr(v, _u32p), _ptr(lb, _u32p), _ptr(d, _u32p),
+                                                     _ptr(pde, _f64p), nv, float(eps), _table_ptr(table), C.byref(ms)))
+        return table, ms.value
+
+    def filter_support_delta(self, plan, vertices, sign, table, eps=1e-6):
+        """gnnpe_filter_support_exact_delta: table += sign * S_T with T = `vertices` (ids of the graph the context holds now, repeats
+        tolerated; sign +1 or -1, mod 2^64): the support of the paths through T, each once.  An empty T launches nothing.  Around an
+        update: subtract on the graph of before, update, vde(), add on the graph of after -- with T the ends of an edge batch,
+        R and its neighbours for a relabel or a removal (include/gnnpe_hip.h).  Returns the device ms."""
+        l, counts, v, lb, d, pde, nv = self._exact_plan_args(plan)
+        t = _vertex_ids(vertices)
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_filter_support_exact_delta(self.ctx, l, counts, _ptr(v, _u32p), _ptr(lb, _u32p), _ptr(d, _u32p),
+                                                           _ptr(pde, _f64p), nv, float(eps), _ptr(t, _u32p) if len(t) else None,
+                                                           len(t), int(sign), _table_ptr(table), C.byref(ms)))
+        return ms.value
+
+    def support_bitmap(self, table, n_query_vertices):
+        """gnnpe_filter_support_bitmap: (bitmap, device ms), bit v of row u set where table[u, v] != 0 -- the candidate sets of
+        filter_candidates_exact on the graph the table is current for, in the layout every refinement call takes."""
+        bm = np.zeros((int(n_query_vertices), (self.n + 31) // 32), np.uint32)
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_filter_support_bitmap(self.ctx, int(n_query_vertices), _table_ptr(table), _ptr(bm, _u32p), C.byref(ms)))
         return bm, ms.value
 
     def refine(self, query_path, bitmap, limit=0xFFFFFFFF):

@@ -81,6 +81,9 @@ struct Options {
     // --apply-vertices FILE (exact -m online / -m filter only): lines `- v` / `+ label`, a batch of vertex removals and additions
     // applied to the loaded data graph on the device before --apply-edges and --set-labels (gnnpe_csr_apply_vertices)
     std::string apply_vertices_file;
+    // --incremental (with --apply-vertices / --apply-edges / --set-labels): the exact candidate sets come from the filter's support table
+    // carried across the batches (gnnpe_filter_support_exact, _delta, _bitmap) and not from a filter pass over the updated graph
+    bool incremental = false;
     bool induced = false;   // --induced (needs --refine sets): induced matching, query non-edges on data non-edges (GNNPE_MATCH_INDUCED)
     bool strict = false;  // refuse a graph file with a duplicate `e` line (the reference loads it as it is: graph.cpp:211-218)
     bool same_device = false;  // testing aid: all --gpus contexts on device 0 (halo by device copies: RCCL needs distinct GPUs)
@@ -161,7 +164,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "           [--refine start|sets [--distinct] [--induced]] [--matches FILE [--all-matches [--match-page ROWS]]]\n"
                    "           [--vertex-counts FILE | --edge-counts FILE | (--delta-edges FILE | --delta-nonedges FILE | --delta-vertices FILE)\n"
                    "           [--delta-vertex-counts FILE | --delta-edge-counts FILE | --delta-pages ROWS]] [--apply-edges FILE]\n"
-                   "           [--set-labels FILE] [--apply-vertices FILE]\n"
+                   "           [--set-labels FILE] [--apply-vertices FILE] [--incremental]\n"
                    "       --matches FILE writes at most 2^20 embeddings (needs --refine sets); with --all-matches every embedding up to -n,\n"
                    "       in pages of ROWS embeddings (default 1048576); --distinct counts and writes every matching subgraph once;\n"
                    "       --induced counts and writes induced matches only: non-adjacent query vertices on non-adjacent data vertices;\n"
@@ -198,7 +201,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's\n"
                    "       --apply-vertices FILE (exact mode only: --exact or -l 3): FILE has one line `- v` (remove vertex v with its edges;\n"
                    "       the survivors keep their order under new ids) or `+ label` (append a vertex with that label and no edges) per\n"
-                   "       change; applied on the device first, so that --apply-edges, --set-labels and --delta-vertices name the new ids\n",
+                   "       change; applied on the device first, so that --apply-edges, --set-labels and --delta-vertices name the new ids\n"
+                   "       --incremental (with --apply-edges, --set-labels or --apply-vertices): the candidate sets come from the exact\n"
+                   "       filter's support table, built on the graph as loaded and patched around every batch, not from a filter pass over\n"
+                   "       the updated graph; same sets, same answer\n",
                    tool, tool);
             exit(0);
         }
@@ -261,6 +267,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "--same-device") { o.same_device = true; continue; }
         if (a == "--strict") { o.strict = true; continue; }
         if (a == "--exact") { o.exact = true; continue; }
+        if (a == "--incremental") { o.incremental = true; continue; }
         if (a.rfind("--", 0) == 0) {
             std::string name = a.substr(2);
             size_t eq = name.find('=');

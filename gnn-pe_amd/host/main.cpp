@@ -515,16 +515,76 @@ int run_filter(const Options &o)
         g.max_label_frequency = 0;
         for (const auto &kv : freq) g.max_label_frequency = std::max(g.max_label_frequency, kv.second);
     };
+    // --incremental: the support table S of the exact filter on the graph as loaded, then around every batch S -= S_T(G), the batch,
+    // gnnpe_vde, S += S_T'(G') (the loops of include/gnnpe_hip.h); the bitmap below is derived from S.  The label table is set
+    // once, with a row for every label a batch can bring: a row depends on its label alone, so the embeddings are those of the
+    // table the plain run sets after the batches
+    void *support = nullptr;
+    double support_ms = 0.0;
+    auto support_delta = [&](const std::vector<uint32_t> &T, int sign) {
+        double ms1 = 0.0;
+        check(gnnpe_filter_support_exact_delta(ctx, o.path_length, counts, qv, ql, qd, qp, n_qv, 1e-6, T.data(), T.size(), sign, support, &ms1),
+              "filter_support_exact_delta");
+        support_ms += ms1;
+    };
+    auto with_neighbours = [&](const std::vector<uint32_t> &R) {  // R u N(R) in the host copy of the graph
+        std::vector<uint32_t> T(R);
+        for (uint32_t v : R)
+            if (v < g.n) T.insert(T.end(), g.neighbors.begin() + g.offsets[v], g.neighbors.begin() + g.offsets[v + 1]);
+        return T;
+    };
+    if (o.incremental) {
+        uint32_t n_labels = std::max<uint32_t>(g.labels_count, 1);
+        if (!o.apply_vertices_file.empty()) {
+            std::vector<uint32_t> rem, add;
+            read_vertex_batch(o.apply_vertices_file, &rem, &add);
+            for (uint32_t lab : add) n_labels = std::max(n_labels, lab + 1);
+        }
+        if (!o.set_labels_file.empty()) {
+            std::vector<uint32_t> vs, ls;
+            read_label_list(o.set_labels_file, &vs, &ls);
+            for (uint32_t lab : ls) n_labels = std::max(n_labels, lab + 1);
+        }
+        std::vector<double> table((size_t)n_labels * o.vde_dim);
+        check(gnnpe_host_label_table(n_labels, o.vde_dim, table.data()), "label table");
+        check(gnnpe_set_label_table(ctx, n_labels, o.vde_dim, table.data()), "set_label_table");
+        check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
+        check(gnnpe_dev_alloc(ctx, (uint64_t)n_qv * g.n * 8, &support), "support table");
+        check(gnnpe_filter_support_exact(ctx, o.path_length, counts, qv, ql, qd, qp, n_qv, 1e-6, support, nullptr), "filter_support_exact");
+    }
     if (!o.apply_vertices_file.empty()) {  // first: an edge file may name the new ids
         std::vector<uint32_t> rem, add;
         read_vertex_batch(o.apply_vertices_file, &rem, &add);
         uint32_t n2 = 0;
         uint64_t entries = 0;
         void *dev_vmap = nullptr;
+        std::vector<uint32_t> touched;  // R u N_G(R), ids of G
+        if (o.incremental) {
+            for (uint32_t v : rem)
+                if (v >= g.n) die("--apply-vertices: vertex " + std::to_string(v) + " is not a vertex of the graph");
+            touched = with_neighbours(rem);
+            support_delta(touched, -1);
+        }
         check(gnnpe_csr_apply_vertices(ctx, rem.data(), rem.size(), add.data(), add.size(), &n2, nullptr, &entries, &dev_vmap, nullptr, nullptr),
               "--apply-vertices");
         std::vector<uint32_t> vmap(n2);
         check(gnnpe_copy_to_host(ctx, vmap.data(), dev_vmap, (uint64_t)n2 * 4), "vertex map");
+        if (o.incremental) {  // the table through the vertex map (the columns of R hold zero by now), then the paths of G' through T'
+            void *carried = nullptr;
+            check(gnnpe_dev_alloc(ctx, (uint64_t)n_qv * n2 * 8, &carried), "support table");
+            check(gnnpe_csr_carry_vertices(ctx, n_qv, 8, support, carried, nullptr), "carry_vertices");
+            check(gnnpe_dev_free(ctx, support), "support table");
+            support = carried;
+            check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
+            std::vector<uint32_t> new_of(g.n, GNNPE_NO_VERTEX), after;
+            for (uint32_t v = 0; v < n2; v++) {
+                if (vmap[v] != GNNPE_NO_VERTEX) new_of[vmap[v]] = v;
+                else after.push_back(v);
+            }
+            for (uint32_t v : touched)
+                if (new_of[v] != GNNPE_NO_VERTEX) after.push_back(new_of[v]);
+            support_delta(after, +1);
+        }
         // order and membership through the vertex map: the survivors in their old order, the added vertices behind them in partition 0
         // (exact mode's candidate sets do not depend on the order)
         std::vector<uint32_t> new_id(g.n, GNNPE_NO_VERTEX), order, member(n2, 0);
@@ -558,13 +618,35 @@ int run_filter(const Options &o)
         }
         fclose(af);
         uint64_t entries = 0;
+        std::vector<uint32_t> ends(ins);  // T: the end vertices of the batch
+        ends.insert(ends.end(), del.begin(), del.end());
+        if (o.incremental) {
+            for (uint32_t v : ends)
+                if (v >= g.n) die("--apply-edges: vertex " + std::to_string(v) + " is not a vertex of the graph");
+            support_delta(ends, -1);
+        }
         check(gnnpe_csr_apply_edges(ctx, ins.data(), ins.size() / 2, del.data(), del.size() / 2, &entries, nullptr), "--apply-edges");
+        if (o.incremental) {
+            check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
+            support_delta(ends, +1);
+        }
         follow_rows(entries);
     }
     if (!o.set_labels_file.empty()) {  // ... and on the relabelled one
         std::vector<uint32_t> vs, ls;
         read_label_list(o.set_labels_file, &vs, &ls);
+        std::vector<uint32_t> touched;  // T = R u N(R): the embedding of a neighbour changes too
+        if (o.incremental) {
+            for (uint32_t v : vs)
+                if (v >= g.n) die("--set-labels: vertex " + std::to_string(v) + " is not a vertex of the graph");
+            touched = with_neighbours(vs);
+            support_delta(touched, -1);
+        }
         check(gnnpe_set_vertex_labels(ctx, vs.data(), ls.data(), vs.size(), nullptr), "--set-labels");
+        if (o.incremental) {
+            check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
+            support_delta(touched, +1);
+        }
         follow_labels();
     }
     if (updating) {
@@ -582,7 +664,11 @@ int run_filter(const Options &o)
     const uint64_t words = ((uint64_t)g.n + 31) / 32;
     std::vector<uint32_t> bitmap((size_t)n_qv * words);
     double ms = 0.0;
-    if (exact)
+    if (o.incremental) {  // the sets of the updated graph from the table carried to it; ms: the delta calls and this one
+        check(gnnpe_filter_support_bitmap(ctx, n_qv, support, bitmap.data(), &ms), "filter_support_bitmap");
+        ms += support_ms;
+        check(gnnpe_dev_free(ctx, support), "support table");
+    } else if (exact)
         check(gnnpe_filter_candidates_exact(ctx, o.path_length, counts, qv, ql, qd, qp, n_qv, 1e-6, bitmap.data(), &ms), "filter");
     else
         check(gnnpe_filter_candidates(ctx, n_qp, qv, ql, qd, qp, n_qv, 1e-6 /* custom.h:43 */, bitmap.data(), &ms), "filter");
@@ -744,6 +830,9 @@ int main(int argc, char **argv)
     if (!o.apply_vertices_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
         die("--apply-vertices applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
             "made from the graph as it was");
+    if (o.incremental && o.apply_vertices_file.empty() && o.apply_edges_file.empty() && o.set_labels_file.empty())
+        die("--incremental applies with --apply-vertices, --apply-edges or --set-labels: it carries the exact filter's support table "
+            "across their batches");
     if (!o.apply_vertices_file.empty()) {  // a malformed file is refused before a GPU is touched
         std::vector<uint32_t> rem, add;
         read_vertex_batch(o.apply_vertices_file, &rem, &add);

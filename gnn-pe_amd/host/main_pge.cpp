@@ -175,6 +175,7 @@ int main(int argc, char **argv)
     if (!o.apply_edges_file.empty()) die("--apply-edges is an option of gnnpe_main's exact -m online / -m filter");
     if (!o.set_labels_file.empty()) die("--set-labels is an option of gnnpe_main's exact -m online / -m filter");
     if (!o.apply_vertices_file.empty()) die("--apply-vertices is an option of gnnpe_main's exact -m online / -m filter");
+    if (o.incremental) die("--incremental is an option of gnnpe_main's exact -m online / -m filter");
     if (!o.delta_vertices_file.empty()) die("--delta-vertices is an option of gnnpe_main's --refine sets");
     if (o.delta_pages_given) die("--delta-pages is an option of gnnpe_main's --refine sets");
     if (o.mode == "online" || o.mode == "filter") return run_online(o);

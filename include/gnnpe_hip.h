@@ -614,6 +614,66 @@ int gnnpe_filter_candidates_exact(gnnpe_ctx *ctx, uint32_t l, const uint32_t cou
                                   const uint32_t *q_labels, const uint32_t *q_degrees, const double *q_pde,
                                   uint32_t n_query_vertices, double epsilon, uint32_t *host_bitmap, double *device_ms);
 
+/* ---- filter support tables: exact candidate sets kept current across updates ------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section only adds symbols.)
+ * The exact candidate set is a union over passing data paths and cannot be patched bit by bit: a deletion may remove the last path
+ * that supported a bit.  The number of supporting paths can be patched, and the paths whose status an update changes lie within l
+ * hops of the batch.  These calls keep that number -- the support table S of the exact filter -- and derive the bitmap from it, so
+ * that a standing exact query pays neither gnnpe_set_order nor a whole-graph gnnpe_filter_candidates_exact per batch.
+ *
+ * Definitions.  The plan is what gnnpe_host_query_plan_exact returns: parts main (width W = l + 1), tri (width 3, l = 3 only) and
+ * single, each path listed once.  S[u][v] is a uint64 cell of a table of n_query_vertices rows by n columns, row-major, in the
+ * CALLER's device memory; it is the sum of
+ *   - over the plan paths q of main and tri and the positions j with q.vids[j] == u: the number of DIRECTED simple data paths P of
+ *     q's width that pass q position by position with P[j] == v.  "Pass" is the leaf test of gnnpe_filter_candidates: labels equal,
+ *     query degree <= data degree, in no dimension q > d && |q - d| > epsilon;
+ *   - over the single entries with vid u: 1 if v passes the same three tests alone.
+ * Counting directed paths against the plan as listed equals counting every undirected path in one orientation against the plan
+ * doubled with its reverses, which is what the filter kernels do: S[u][v] != 0 exactly where gnnpe_filter_candidates_exact sets bit
+ * v of row u.  The table depends on no processing order: none of these calls needs gnnpe_set_order, and none uses a slab.
+ * S_T, for a vertex set T, is the same sum over the paths that contain at least one vertex of T, each counted once, and over the
+ * singles with v in T.  S_V = S.  (Each once: a path is charged to the smallest position j with P[j] in T; a work item (t, j) walks
+ * the paths with P[j] = t, any vertex to the right of j, only vertices outside T to the left -- csrc/gnnpe_filter_support.hip.)
+ *
+ * gnnpe_filter_support_exact: dev_table = S(G), overwritten.
+ * gnnpe_filter_support_exact_delta: dev_table += sign * S_T(G) with T = vertices (n_vertices ids < n; a repeated id means the vertex
+ *   once).  sign is +1 or -1; the subtraction is the wrapping 64-bit add, as in the count tables of ABI 17.  n_vertices == 0 succeeds,
+ *   launches nothing and leaves the table's bytes alone.
+ * gnnpe_filter_support_bitmap: host_bitmap (n_query_vertices x ceil(n/32) uint32, the layout gnnpe_filter_candidates and every
+ *   refinement call take) with bit v of row u set where S[u][v] != 0.
+ * *device_ms (may be NULL): the time on the device, the plan's upload excluded.  Each call waits for the device once; nothing per
+ * path leaves the device.
+ *
+ * Requirements: the whole graph on the device (gnnpe_load_csr state), a label table, and gnnpe_vde since the last change of the rows
+ * or the labels.  Refusals, all on the host before any launch, each leaving the context and the table untouched:
+ *   - the plan checks of gnnpe_filter_candidates_exact, the limit of 512 paths per width after doubling included
+ *     (GNNPE_ERR_UNSUPPORTED);
+ *   - GNNPE_ERR_ARG: a null or not 8-byte aligned dev_table, a sign other than +1 / -1, an id >= n, a null list with a count > 0;
+ *   - GNNPE_ERR_UNSUPPORTED: a slab-only context (gnnpe_load_rows) or the multigraph state;
+ *   - GNNPE_ERR_ARG naming gnnpe_vde where the embeddings are missing or stale: what catches a caller who forgot it after an update.
+ *
+ * The loops.  A, R and N as above; every update call resets gnnpe_vde, which the next support call asks for.
+ *   Edges, batch B = I u D, T = the end vertices of B:
+ *       S -= S_T(G);  gnnpe_csr_apply_edges(B);  gnnpe_vde;  S += S_T(G');  C' = bitmap(S)
+ *     Degree and vde change only at the ends of B, and a path with a changed edge contains both of its ends: every path whose
+ *     existence or test result changes contains a vertex of T.
+ *   Relabel of R: the same with gnnpe_set_vertex_labels and T = R u N(R) -- the vde of a neighbour changes too.
+ *   Vertex batch removing R and adding A:
+ *       S -= S_T(G), T = R u N_G(R);  gnnpe_csr_apply_vertices;  gnnpe_csr_carry_vertices(n_rows = n_query_vertices, elem_bytes = 8);
+ *       gnnpe_vde;  S += S_T'(G'), T' = the new ids of N_G(R) \ R together with the added vertices
+ *     After the subtraction the columns of R hold zero, so dropping them in the carry loses nothing; an added vertex has an empty
+ *     row and can still pass a single-vertex test.
+ * Not here: slab contexts, multigraph rows, the reference-mode filter, a plan handle that would save the upload per call. */
+int gnnpe_filter_support_exact(gnnpe_ctx *ctx, uint32_t l, const uint32_t counts[3], const uint32_t *q_vids,
+                               const uint32_t *q_labels, const uint32_t *q_degrees, const double *q_pde,
+                               uint32_t n_query_vertices, double epsilon, void *dev_table, double *device_ms);
+int gnnpe_filter_support_exact_delta(gnnpe_ctx *ctx, uint32_t l, const uint32_t counts[3], const uint32_t *q_vids,
+                                     const uint32_t *q_labels, const uint32_t *q_degrees, const double *q_pde,
+                                     uint32_t n_query_vertices, double epsilon, const uint32_t *vertices, uint64_t n_vertices,
+                                     int sign, void *dev_table, double *device_ms);
+int gnnpe_filter_support_bitmap(gnnpe_ctx *ctx, uint32_t n_query_vertices, const void *dev_table, uint32_t *host_bitmap,
+                                double *device_ms);
+
 /* The refinement half of the reference's online step (custom.h:634-932) is outside SURVEY section 8's scope (frozen since round 1)
  * and ships in a library of its own since round 6: include/gnnpe_online.h, libgnnpe_online.so (gnnpe_refine, gnnpe_host_refine). */
 
