@@ -121,6 +121,7 @@ SIGNATURES = {
     "gnnpe_filter_support_exact_delta": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double,
                                                    _u32p, C.c_uint64, C.c_int, _vp, _f64p]),
     "gnnpe_filter_support_bitmap": (C.c_int, [_vp, C.c_uint32, _vp, _u32p, _f64p]),
+    "gnnpe_filter_support_bitmap_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _f64p]),
     "gnnpe_build_index_device": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.POINTER(_vp), _u64p,
                                            C.POINTER(C.c_int32)]),
     "gnnpe_build_index": (C.c_int, [_vp, C.c_uint32, C.c_char_p]),
@@ -156,6 +157,19 @@ class GnnpeError(RuntimeError):
 ONLINE_LIB_PATH = os.path.join(_HERE, "libgnnpe_online.so")
 ONLINE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gnnpe_online.h")
 ONLINE_SIGNATURES = {
+    # the standing exact query
+    "gnnpe_standing_open": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.c_double, C.c_uint32, C.c_uint64, C.POINTER(_vp), _u64p, _f64p]),
+    "gnnpe_standing_open_sets": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.c_uint64, _u32p, C.POINTER(_vp), _u64p, _f64p]),
+    "gnnpe_standing_set_bitmap": (C.c_int, [_vp, _u32p]),
+    "gnnpe_standing_apply_edges": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_standing_result": (C.c_int, [_vp, _u64p]),
+    "gnnpe_standing_rows": (C.c_int, [_vp, C.c_int, _u32p, C.c_uint64, _u64p]),
+    "gnnpe_standing_set_sizes": (C.c_int, [_vp, _u64p]),
+    "gnnpe_standing_set_members": (C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint64, _u64p]),
+    "gnnpe_standing_bitmap": (C.c_int, [_vp, _u32p]),
+    "gnnpe_standing_table": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "gnnpe_standing_refresh": (C.c_int, [_vp, _u64p, _f64p]),
+    "gnnpe_standing_close": (C.c_int, [_vp]),
     "gnnpe_host_refine": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
     "gnnpe_refine": (C.c_int, [_vp, C.c_char_p, _u32p, C.c_uint64, _u64p, _f64p]),
     "gnnpe_host_refine_sets": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
@@ -935,6 +949,113 @@ class MatchCursor:
             pass
 
 
+class StandingQuery:
+    """A standing exact query (gnnpe_standing_* of include/gnnpe_online.h): the parsed query, the support table S of the exact
+    filter, the candidate bitmap C and the exact match count stay on the device, and Engine.standing_apply_edges moves the graph
+    and every open handle forward by an edge batch.  Made by Engine.standing_open.  count / created / destroyed: the count on the
+    current graph and what the last batch created and destroyed.  Every call but refresh() and close() raises GnnpeError once the
+    graph, the labels or the label table changed behind the handle."""
+
+    def __init__(self, eng, query_path, l, eps, mode, rows_cap, bitmap):
+        self.eng, self.handle = eng, _vp()
+        self.online = load_online()
+        count, ms = C.c_uint64(), C.c_double()
+        if bitmap is None:
+            rc = self.online.gnnpe_standing_open(eng.ctx, query_path.encode(), int(l), float(eps), mode, int(rows_cap),
+                                                 C.byref(self.handle), C.byref(count), C.byref(ms))
+        else:
+            bm = _np(bitmap, np.uint32)
+            rc = self.online.gnnpe_standing_open_sets(eng.ctx, query_path.encode(), mode, int(rows_cap), _ptr(bm, _u32p),
+                                                      C.byref(self.handle), C.byref(count), C.byref(ms))
+        eng._ck(rc)
+        self.open_ms = ms.value
+        self.nq = len(self.set_sizes())
+        eng._standing.append(self)
+
+    def result(self):
+        """(count, created, destroyed, rows_created, rows_destroyed, graph generation)"""
+        out = (C.c_uint64 * 6)()
+        self.eng._ck(self.online.gnnpe_standing_result(self.handle, out))
+        return tuple(int(x) for x in out)
+
+    count = property(lambda self: self.result()[0])
+    created = property(lambda self: self.result()[1])
+    destroyed = property(lambda self: self.result()[2])
+
+    def rows(self, which, cap=None):
+        """the kept rows of the last batch: which = 0 (or "created") / 1 (or "destroyed"); (rows, nq) uint32, column = query vertex"""
+        which = {"created": 0, "destroyed": 1}.get(which, which)
+        held = self.result()[3 + int(which)] if cap is None else int(cap)
+        out, n = np.zeros((max(held, 1), self.nq), np.uint32), C.c_uint64()
+        self.eng._ck(self.online.gnnpe_standing_rows(self.handle, int(which), _ptr(out, _u32p), held, C.byref(n)))
+        return out[:min(held, n.value)]
+
+    def set_sizes(self):
+        """|C(u)| of every query vertex, from k_sets_sizes"""
+        out = (C.c_uint64 * 32)(*([2 ** 64 - 1] * 32))  # the library writes one value per query vertex, each below 2^32
+        self.eng._ck(self.online.gnnpe_standing_set_sizes(self.handle, out))
+        return np.array([x for x in out if x != 2 ** 64 - 1], np.uint64)
+
+    def set_members(self, u, cap=None, out=None):
+        """the ascending ids of C(u), from k_sets_members: (ids, size); with cap the first cap ids and the true size.  `out`: a
+        uint32 array to write the ids into (its words beyond cap are left alone)."""
+        cap = self.eng.n if cap is None else int(cap)
+        buf = np.zeros(max(cap, 1), np.uint32) if out is None else out
+        n = C.c_uint64()
+        self.eng._ck(self.online.gnnpe_standing_set_members(self.handle, int(u), _ptr(buf, _u32p), cap, C.byref(n)))
+        return buf[:min(cap, n.value)], int(n.value)
+
+    def bitmap(self):
+        """C as the host bitmap every refinement call takes: (nq, ceil(n / 32)) uint32"""
+        bm = np.zeros((self.nq, (self.eng.n + 31) // 32), np.uint32)
+        self.eng._ck(self.online.gnnpe_standing_bitmap(self.handle, _ptr(bm, _u32p)))
+        return bm
+
+    def set_bitmap(self, bitmap):
+        """a new bitmap for a handle opened with one; the count is taken again"""
+        bm = _np(bitmap, np.uint32)
+        self.eng._ck(self.online.gnnpe_standing_set_bitmap(self.handle, _ptr(bm, _u32p)))
+
+    def table_ptr(self):
+        """device address of S (nq x n uint64), 0 for a handle opened with a bitmap"""
+        p = _vp()
+        self.eng._ck(self.online.gnnpe_standing_table(self.handle, C.byref(p)))
+        return p.value or 0
+
+    def table(self):
+        """S on the host, (nq, n) uint64; None for a handle opened with a bitmap"""
+        p = self.table_ptr()
+        if not p:
+            return None
+        return self.eng.copy_to_host(p, self.nq * self.eng.n * 8).view(np.uint64).reshape(self.nq, self.eng.n)
+
+    def refresh(self, timing=False):
+        """S, C and the count again from the graph as it is now: the state of a fresh open"""
+        count, ms = C.c_uint64(), C.c_double()
+        self.eng._ck(self.online.gnnpe_standing_refresh(self.handle, C.byref(count), C.byref(ms) if timing else None))
+        return (count.value, ms.value) if timing else count.value
+
+    def close(self):
+        if self.handle:
+            if self.eng.ctx:
+                self.online.gnnpe_standing_close(self.handle)
+            self.handle = _vp()
+            if self in self.eng._standing:
+                self.eng._standing.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One context = one GPU.  Method names follow the reference functions they replace."""
 
@@ -956,6 +1077,7 @@ class Engine:
         self.total = None
         self._pools = []
         self._cursors = []  # open match cursors: closed before the context goes
+        self._standing = []  # open standing queries: closed before the context goes
         self.stream_handle = None  # None = the context's own stream
         if stream is not None:
             self.set_stream(stream)
@@ -964,6 +1086,8 @@ class Engine:
         if self.ctx:
             for cur in list(getattr(self, "_cursors", [])):
                 cur.close()
+            for sq in list(getattr(self, "_standing", [])):
+                sq.close()
             for p in list(getattr(self, "_pools", [])):
                 p.close(force=True)
             self.lib.gnnpe_destroy(self.ctx)
@@ -1543,6 +1667,27 @@ class Engine:
             self.slab = (0, self.n)
         self.entries = after.value
         return (after.value, ms.value) if timing else after.value
+
+    def standing_open(self, query_path, l=2, eps=1e-6, distinct=False, induced=False, rows_cap=0, bitmap=None):
+        """gnnpe_standing_open: a StandingQuery on this context (at most 16).  bitmap=None: the exact filter at path length l keeps
+        the candidate sets (needs the label table and vde()); a bitmap: gnnpe_standing_open_sets, the caller's sets, which must be
+        sound for every graph the handle will see.  rows_cap: how many created and destroyed rows a batch keeps."""
+        return StandingQuery(self, query_path, l, eps, match_mode(distinct, induced), rows_cap, bitmap)
+
+    def standing_apply_edges(self, insert=None, delete=None, timing=False):
+        """gnnpe_standing_apply_edges: apply_edges that carries every open StandingQuery through the batch (and runs vde()).  A
+        refused batch raises GnnpeError and changes nothing, neither the graph nor a handle.  Returns the device ms with timing."""
+        ins, dele = _delta_pairs([] if insert is None else insert), _delta_pairs([] if delete is None else delete)
+        ms = C.c_double()
+        self._map_call += 1
+        self._ck(load_online().gnnpe_standing_apply_edges(self.ctx, _ptr(ins, _u32p) if len(ins) else None, len(ins),
+                                                          _ptr(dele, _u32p) if len(dele) else None, len(dele),
+                                                          C.byref(ms) if timing else None))
+        if len(ins) or len(dele):
+            self._rows_gen += 1
+            self.slab = (0, self.n)
+            self.entries = self.rows_held()[1]
+        return ms.value if timing else None
 
     def apply_edges_map(self, insert=None, delete=None, timing=False):
         """gnnpe_csr_apply_edges_map: apply_edges that also leaves the batch's entry map on the device.  Returns (entries_before,

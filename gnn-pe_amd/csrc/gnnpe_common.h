@@ -132,6 +132,11 @@ struct gnnpe_ctx {
     int device = 0;
     gnnpe::Switches sw;  // the environment as gnnpe_create found it
     std::vector<gnnpe_pool *> pools;  // output pools created on this context and not yet destroyed: freed with it
+    // standing exact queries open on this context (gnnpe_standing_open of include/gnnpe_online.h, at most 16): registered here as the
+    // pools are.  The handles belong to libgnnpe_online.so, which this library does not link: the first open leaves the function that
+    // closes what is still open, and gnnpe_destroy calls it.
+    std::vector<void *> standing;
+    void (*standing_close_all)(gnnpe_ctx *) = nullptr;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
 
@@ -208,6 +213,7 @@ struct gnnpe_ctx {
     // ---- label table (R3) / vertex embeddings (R4) ----
     uint32_t n_labels = 0, e = 0;
     bool have_table = false, have_vde = false;
+    uint64_t table_gen = 0;  // counts gnnpe_set_label_table: with graph_gen the state a standing query is exact for
     bool labels_checked = false;  // every label indexes the table (checked once per label / table upload)
     gnnpe::DevBuf xtab, x, nx, vde, nbr_vde;
     // the label table by rank: xrank[label * e + k] = position of xtab[label][k] among the labels' values of dimension k

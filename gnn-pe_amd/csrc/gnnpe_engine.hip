@@ -247,6 +247,7 @@ void gnnpe_destroy(gnnpe_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    if (c->standing_close_all) c->standing_close_all(c);  // standing queries the caller did not close
     for (gnnpe_pool *p : c->pools) pool_free(p);  // output pools the caller did not destroy
     c->pools.clear();
     // every DevBuf member releases itself in ~gnnpe_ctx
@@ -692,6 +693,7 @@ int gnnpe_set_label_table(gnnpe_ctx *c, uint32_t n_labels, uint32_t e, const dou
     c->n_labels = n_labels;
     c->e = e;
     c->have_table = true;
+    c->table_gen++;
     c->labels_checked = false;
     c->counted = false;  // record layouts of the enumeration depend on e
     c->have_vde = false;

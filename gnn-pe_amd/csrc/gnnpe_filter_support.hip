@@ -481,4 +481,31 @@ int gnnpe_filter_support_bitmap(gnnpe_ctx *c, uint32_t n_query_vertices, const v
     return support_result(who, timer.end(he, c->stream, device_ms, host_bitmap, c->q_bitmap.p, bm_bytes));
 }
 
+// the same kernel into the caller's device buffer, on the context's stream; waits for nothing unless the call is timed (the two
+// events of *device_ms need their wait).  k_support_bitmap writes every word of every row and leaves the bits at positions >= n of
+// a row's last word zero (its __ballot is taken under v < n).
+int gnnpe_filter_support_bitmap_device(gnnpe_ctx *c, uint32_t n_query_vertices, const void *dev_table, void *dev_bitmap, double *device_ms)
+{
+    const char *who = "gnnpe_filter_support_bitmap_device";
+    GNNPE_REQUIRE(c && n_query_vertices, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(dev_table && (reinterpret_cast<uintptr_t>(dev_table) & 7u) == 0, GNNPE_ERR_ARG,
+                  "%s: dev_table must be an 8-byte aligned device pointer", who);
+    GNNPE_REQUIRE(dev_bitmap && (reinterpret_cast<uintptr_t>(dev_bitmap) & 3u) == 0, GNNPE_ERR_ARG,
+                  "%s: dev_bitmap must be a 4-byte aligned device pointer", who);
+    int rc = support_whole_graph(who, c);
+    if (rc) return rc;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    const uint64_t words = ((uint64_t)c->n + 31) / 32;
+    if (device_ms) *device_ms = 0.0;
+    SupportTimer timer;
+    hipError_t he = timer.begin(device_ms != nullptr, c->stream);
+    if (he == hipSuccess && c->n) {
+        hipLaunchKernelGGL(k_support_bitmap, dim3(grid_for(((uint64_t)c->n + 63) / 64 * 64)), dim3(kBlock), 0, c->stream, c->n,
+                           n_query_vertices, static_cast<const unsigned long long *>(dev_table), words, static_cast<uint32_t *>(dev_bitmap));
+        he = hipGetLastError();
+    }
+    if (!device_ms) return support_result(who, he);
+    return support_result(who, timer.end(he, c->stream, device_ms));
+}
+
 }  // extern "C"

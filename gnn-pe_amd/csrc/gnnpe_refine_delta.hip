@@ -79,18 +79,20 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta(SetsPlan P, SetsDelta D
 
 using namespace gnnpe;
 
-extern "C" int gnnpe_refine_sets_delta(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+// the body of gnnpe_refine_sets_delta; `res` (a standing query, gnnpe_standing.hip): the sets are on the device already and the rows stay there
+static int refine_delta_run(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
                                        const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers,
-                                       uint32_t *matches, uint64_t matches_cap, double *device_ms)
+                                       uint32_t *matches, uint64_t matches_cap, double *device_ms, SetsResident *res = nullptr)
 {
     const char *who = "gnnpe_refine_sets_delta";
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && (delta_edges || n_delta == 0), GNNPE_ERR_ARG, "%s: null argument",
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers && (delta_edges || n_delta == 0), GNNPE_ERR_ARG, "%s: null argument",
                   who);
     *answers = 0;
     if (device_ms) *device_ms = 0.0;
+    if (res) res->rows_held = 0;
     SetsQuery Q;
     gnnpe_host::StaticGraph q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, &q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, &q, res);
     if (rc) return rc;
     // F as ascending keys and directed pairs, the plan of every launch; a loop or an id the graph does not have is refused here
     DeltaPlans D;
@@ -98,25 +100,27 @@ extern "C" int gnnpe_refine_sets_delta(gnnpe_ctx *c, const char *query_graph_pat
     if (D.nothing) return GNNPE_OK;  // limit 0, an empty set, no F, a single-vertex query: nothing is launched
     const size_t n_keys = D.keys.size();
     const uint32_t nq = Q.nq, n_items = D.n_items;
-    if (!matches) matches_cap = 0;
+    if (res) matches_cap = res->rows_cap;
+    else if (!matches) matches_cap = 0;
     matches_cap = std::min(matches_cap, limit);
 
     // context-owned, grow-only: the counters, the bitmap, F, the rows
-    if ((rc = c->q_work.reserve(SetsWork::kCtrBytes)) || (rc = c->q_bitmap.reserve((size_t)nq * Q.words * 4)) ||
-        (rc = c->q_delta.reserve(DeltaBuf::bytes(n_keys))) || (matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))))
+    if ((rc = c->q_work.reserve(SetsWork::kCtrBytes)) || (!res && (rc = c->q_bitmap.reserve((size_t)nq * Q.words * 4))) ||
+        (rc = c->q_delta.reserve(DeltaBuf::bytes(n_keys))) || (!res && matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))))
         return rc;
     SetsCounters *ctr = c->q_work.as<SetsCounters>();
     const DeltaBuf F(c->q_delta, n_keys);
-    uint32_t *d_rows = matches_cap ? c->q_matches.as<uint32_t>() : nullptr;
+    uint32_t *d_rows = !matches_cap ? nullptr : res ? res->d_rows : c->q_matches.as<uint32_t>();
+    const uint32_t *d_bitmap = res ? res->d_bitmap : c->q_bitmap.as<uint32_t>();
     SetsCall call(who, c, device_ms != nullptr);
-    const uint32_t blocks = delta_stage(call, c, Q, D, candidate_bitmap);
+    const uint32_t blocks = delta_stage(call, c, Q, D, candidate_bitmap, false, nullptr, nullptr, nullptr, res);
     if (c->sw.debug)
         fprintf(stderr, "[refine_delta] edges=%zu items=%u launches=%zu blocks=%u pairs=%u nonedges=%u\n", n_keys, n_items, D.plans.size(), blocks,
                 D.plans[0].n_pairs, D.plans[0].n_non);
     delta_launches(call, c, D, [&](size_t k, const SetsQuery &K, auto... ord) {
         hipLaunchKernelGGL((k_refine_delta<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0, c->stream, K.P,
                            D.older[k], n_items, F.pairs, F.ent, F.keys, (uint32_t)n_keys, c->adj_start.as<uint32_t>(),
-                           c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), Q.words,
+                           c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), d_bitmap, Q.words,
                            (unsigned long long)limit, ctr, d_rows, (unsigned long long)matches_cap, ord...);
     });
     call.wait(ctr, sizeof(SetsCounters));  // all of it: `bad` is in the second half
@@ -128,8 +132,24 @@ extern "C" int gnnpe_refine_sets_delta(gnnpe_ctx *c, const char *query_graph_pat
             *answers = std::min<uint64_t>(c->h_pinned[0], limit);
             // every find reserved a row, so the first min(cursor, cap) rows are written
             const uint64_t n_rows = std::min<uint64_t>(c->h_pinned[1], matches_cap);
-            if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
+            if (res) res->rows_held = n_rows;
+            else if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
         }
     }
     return call.finish(device_ms);
 }
+
+extern "C" int gnnpe_refine_sets_delta(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                       const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers,
+                                       uint32_t *matches, uint64_t matches_cap, double *device_ms)
+{
+    return refine_delta_run(c, query_graph_path, candidate_bitmap, delta_edges, n_delta, limit, mode, answers, matches, matches_cap, device_ms);
+}
+
+// the same on resident sets, for gnnpe_standing.hip (declared there)
+namespace gnnpe {
+int refine_delta_resident(gnnpe_ctx *c, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers, SetsResident *res, double *device_ms)
+{
+    return refine_delta_run(c, nullptr, nullptr, edges, n_edges, ~0ull, mode, answers, nullptr, 0, device_ms, res);
+}
+}  // namespace gnnpe

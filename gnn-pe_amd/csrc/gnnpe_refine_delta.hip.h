@@ -207,9 +207,11 @@ static inline int delta_plans(const char *who, gnnpe_ctx *c, const SetsQuery &Q,
 // The staging of a call whose buffers (q_work, q_bitmap, q_delta) are reserved, on the context's stream: F and the bitmap go up, the
 // counters are zeroed, ev0 is recorded and k_delta_entries looks the pairs up -- each must be an edge of the graph, or with
 // `nonedges` none of them may be.  Returns the blocks of a search launch: a resident grid, or as many waves as there are items.
-// (A cursor hands in its own reserved buffers in the place of the context's: `work` begins with the counter block.)
+// (A cursor hands in its own reserved buffers in the place of the context's: `work` begins with the counter block.)  With `res` the
+// bitmap is not uploaded: the search reads res->d_bitmap.
 static inline uint32_t delta_stage(SetsCall &call, gnnpe_ctx *c, const SetsQuery &Q, const DeltaPlans &D, const uint32_t *bitmap,
-                                   bool nonedges = false, const DevBuf *work = nullptr, const DevBuf *bm = nullptr, const DevBuf *fset = nullptr)
+                                   bool nonedges = false, const DevBuf *work = nullptr, const DevBuf *bm = nullptr, const DevBuf *fset = nullptr,
+                                   const SetsResident *res = nullptr)
 {
     const size_t n_keys = D.keys.size();
     SetsCounters *ctr = (work ? *work : c->q_work).as<SetsCounters>();
@@ -217,7 +219,7 @@ static inline uint32_t delta_stage(SetsCall &call, gnnpe_ctx *c, const SetsQuery
     void *d_bitmap = (bm ? *bm : c->q_bitmap).p;
     if (call.ok()) call.he = hipMemcpyAsync(F.keys, D.keys.data(), n_keys * 8, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemcpyAsync(F.pairs, D.pairs.data(), n_keys * 16, hipMemcpyHostToDevice, c->stream);
-    if (call.ok()) call.he = hipMemcpyAsync(d_bitmap, bitmap, (size_t)Q.nq * Q.words * 4, hipMemcpyHostToDevice, c->stream);
+    if (call.ok() && !res) call.he = hipMemcpyAsync(d_bitmap, bitmap, (size_t)Q.nq * Q.words * 4, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemsetAsync(ctr, 0, SetsWork::kCtrBytes, c->stream);
     if (call.ok() && call.ev0) call.he = hipEventRecord(call.ev0, c->stream);
     call.launch([&] {

@@ -94,23 +94,27 @@ using namespace gnnpe;
 
 // gnnpe_refine_sets (mode 0: R), gnnpe_refine_sets_distinct (GNNPE_MATCH_DISTINCT: D, the ordered kernel unless the query has no
 // symmetry) and gnnpe_refine_sets_mode (any mode; GNNPE_MATCH_INDUCED: I or ID, an induced kernel unless the query has no non-edge)
+// `res` (a standing query, gnnpe_standing.hip): the sets are on the device already and the rows stay there
 static int refine_sets_run(const char *who, uint32_t mode, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
-                           uint64_t limit, uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+                           uint64_t limit, uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms,
+                           SetsResident *res = nullptr)
 {
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers, GNNPE_ERR_ARG, "%s: null argument", who);
     *answers = 0;
     if (device_ms) *device_ms = 0.0;
+    if (res) res->rows_held = 0;
     SetsQuery Q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, nullptr, res);
     if (rc || Q.empty) return rc;  // limit 0 or an empty set: no answers
     const uint32_t nq = Q.nq, n_cand = Q.n_cand;
-    if (!matches) matches_cap = 0;
+    if (res) matches_cap = res->rows_cap;
+    else if (!matches) matches_cap = 0;
     matches_cap = std::min(matches_cap, limit);
 
     // context-owned, grow-only: the work buffer, the bitmap, the rows
-    if (matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))) return rc;
+    if (!res && matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))) return rc;
     SetsCall call(who, c, device_ms != nullptr);
-    if (call.ok()) call.rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, call.ev0);
+    if (call.ok()) call.rc = sets_stage_items(c, &Q, candidate_bitmap, c->q_work, c->q_bitmap, c->q_tmp, call.ev0, res);
     if (c->sw.debug) {
         char pairs[32] = "", non[32] = "";  // a distinct call appends pairs=K, an induced one nonedges=K
         if (mode & GNNPE_MATCH_DISTINCT) snprintf(pairs, sizeof pairs, " pairs=%u", Q.n_pairs);
@@ -118,13 +122,14 @@ static int refine_sets_run(const char *who, uint32_t mode, gnnpe_ctx *c, const c
         fprintf(stderr, "[refine_sets] shift=%u forced=%d cands=%u hubs=%u cus=%d%s%s\n", Q.w_shift, (int)Q.forced, n_cand, c->n_hub,
                 c->num_cus, pairs, non);
     }
-    uint32_t *d_rows = matches_cap ? c->q_matches.as<uint32_t>() : nullptr;
+    uint32_t *d_rows = !matches_cap ? nullptr : res ? res->d_rows : c->q_matches.as<uint32_t>();
+    const uint32_t *d_bitmap = res ? res->d_bitmap : c->q_bitmap.as<uint32_t>();
     call.launch([&] {
         const SetsWork W(c->q_work, n_cand);
         sets_dispatch(Q, [&](auto... ord) {
             hipLaunchKernelGGL((k_refine_sets<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)), dim3(kBlock), 0,
                                c->stream, Q.P, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(),
-                               c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), Q.words,
+                               c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), d_bitmap, Q.words,
                                (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr), d_rows, (unsigned long long)matches_cap,
                                ord...);
         });
@@ -134,10 +139,19 @@ static int refine_sets_run(const char *who, uint32_t mode, gnnpe_ctx *c, const c
         *answers = std::min<uint64_t>(c->h_pinned[0], limit);
         // every find reserved a row, so the first min(cursor, cap) rows are written
         const uint64_t n_rows = std::min<uint64_t>(c->h_pinned[1], matches_cap);
-        if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
+        if (res) res->rows_held = n_rows;
+        else if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
     }
     return call.finish(device_ms);
 }
+
+// gnnpe_refine_sets_mode on resident sets, for gnnpe_standing.hip (declared there)
+namespace gnnpe {
+int refine_sets_resident(gnnpe_ctx *c, uint32_t mode, uint64_t limit, uint64_t *answers, SetsResident *res, double *device_ms)
+{
+    return refine_sets_run("gnnpe_standing", mode, c, nullptr, nullptr, limit, answers, nullptr, 0, device_ms, res);
+}
+}  // namespace gnnpe
 
 extern "C" {
 

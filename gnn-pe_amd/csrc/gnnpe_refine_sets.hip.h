@@ -489,11 +489,33 @@ static inline std::vector<uint32_t> sets_plan_from_order(const gnnpe_host::Stati
     return pos_of;
 }
 
+// "The sets are already on the device": what a standing exact query (gnnpe_standing.hip) hands sets_prepare, sets_stage_items and
+// delta_stage in the place of the query file and the host bitmap.  The query graph was parsed once; d_bitmap is the handle's own
+// nq x words bitmap; sizes[u] = |C(u)| are on the host already (k_sets_sizes, read in a wait the handle had anyway); the start
+// candidates are written on the device by k_sets_members.  With it the three skip the file, the host walk over the sets and the two
+// uploads; the kernels read d_bitmap.  d_rows / rows_cap: the rows of the call stay on the device, in the handle's buffer, and
+// rows_held says how many were written; nothing per match comes to the host.
+struct SetsResident {
+    const gnnpe_host::StaticGraph *query = nullptr;
+    const uint32_t *d_bitmap = nullptr;
+    const uint64_t *sizes = nullptr;
+    uint32_t *d_rows = nullptr;
+    uint64_t rows_cap = 0;
+    uint64_t rows_held = 0;  // out
+};
+
+// k_sets_members of gnnpe_standing.hip on the stream: the ascending ids below n of the `words`-word bitmap row d_row into d_out (at
+// most cap of them), their number into *d_total if that is given.  Waits for nothing.
+hipError_t sets_members_launch(hipStream_t stream, const uint32_t *d_row, uint64_t words, uint32_t n, uint32_t *d_out, uint64_t cap,
+                               unsigned long long *d_total);
+
 // Everything between a call's own argument checks and the device: the state of the context, the query graph, the set sizes and the
 // matching order -- a disconnected query is refused whatever the limit -- then the plan, the pairs and the start candidates.
-// `query`, if given, receives the loaded query graph (gnnpe_refine_sets_delta builds its own orders from it).
+// `query`, if given, receives the loaded query graph (gnnpe_refine_sets_delta builds its own orders from it).  With `res` the query
+// graph and the set sizes are the handle's, Q->cand stays empty (sets_stage_items has the device write the candidates) and
+// query_graph_path and bitmap are not read.
 static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *bitmap, uint32_t mode,
-                               uint64_t limit, SetsQuery *Q, gnnpe_host::StaticGraph *query = nullptr)
+                               uint64_t limit, SetsQuery *Q, gnnpe_host::StaticGraph *query = nullptr, const SetsResident *res = nullptr)
 {
     GNNPE_REQUIRE((mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) == 0, GNNPE_ERR_ARG, "%s: unknown mode bits 0x%x", who, mode);
     const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0, induced = (mode & GNNPE_MATCH_INDUCED) != 0;
@@ -503,15 +525,16 @@ static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_
     gnnpe_host::StaticGraph q_own;
     gnnpe_host::StaticGraph &q = query ? *query : q_own;
     std::string err;
-    const int rc = q.load(query_graph_path, &err);
+    const int rc = res ? 0 : q.load(query_graph_path, &err);
     if (rc != 0) {
         set_error("%s", err.c_str());
         return rc;
     }
+    if (res) q = *res->query;
     const uint32_t nq = Q->nq = q.n;
     GNNPE_REQUIRE(nq >= 1 && nq <= (uint32_t)kSetsMaxQ, GNNPE_ERR_UNSUPPORTED, "query graphs of 1..%d vertices (got %u)", kSetsMaxQ, nq);
     const uint64_t words = Q->words = ((uint64_t)c->n + 31) / 32;
-    const std::vector<uint64_t> cnt = gnnpe_host::set_sizes(bitmap, words, nq);
+    const std::vector<uint64_t> cnt = res ? std::vector<uint64_t>(res->sizes, res->sizes + nq) : gnnpe_host::set_sizes(bitmap, words, nq);
     gnnpe_host::MatchOrder mo;
     if (gnnpe_host::build_match_order(q, cnt, &mo, &err) != 0) {
         set_error("%s", err.c_str());
@@ -520,8 +543,8 @@ static inline int sets_prepare(const char *who, gnnpe_ctx *c, const char *query_
     Q->empty = limit == 0 || std::find(cnt.begin(), cnt.end(), 0u) != cnt.end();  // an empty set anywhere means no embedding
     if (Q->empty) return GNNPE_OK;
     sets_plan_from_order(q, mo, distinct, induced, c->sw.sets_trim, Q);
-    Q->cand = gnnpe_host::set_members(bitmap, words, mo.order[0], c->n);
-    Q->n_cand = (uint32_t)Q->cand.size();
+    if (!res) Q->cand = gnnpe_host::set_members(bitmap, words, mo.order[0], c->n);
+    Q->n_cand = res ? (uint32_t)cnt[mo.order[0]] : (uint32_t)Q->cand.size();  // (a resident row has no bit at or above n)
     Q->empty = Q->n_cand == 0;
     return GNNPE_OK;
 }
@@ -550,9 +573,10 @@ static inline uint32_t sets_grid_blocks(const gnnpe_ctx *c, uint32_t nq, uint32_
 // Puts a prepared query on the device, on the context's stream, in the buffers it is handed (the context's for the one-shot call,
 // a cursor's own): the start candidates, the bitmap, zeroed counters, and for nq > 1 the offsets of the first-level items
 // (k_sets_cand_chunks and a scan; item_off[n_cand] is their number).  Chooses Q->w_shift first.  `uploaded`, if given, is recorded
-// between the copies and the kernels.  Waits for nothing.
+// between the copies and the kernels.  Waits for nothing.  With `res` nothing is uploaded: k_sets_members writes the start
+// candidates from the resident row of the start vertex (P.qv[0]), and `bm` is neither reserved nor written.
 static inline int sets_stage_items(gnnpe_ctx *c, SetsQuery *Q, const uint32_t *bitmap, DevBuf &work, DevBuf &bm, DevBuf &tmp,
-                                   hipEvent_t uploaded = nullptr)
+                                   hipEvent_t uploaded = nullptr, const SetsResident *res = nullptr)
 {
     // GNNPE_TESTING=sets_first_shift=K stands in for the heuristic; the 32-bit item offsets still come first
     Q->forced = c->sw.sets_first_shift >= 0 && c->nbr_used + c->n < (1ull << 32);
@@ -560,10 +584,14 @@ static inline int sets_stage_items(gnnpe_ctx *c, SetsQuery *Q, const uint32_t *b
     const uint32_t n_cand = Q->n_cand;
     const size_t bm_bytes = (size_t)Q->nq * Q->words * 4;
     int rc;
-    if ((rc = work.reserve(SetsWork::bytes(n_cand))) || (rc = bm.reserve(bm_bytes))) return rc;
+    if ((rc = work.reserve(SetsWork::bytes(n_cand))) || (!res && (rc = bm.reserve(bm_bytes)))) return rc;
     const SetsWork W(work, n_cand);
-    GNNPE_HIP_TRY(hipMemcpyAsync(W.cand, Q->cand.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, c->stream));
-    GNNPE_HIP_TRY(hipMemcpyAsync(bm.p, bitmap, bm_bytes, hipMemcpyHostToDevice, c->stream));
+    if (res) {
+        GNNPE_HIP_TRY(sets_members_launch(c->stream, res->d_bitmap + (uint64_t)Q->P.qv[0] * Q->words, Q->words, c->n, W.cand, n_cand, nullptr));
+    } else {
+        GNNPE_HIP_TRY(hipMemcpyAsync(W.cand, Q->cand.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, c->stream));
+        GNNPE_HIP_TRY(hipMemcpyAsync(bm.p, bitmap, bm_bytes, hipMemcpyHostToDevice, c->stream));
+    }
     GNNPE_HIP_TRY(hipMemsetAsync(W.ctr, 0, SetsWork::kCtrBytes, c->stream));
     if (uploaded) GNNPE_HIP_TRY(hipEventRecord(uploaded, c->stream));
     if (Q->nq == 1) return GNNPE_OK;

@@ -1,0 +1,602 @@
+// gnnpe_standing.hip -- THE STANDING EXACT QUERY of include/gnnpe_online.h: a handle that keeps the parsed query, the support
+// table S of the exact filter, the candidate bitmap C and the exact match count |M| on the device, and the one call that moves the
+// resident graph and every open handle forward by an edge batch.
+//
+// The loop it runs was written out three times before (include/gnnpe_hip.h, `gnnpe_main --incremental`, the tests):
+//     S -= S_T(G);  destroyed = Delta(G, C, D);  gnnpe_csr_apply_edges;  gnnpe_vde;  S += S_T(G');  C' = bitmap(S);
+//     created = Delta(G', C', I);  |M'| = |M| + created - destroyed
+// and every turn of it read and planned the query file again, walked the nq x ceil(n/32) words of C on the host, uploaded them
+// for every delta call and downloaded them after every gnnpe_filter_support_bitmap.  Here the words of C never leave the device:
+//   * gnnpe_filter_support_bitmap_device (gnnpe_filter_support.hip) writes C into the handle's buffer;
+//   * k_sets_sizes gives |C(u)|, the 8 nq bytes the host needs for the matching order and the empty-set test;
+//   * k_sets_members writes the start candidates of a full count (open, refresh) where sets_stage_items used to upload them;
+//   * the searches are the kernels of gnnpe_refine_sets_mode, gnnpe_refine_sets_delta and gnnpe_refine_sets_delta_nonedges,
+//     unchanged, reading the handle's bitmap: SetsResident of gnnpe_refine_sets.hip.h is the optional argument of sets_prepare,
+//     sets_stage_items and delta_stage that says "the sets are already on the device".
+//
+// k_sets_sizes: one workgroup per bitmap row, lanes over the words, __popc, a DPP wave sum and four LDS words.
+// k_sets_members: an ORDERED stream compaction, no atomics, so that the ids come out ascending as gnnpe_host::set_members gives
+//   them.  One workgroup walks the row tile by tile (kMembersTile words = 8192 vertices): a lane's word, its popcount, the
+//   inclusive DPP scan of the wave (wave_scan_add of gnnpe_dpp.hip.h), the four wave totals through LDS, and the lane expands its
+//   word into the tile's ids in LDS at its exclusive offset; then the workgroup stores the tile's ids to carry + i with consecutive
+//   lanes on consecutive words (the expansion's scattered stores stay in LDS), and the carry moves on by the tile's total.  The last
+//   word of the row is masked to the bits below n.  One workgroup is enough for what calls it: the start candidates of a full count
+//   at open and refresh, and gnnpe_standing_set_members; no batch runs it.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage) and the measurement: profiles/online_standing.txt.
+#include "../../include/gnnpe_online.h"
+#include "gnnpe_dpp.hip.h"
+#include "gnnpe_refine_delta.hip.h"
+
+#include <iterator>
+#include <memory>
+
+namespace gnnpe {
+
+constexpr uint32_t kMembersTile = kBlock;  // words of a row per step of k_sets_members: one per lane
+
+// the bits of word w of a row that stand for vertices below n
+__device__ __forceinline__ uint32_t sets_word_below_n(uint32_t x, uint64_t w, uint64_t words, uint32_t n)
+{
+    const uint32_t tail = n & 31u;
+    return tail && w == words - 1 ? x & ((1u << tail) - 1u) : x;
+}
+
+// sizes[u] = the set bits below n of row u; grid = nq workgroups
+static __global__ __launch_bounds__(kBlock) void k_sets_sizes(const uint32_t *__restrict__ bitmap, uint64_t words, uint32_t n,
+                                                              unsigned long long *__restrict__ sizes)
+{
+    __shared__ uint32_t s_wave[kBlock / 64];
+    const uint32_t *__restrict__ row = bitmap + (uint64_t)blockIdx.x * words;
+    uint32_t acc = 0;  // at most n < 2^32 in the whole row
+    for (uint64_t w = threadIdx.x; w < words; w += kBlock) acc += (uint32_t)__popc(sets_word_below_n(row[w], w, words, n));
+    const uint32_t sum = wave_sum_u32(acc);
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long total = 0;
+        for (int i = 0; i < kBlock / 64; i++) total += s_wave[i];
+        sizes[blockIdx.x] = total;
+    }
+}
+
+// out[0 .. min(cap, k)) = the first ids of the k set bits below n of `row`, ascending; *total = k (total may be null: the walk then
+// ends with the tile that fills cap).  One workgroup of kBlock lanes.
+static __global__ __launch_bounds__(kBlock) void k_sets_members(const uint32_t *__restrict__ row, uint64_t words, uint32_t n,
+                                                                uint32_t *__restrict__ out, uint64_t cap, unsigned long long *__restrict__ total)
+{
+    __shared__ uint32_t s_ids[kMembersTile * 32];  // the ids of one tile: 32 KiB
+    __shared__ uint32_t s_wave[kBlock / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    uint64_t carry = 0;  // ids of the tiles before this one
+    for (uint64_t w0 = 0; w0 < words; w0 += kMembersTile) {
+        if (!total && carry >= cap) break;  // (uniform)
+        const uint64_t w = w0 + t;
+        uint32_t x = w < words ? sets_word_below_n(row[w], w, words, n) : 0u;
+        const uint32_t c = (uint32_t)__popc(x);
+        const uint32_t incl = wave_scan_add(c);
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, tile_total = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kBlock / 64; i++) {
+            const uint32_t v = s_wave[i];
+            before += i < wave ? v : 0u;
+            tile_total += v;
+        }
+        uint32_t o = before + incl - c;  // at most kMembersTile * 32 - c: the expansion stays inside s_ids
+        for (; x; x &= x - 1u) s_ids[o++] = (uint32_t)(w * 32u) + (uint32_t)__ffs((int)x) - 1u;
+        __syncthreads();
+        for (uint32_t i = t; i < tile_total; i += kBlock)
+            if (carry + i < cap) out[carry + i] = s_ids[i];
+        carry += tile_total;
+        __syncthreads();  // s_wave and s_ids are written again in the next step
+    }
+    if (t == 0 && total) *total = carry;
+}
+
+hipError_t sets_members_launch(hipStream_t stream, const uint32_t *d_row, uint64_t words, uint32_t n, uint32_t *d_out, uint64_t cap,
+                               unsigned long long *d_total)
+{
+    hipLaunchKernelGGL(k_sets_members, dim3(1), dim3(kBlock), 0, stream, d_row, words, n, d_out, cap, d_total);
+    return hipGetLastError();
+}
+
+// gnnpe_refine_sets.hip, gnnpe_refine_delta.hip, gnnpe_refine_delta_nonedges.hip: the three searches on resident sets, limit 2^64 - 1
+int refine_sets_resident(gnnpe_ctx *c, uint32_t mode, uint64_t limit, uint64_t *answers, SetsResident *res, double *device_ms);
+int refine_delta_resident(gnnpe_ctx *c, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers, SetsResident *res,
+                          double *device_ms);
+int refine_delta_nonedges_resident(gnnpe_ctx *c, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers,
+                                   SetsResident *res, double *device_ms);
+
+constexpr size_t kStandingMax = 16;       // handles open on one context
+constexpr uint64_t kStandingPoison = ~0ull;  // a generation no context has: the handle is stale whatever happens
+constexpr uint32_t kMembersCanary = 16;   // words behind the ids of gnnpe_standing_set_members that must stay as they were
+
+}  // namespace gnnpe
+
+using namespace gnnpe;
+
+struct gnnpe_standing {
+    gnnpe_ctx *c = nullptr;
+    uint32_t mode = 0, l = 0, nq = 0;
+    double eps = 0.0;
+    bool filter = false;  // gnnpe_standing_open: S is kept and C derived from it; gnnpe_standing_open_sets: C is the caller's
+    gnnpe_host::StaticGraph query;  // parsed once
+    // the exact plan of gnnpe_host_query_plan_exact (filter handles): the host arrays the support calls take
+    uint32_t counts[3] = {0, 0, 0};
+    uint32_t *qv = nullptr, *ql = nullptr, *qd = nullptr;
+    double *qp = nullptr;
+    std::string path;    // of the query file: read again only where a new label table changes e, which the plan depends on
+    uint32_t plan_e = 0;
+    uint32_t n = 0;      // the graph's vertices the buffers are sized for
+    uint64_t words = 0;
+    DevBuf table, bitmap, d_sizes, members;
+    DevBuf rows[2][2];  // [0 created, 1 destroyed][the kept rows, the batch being applied]
+    int cur = 0;        // which of the two holds the kept rows
+    uint64_t rows_cap = 0;
+    std::vector<uint64_t> sizes;  // |C(u)|, from k_sets_sizes
+    uint64_t count = 0, created = 0, destroyed = 0, held[2] = {0, 0};
+    uint64_t graph_gen = 0, table_gen = 0;  // the state of the context the handle is exact for
+    // the batch being applied, committed when every handle got through
+    uint64_t p_created = 0, p_destroyed = 0, p_held[2] = {0, 0};
+    ~gnnpe_standing()
+    {
+        gnnpe_host_free(qv);
+        gnnpe_host_free(ql);
+        gnnpe_host_free(qd);
+        gnnpe_host_free(qp);
+    }
+};
+
+namespace {
+
+bool standing_stale(const gnnpe_standing *h) { return h->graph_gen != h->c->graph_gen || h->table_gen != h->c->table_gen; }
+
+#define STANDING_LIVE(who, h)                                                                                                          \
+    do {                                                                                                                               \
+        GNNPE_REQUIRE((h), GNNPE_ERR_ARG, "%s: null handle", who);                                                                     \
+        GNNPE_REQUIRE(!standing_stale(h), GNNPE_ERR_ARG,                                                                               \
+                      "%s: the graph, the labels or the label table changed behind the handle: gnnpe_standing_refresh brings it up to date", \
+                      who);                                                                                                            \
+    } while (0)
+
+int standing_whole_graph(const char *who, gnnpe_ctx *c)
+{
+    GNNPE_REQUIRE(c->have_graph && c->rows_identity, GNNPE_ERR_UNSUPPORTED, "%s: the whole graph must be on the device (gnnpe_load_csr)", who);
+    GNNPE_REQUIRE(!c->multigraph, GNNPE_ERR_UNSUPPORTED, "%s: simple graphs only (gnnpe_set_multigraph_rows was called)", who);
+    return GNNPE_OK;
+}
+
+SetsResident standing_sets(const gnnpe_standing *h)
+{
+    SetsResident R;
+    R.query = &h->query;
+    R.d_bitmap = h->bitmap.as<uint32_t>();
+    R.sizes = h->sizes.data();
+    return R;
+}
+
+// |C(u)| of the handle's bitmap to the host: k_sets_sizes, 8 nq bytes, one wait
+int standing_sizes(gnnpe_standing *h)
+{
+    gnnpe_ctx *c = h->c;
+    hipLaunchKernelGGL(k_sets_sizes, dim3(h->nq), dim3(kBlock), 0, c->stream, h->bitmap.as<uint32_t>(), h->words, h->n,
+                       h->d_sizes.as<unsigned long long>());
+    GNNPE_HIP_TRY(hipGetLastError());
+    GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned, h->d_sizes.p, (size_t)h->nq * 8, hipMemcpyDeviceToHost, c->stream));
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    h->sizes.assign(c->h_pinned, c->h_pinned + h->nq);
+    return GNNPE_OK;
+}
+
+// C = bitmap(S) on the device, then its sizes
+int standing_derive(gnnpe_standing *h, double *ms)
+{
+    double ms1 = 0.0;
+    int rc = gnnpe_filter_support_bitmap_device(h->c, h->nq, h->table.p, h->bitmap.p, ms ? &ms1 : nullptr);
+    if (ms) *ms += ms1;
+    return rc ? rc : standing_sizes(h);
+}
+
+int standing_support_delta(gnnpe_standing *h, const std::vector<uint32_t> &T, int sign, double *ms)
+{
+    double ms1 = 0.0;
+    const int rc = gnnpe_filter_support_exact_delta(h->c, h->l, h->counts, h->qv, h->ql, h->qd, h->qp, h->nq, h->eps, T.data(), T.size(), sign,
+                                                    h->table.p, ms ? &ms1 : nullptr);
+    if (ms) *ms += ms1;
+    return rc;
+}
+
+// S, C and |M| from the context's graph as it is: what open leaves, and refresh.  The buffers are sized for the graph's n.
+int standing_compute(const char *who, gnnpe_standing *h, double *ms)
+{
+    gnnpe_ctx *c = h->c;
+    int rc = standing_whole_graph(who, c);
+    if (rc) return rc;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    const uint64_t words = ((uint64_t)c->n + 31) / 32;
+    if (!h->filter)
+        GNNPE_REQUIRE(c->n == h->n, GNNPE_ERR_ARG, "%s: the graph has %u vertices, the caller's bitmap was made for %u: close the handle and open it again",
+                      who, c->n, h->n);
+    h->n = c->n;
+    h->words = words;
+    if ((rc = h->bitmap.reserve(std::max<uint64_t>((uint64_t)h->nq * words * 4, 4))) || (rc = h->d_sizes.reserve(((size_t)h->nq + 1) * 8))) return rc;
+    if (h->filter) {
+        GNNPE_REQUIRE(c->have_table, GNNPE_ERR_ARG, "%s: needs the label table and gnnpe_vde since the last change of the rows or the labels", who);
+        if (h->plan_e != c->e) {
+            gnnpe_host_free(h->qv), gnnpe_host_free(h->ql), gnnpe_host_free(h->qd), gnnpe_host_free(h->qp);
+            h->qv = h->ql = h->qd = nullptr, h->qp = nullptr;
+            uint32_t n_qv = 0;
+            if ((rc = gnnpe_host_query_plan_exact(h->path.c_str(), c->e, h->l, &n_qv, h->counts, &h->qv, &h->ql, &h->qd, &h->qp))) return rc;
+            h->plan_e = c->e;
+        }
+        if ((rc = h->table.reserve(std::max<uint64_t>((uint64_t)h->nq * c->n * 8, 8)))) return rc;
+        double ms1 = 0.0;
+        if ((rc = gnnpe_filter_support_exact(c, h->l, h->counts, h->qv, h->ql, h->qd, h->qp, h->nq, h->eps, h->table.p, ms ? &ms1 : nullptr))) return rc;
+        if (ms) *ms += ms1;
+        if ((rc = standing_derive(h, ms))) return rc;
+    } else if ((rc = standing_sizes(h)))
+        return rc;
+    SetsResident R = standing_sets(h);
+    double ms1 = 0.0;
+    uint64_t count = 0;
+    if ((rc = refine_sets_resident(c, h->mode, ~0ull, &count, &R, ms ? &ms1 : nullptr))) return rc;
+    if (ms) *ms += ms1;
+    h->count = count;
+    h->created = h->destroyed = h->held[0] = h->held[1] = 0;
+    h->graph_gen = c->graph_gen;
+    h->table_gen = c->table_gen;
+    return GNNPE_OK;
+}
+
+void standing_unregister(gnnpe_standing *h)
+{
+    auto &v = h->c->standing;
+    v.erase(std::remove(v.begin(), v.end(), static_cast<void *>(h)), v.end());
+}
+
+void standing_close_all(gnnpe_ctx *c)
+{
+    const std::vector<void *> open(c->standing);
+    c->standing.clear();
+    for (void *p : open) delete static_cast<gnnpe_standing *>(p);
+}
+
+// what both opens share: the checks, the query graph, the handle and its row buffers; the bitmap comes from `host_bitmap` or, with
+// l != 0, from the filter
+int standing_open(const char *who, gnnpe_ctx *c, const char *query_graph_path, uint32_t l, double epsilon, uint32_t mode, uint64_t rows_cap,
+                  const uint32_t *host_bitmap, gnnpe_standing **sq, uint64_t *count, double *device_ms)
+{
+    if (sq) *sq = nullptr;
+    if (count) *count = 0;
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c && query_graph_path && sq && count, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE((mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) == 0, GNNPE_ERR_ARG, "%s: unknown mode bits 0x%x", who, mode);
+    int rc = standing_whole_graph(who, c);
+    if (rc) return rc;
+    GNNPE_REQUIRE(c->standing.size() < kStandingMax, GNNPE_ERR_ARG, "%s: %zu standing queries are open on the context already", who, kStandingMax);
+    std::unique_ptr<gnnpe_standing> h(new gnnpe_standing);
+    h->c = c;
+    h->mode = mode;
+    h->filter = host_bitmap == nullptr;
+    h->l = l;
+    h->eps = epsilon;
+    h->rows_cap = rows_cap;
+    std::string err;
+    if ((rc = h->query.load(query_graph_path, &err)) != 0) {
+        set_error("%s", err.c_str());
+        return rc;
+    }
+    h->nq = h->query.n;
+    GNNPE_REQUIRE(h->nq >= 1 && h->nq <= (uint32_t)kSetsMaxQ, GNNPE_ERR_UNSUPPORTED, "query graphs of 1..%d vertices (got %u)", kSetsMaxQ, h->nq);
+    GNNPE_REQUIRE(rows_cap <= (1ull << 40) / ((uint64_t)h->nq * 4), GNNPE_ERR_ARG, "%s: rows_cap %llu", who, (unsigned long long)rows_cap);
+    h->n = c->n;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    h->path = query_graph_path;
+    if (!h->filter) {
+        const uint64_t bytes = (uint64_t)h->nq * (((uint64_t)c->n + 31) / 32) * 4;
+        if ((rc = h->bitmap.reserve(std::max<uint64_t>(bytes, 4)))) return rc;
+        if (bytes) GNNPE_HIP_TRY(hipMemcpy(h->bitmap.p, host_bitmap, bytes, hipMemcpyHostToDevice));
+    }
+    for (int which = 0; which < 2 && rows_cap; which++)
+        for (int b = 0; b < 2; b++)
+            if ((rc = h->rows[which][b].reserve((size_t)rows_cap * h->nq * 4))) return rc;
+    if ((rc = standing_compute(who, h.get(), device_ms))) return rc;
+    c->standing.push_back(h.get());
+    c->standing_close_all = standing_close_all;
+    *count = h->count;
+    *sq = h.release();
+    return GNNPE_OK;
+}
+
+// one delta search of a handle on the graph as it is: Delta (nonedges false) or N (true) of `edges`, the rows behind the p_held[which]
+// rows of the batch's buffer.  Adds to *sum.
+int standing_delta(gnnpe_standing *h, bool nonedges, const std::vector<uint32_t> &edges, int which, uint64_t *sum, double *ms)
+{
+    if (edges.empty()) return GNNPE_OK;
+    SetsResident R = standing_sets(h);
+    const uint64_t at = h->p_held[which];
+    if (h->rows_cap > at) {
+        R.d_rows = h->rows[which][h->cur ^ 1].as<uint32_t>() + at * h->nq;
+        R.rows_cap = h->rows_cap - at;
+    }
+    uint64_t found = 0;
+    double ms1 = 0.0;
+    const int rc = (nonedges ? refine_delta_nonedges_resident : refine_delta_resident)(h->c, edges.data(), edges.size() / 2, h->mode, &found, &R,
+                                                                                      ms ? &ms1 : nullptr);
+    if (rc) return rc;
+    if (ms) *ms += ms1;
+    *sum += found;
+    h->p_held[which] += R.rows_held;
+    return GNNPE_OK;
+}
+
+// One apply of the context's graph with every handle carried through it (the header has the loop).  Returns the first failure; with
+// *swapped false the graph is what it was and every S has been put back.
+int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const std::vector<uint32_t> &I, const std::vector<uint32_t> &D, bool *swapped,
+                  double *ms)
+{
+    *swapped = false;
+    std::vector<uint32_t> T(I);  // the end vertices of the step, each once
+    T.insert(T.end(), D.begin(), D.end());
+    std::sort(T.begin(), T.end());
+    T.erase(std::unique(T.begin(), T.end()), T.end());
+    int rc = GNNPE_OK;
+    std::vector<gnnpe_standing *> reduced;  // the handles whose S has lost S_T(G)
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        if (H[i]->filter && !(rc = standing_support_delta(H[i], T, -1, ms))) reduced.push_back(H[i]);
+    for (size_t i = 0; i < H.size() && !rc; i++) {
+        gnnpe_standing *h = H[i];
+        rc = standing_delta(h, false, D, 1, &h->p_destroyed, ms);
+        if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(h, true, I, 1, &h->p_destroyed, ms);
+    }
+    double ms1 = 0.0;
+    if (!rc) rc = gnnpe_csr_apply_edges(c, I.data(), I.size() / 2, D.data(), D.size() / 2, nullptr, ms ? &ms1 : nullptr);
+    if (rc) {  // nothing of the context has changed: S is put back on the unchanged graph (the message of the failure is kept)
+        const std::string why = gnnpe_last_error();
+        for (gnnpe_standing *h : reduced)
+            if (standing_support_delta(h, T, +1, nullptr)) h->graph_gen = kStandingPoison;
+        set_error("%s", why.c_str());
+        return rc;
+    }
+    *swapped = true;
+    if (ms) *ms += ms1;
+    if (c->have_table && (rc = gnnpe_vde(c, nullptr, nullptr, nullptr))) return rc;
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        if (H[i]->filter && !(rc = standing_support_delta(H[i], T, +1, ms))) rc = standing_derive(H[i], ms);
+    for (size_t i = 0; i < H.size() && !rc; i++) {
+        gnnpe_standing *h = H[i];
+        rc = standing_delta(h, false, I, 0, &h->p_created, ms);
+        if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(h, true, D, 0, &h->p_created, ms);
+    }
+    return rc;
+}
+
+// the refusals of a batch that are decided before anything changes: a loop, an id >= n, an edge in both lists (host); a deletion
+// that is no edge, an insertion that is one (k_delta_entries, one wait).  The codes and the cases are gnnpe_csr_apply_edges'.
+int standing_check_batch(const char *who, gnnpe_ctx *c, const std::vector<uint32_t> &I, const std::vector<uint32_t> &D)
+{
+    std::vector<uint64_t> ki, kd;
+    std::string err;
+    if (gnnpe_host::delta_edge_keys(c->n, I.data(), I.size() / 2, &ki, &err) != 0 || gnnpe_host::delta_edge_keys(c->n, D.data(), D.size() / 2, &kd, &err) != 0) {
+        set_error("%s: %s", who, err.c_str());
+        return GNNPE_ERR_ARG;
+    }
+    std::vector<uint64_t> both;
+    std::set_intersection(ki.begin(), ki.end(), kd.begin(), kd.end(), std::back_inserter(both));
+    GNNPE_REQUIRE(both.empty(), GNNPE_ERR_ARG, "%s: edge (%u, %u) is in both lists", who, (uint32_t)(both[0] >> 32), (uint32_t)both[0]);
+    const size_t ni = ki.size(), nd = kd.size(), np = ni + nd;
+    GNNPE_REQUIRE(np < (1ull << 31), GNNPE_ERR_ARG, "%s: %zu pairs, the items are 32-bit", who, np);
+    std::vector<uint32_t> pairs(2 * np);
+    for (size_t i = 0; i < np; i++) {
+        const uint64_t k = i < ni ? ki[i] : kd[i - ni];
+        pairs[2 * i] = (uint32_t)(k >> 32);
+        pairs[2 * i + 1] = (uint32_t)k;
+    }
+    // [counters of the insertions | counters of the deletions | pairs | entries] in the buffer of F, which the delta calls fill afterwards
+    int rc = c->q_delta.reserve(2 * sizeof(SetsCounters) + np * 12);
+    if (rc) return rc;
+    SetsCounters *ctr = c->q_delta.as<SetsCounters>();
+    uint32_t *d_pairs = reinterpret_cast<uint32_t *>(ctr + 2), *d_ent = d_pairs + 2 * np;
+    GNNPE_HIP_TRY(hipMemsetAsync(ctr, 0, 2 * sizeof(SetsCounters), c->stream));
+    GNNPE_HIP_TRY(hipMemcpyAsync(d_pairs, pairs.data(), np * 8, hipMemcpyHostToDevice, c->stream));
+    if (ni)
+        hipLaunchKernelGGL(k_delta_entries, dim3((ni + 255) / 256), dim3(256), 0, c->stream, (uint32_t)ni, d_pairs, c->adj_start.as<uint32_t>(),
+                           c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), d_ent, ctr, 0u);
+    if (nd)
+        hipLaunchKernelGGL(k_delta_entries, dim3((nd + 255) / 256), dim3(256), 0, c->stream, (uint32_t)nd, d_pairs + 2 * ni, c->adj_start.as<uint32_t>(),
+                           c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), d_ent + ni, ctr + 1, 1u);
+    GNNPE_HIP_TRY(hipGetLastError());
+    GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned, ctr, 2 * sizeof(SetsCounters), hipMemcpyDeviceToHost, c->stream));
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));  // (`pairs` lives until here)
+    const SetsCounters *R = reinterpret_cast<const SetsCounters *>(c->h_pinned);
+    GNNPE_REQUIRE(!R[0].bad, GNNPE_ERR_ARG, "%s: an insertion is already an edge of the graph", who);
+    GNNPE_REQUIRE(!R[1].bad, GNNPE_ERR_ARG, "%s: a deletion is not an edge of the graph", who);
+    return GNNPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gnnpe_standing_open(gnnpe_ctx *c, const char *query_graph_path, uint32_t l, double epsilon, uint32_t mode, uint64_t rows_cap,
+                        gnnpe_standing **sq, uint64_t *count, double *device_ms)
+{
+    const char *who = "gnnpe_standing_open";
+    if (sq) *sq = nullptr;
+    GNNPE_REQUIRE(l == 2 || l == 3, GNNPE_ERR_UNSUPPORTED, "%s: l = %u (2 or 3)", who, l);
+    return standing_open(who, c, query_graph_path, l, epsilon, mode, rows_cap, nullptr, sq, count, device_ms);
+}
+
+int gnnpe_standing_open_sets(gnnpe_ctx *c, const char *query_graph_path, uint32_t mode, uint64_t rows_cap, const uint32_t *host_bitmap,
+                             gnnpe_standing **sq, uint64_t *count, double *device_ms)
+{
+    const char *who = "gnnpe_standing_open_sets";
+    if (sq) *sq = nullptr;
+    GNNPE_REQUIRE(host_bitmap, GNNPE_ERR_ARG, "%s: null argument", who);
+    return standing_open(who, c, query_graph_path, 0, 0.0, mode, rows_cap, host_bitmap, sq, count, device_ms);
+}
+
+int gnnpe_standing_set_bitmap(gnnpe_standing *h, const uint32_t *host_bitmap)
+{
+    const char *who = "gnnpe_standing_set_bitmap";
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(host_bitmap, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(!h->filter, GNNPE_ERR_ARG, "%s: the handle keeps its own sets (gnnpe_standing_open); only gnnpe_standing_open_sets handles take a bitmap", who);
+    GNNPE_HIP_TRY(hipSetDevice(h->c->device));
+    GNNPE_HIP_TRY(hipStreamSynchronize(h->c->stream));
+    const uint64_t bytes = (uint64_t)h->nq * h->words * 4;
+    if (bytes) GNNPE_HIP_TRY(hipMemcpy(h->bitmap.p, host_bitmap, bytes, hipMemcpyHostToDevice));
+    h->graph_gen = kStandingPoison;  // until the count below is in place
+    return standing_compute(who, h, nullptr);
+}
+
+int gnnpe_standing_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges, uint64_t n_delete,
+                               double *device_ms)
+{
+    const char *who = "gnnpe_standing_apply_edges";
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c && (insert_edges || n_insert == 0) && (delete_edges || n_delete == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    int rc = standing_whole_graph(who, c);
+    if (rc) return rc;
+    std::vector<gnnpe_standing *> H;
+    bool induced = false;
+    for (void *p : c->standing) {
+        H.push_back(static_cast<gnnpe_standing *>(p));
+        STANDING_LIVE(who, H.back());
+        induced = induced || (H.back()->mode & GNNPE_MATCH_INDUCED) != 0;
+    }
+    GNNPE_REQUIRE(n_insert < (1ull << 30) && n_delete < (1ull << 30), GNNPE_ERR_ARG, "%s: %llu + %llu pairs, the key lists are 32-bit", who,
+                  (unsigned long long)n_insert, (unsigned long long)n_delete);
+    const std::vector<uint32_t> I(insert_edges, insert_edges + 2 * n_insert), D(delete_edges, delete_edges + 2 * n_delete), none;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = standing_check_batch(who, c, I, D))) return rc;
+    for (gnnpe_standing *h : H) h->p_created = h->p_destroyed = h->p_held[0] = h->p_held[1] = 0;
+    if (n_insert || n_delete) {
+        // an induced handle and a mixed batch: D first, then I (the header says why); otherwise one apply
+        const bool split = induced && n_insert && n_delete;
+        bool swapped = false;
+        rc = standing_step(c, H, split ? none : I, D, &swapped, device_ms);
+        if (rc && !swapped) return rc;  // refused with everything as it was
+        if (!rc && split) rc = standing_step(c, H, I, none, &swapped, device_ms);
+        if (rc) {  // a failure behind a swap: the graph has moved on and the handles have not
+            for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
+            return rc;
+        }
+    }
+    for (gnnpe_standing *h : H) {
+        h->created = h->p_created;
+        h->destroyed = h->p_destroyed;
+        h->count += h->p_created - h->p_destroyed;
+        h->held[0] = h->p_held[0];
+        h->held[1] = h->p_held[1];
+        if (n_insert || n_delete) h->cur ^= 1;
+        h->graph_gen = c->graph_gen;
+    }
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_result(gnnpe_standing *h, uint64_t out[6])
+{
+    const char *who = "gnnpe_standing_result";
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(out, GNNPE_ERR_ARG, "%s: null argument", who);
+    out[0] = h->count, out[1] = h->created, out[2] = h->destroyed, out[3] = h->held[0], out[4] = h->held[1], out[5] = h->graph_gen;
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_rows(gnnpe_standing *h, int which, uint32_t *host_rows, uint64_t cap, uint64_t *n_rows)
+{
+    const char *who = "gnnpe_standing_rows";
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(n_rows && (which == 0 || which == 1) && (host_rows || cap == 0), GNNPE_ERR_ARG, "%s: bad argument", who);
+    *n_rows = h->held[which];
+    const uint64_t take = std::min(cap, h->held[which]);
+    GNNPE_HIP_TRY(hipSetDevice(h->c->device));
+    if (take) GNNPE_HIP_TRY(hipMemcpy(host_rows, h->rows[which][h->cur].p, (size_t)take * h->nq * 4, hipMemcpyDeviceToHost));
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_set_sizes(gnnpe_standing *h, uint64_t *sizes)
+{
+    const char *who = "gnnpe_standing_set_sizes";
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(sizes, GNNPE_ERR_ARG, "%s: null argument", who);
+    std::copy(h->sizes.begin(), h->sizes.end(), sizes);
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_set_members(gnnpe_standing *h, uint32_t u, uint32_t *host_ids, uint64_t cap, uint64_t *n_ids)
+{
+    const char *who = "gnnpe_standing_set_members";
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(n_ids && (host_ids || cap == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(u < h->nq, GNNPE_ERR_ARG, "%s: query vertex %u of %u", who, u, h->nq);
+    gnnpe_ctx *c = h->c;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    // no more room than ids can come out; behind it words that the kernel must leave as they are
+    const uint64_t room = std::min<uint64_t>(cap, h->n);
+    int rc = h->members.reserve((room + kMembersCanary) * 4);
+    if (rc) return rc;
+    uint32_t *d_ids = h->members.as<uint32_t>();
+    unsigned long long *d_total = h->d_sizes.as<unsigned long long>() + h->nq;
+    GNNPE_HIP_TRY(hipMemsetAsync(d_ids + room, 0xFF, kMembersCanary * 4, c->stream));
+    GNNPE_HIP_TRY(sets_members_launch(c->stream, h->bitmap.as<uint32_t>() + (uint64_t)u * h->words, h->words, h->n, d_ids, room, d_total));
+    GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+    GNNPE_HIP_TRY(hipMemcpyAsync(c->h_pinned + 1, d_ids + room, kMembersCanary * 4, hipMemcpyDeviceToHost, c->stream));
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    *n_ids = c->h_pinned[0];
+    for (uint32_t i = 0; i < kMembersCanary / 2; i++)
+        GNNPE_REQUIRE(c->h_pinned[1 + i] == ~0ull, GNNPE_ERR_HIP, "%s: internal error: ids were written past the %llu asked for", who, (unsigned long long)room);
+    const uint64_t take = std::min<uint64_t>(room, *n_ids);
+    if (take) GNNPE_HIP_TRY(hipMemcpy(host_ids, d_ids, (size_t)take * 4, hipMemcpyDeviceToHost));
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_bitmap(gnnpe_standing *h, uint32_t *host_bitmap)
+{
+    const char *who = "gnnpe_standing_bitmap";
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(host_bitmap, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_HIP_TRY(hipSetDevice(h->c->device));
+    GNNPE_HIP_TRY(hipStreamSynchronize(h->c->stream));
+    const uint64_t bytes = (uint64_t)h->nq * h->words * 4;
+    if (bytes) GNNPE_HIP_TRY(hipMemcpy(host_bitmap, h->bitmap.p, bytes, hipMemcpyDeviceToHost));
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_table(gnnpe_standing *h, void **dev_table)
+{
+    const char *who = "gnnpe_standing_table";
+    if (dev_table) *dev_table = nullptr;
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(dev_table, GNNPE_ERR_ARG, "%s: null argument", who);
+    *dev_table = h->filter ? h->table.p : nullptr;
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_refresh(gnnpe_standing *h, uint64_t *count, double *device_ms)
+{
+    const char *who = "gnnpe_standing_refresh";
+    if (count) *count = 0;
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(h && count, GNNPE_ERR_ARG, "%s: null argument", who);
+    h->graph_gen = kStandingPoison;  // a refresh that fails leaves a stale handle
+    // the rows belong to a batch of the graph before
+    const int rc = standing_compute(who, h, device_ms);
+    if (rc) return rc;
+    *count = h->count;
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_close(gnnpe_standing *h)
+{
+    if (!h) return GNNPE_OK;
+    (void)hipSetDevice(h->c->device);
+    (void)hipStreamSynchronize(h->c->stream);
+    standing_unregister(h);
+    delete h;
+    return GNNPE_OK;
+}
+
+}  // extern "C"

@@ -66,6 +66,8 @@ struct Options {
     // --apply-edges FILE (exact -m online / -m filter only): lines `+ x y` / `- x y`, a batch of edge insertions and deletions
     // applied to the loaded data graph on the device before anything is computed from it (gnnpe_csr_apply_edges)
     std::string apply_edges_file;
+    std::vector<std::string> apply_edges_files;  // every --apply-edges in the order given: the batches of --standing
+    bool standing = false;  // --standing: a standing exact query carried through the batches (gnnpe_standing_* of include/gnnpe_online.h)
     // --delta-vertices FILE (needs --refine sets; with --distinct, --induced and --matches, not with --delta-edges, --delta-nonedges,
     // --all-matches, --vertex-counts or --edge-counts): one data vertex id per line; the answer is the matches with at least one image
     // among them, each once (gnnpe_refine_sets_delta_vertices); --delta-vertex-counts / --delta-edge-counts write their tables
@@ -233,7 +235,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             if (a == "--delta-nonedges") { o.delta_nonedges_file = argv[++i]; continue; }
             if (a == "--delta-vertex-counts") { o.delta_vertex_counts_file = argv[++i]; continue; }
             if (a == "--delta-edge-counts") { o.delta_edge_counts_file = argv[++i]; continue; }
-            if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; continue; }
+            if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; o.apply_edges_files.push_back(o.apply_edges_file); continue; }
             if (a == "--delta-vertices") { o.delta_vertices_file = argv[++i]; continue; }
             if (a == "--set-labels") { o.set_labels_file = argv[++i]; continue; }
             if (a == "--apply-vertices") { o.apply_vertices_file = argv[++i]; continue; }
@@ -268,6 +270,7 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "--strict") { o.strict = true; continue; }
         if (a == "--exact") { o.exact = true; continue; }
         if (a == "--incremental") { o.incremental = true; continue; }
+        if (a == "--standing") { o.standing = true; continue; }
         if (a.rfind("--", 0) == 0) {
             std::string name = a.substr(2);
             size_t eq = name.find('=');

@@ -440,6 +440,70 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
     return r;
 }
 
+// a file of --apply-edges: one `+ x y` (insert) or `- x y` (delete) per line
+static void read_edge_batch(const std::string &path, std::vector<uint32_t> *ins, std::vector<uint32_t> *del)
+{
+    FILE *af = fopen(path.c_str(), "r");
+    if (!af) die("cannot read " + path);
+    char sign = 0;
+    unsigned long long x = 0, y = 0;
+    for (int got; (got = fscanf(af, " %c %llu %llu", &sign, &x, &y)) != EOF;) {
+        if (got != 3 || (sign != '+' && sign != '-') || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull)
+            die(path + ": one `+ x y` or `- x y` per line expected");
+        std::vector<uint32_t> &to = sign == '+' ? *ins : *del;
+        to.push_back((uint32_t)x);
+        to.push_back((uint32_t)y);
+    }
+    fclose(af);
+}
+
+// -m online --exact [-l 3] --standing --apply-edges FILE [--apply-edges FILE ...]: a standing exact query (gnnpe_standing_open, with
+// --distinct / --induced in its mode) opened on the graph as loaded and carried through the batches in the order given, one
+// gnnpe_standing_apply_edges each.  Prints `standing: count created destroyed device_ms` for the open (created = destroyed = 0) and
+// after every batch.  No order and no membership.txt are read: the support calls need none.
+int run_standing(const Options &o)
+{
+    StaticGraph g;
+    std::string err;
+    int rc = g.load(o.data_graph, &err, o.strict);
+    if (rc == -1) {
+        printf("%s\n", err.c_str());
+        exit(-1);
+    }
+    if (rc != 0) die(o.data_graph + ": " + err);
+    if (!g.simple) die(o.data_graph + " repeats an edge (duplicate `e` lines): --standing needs a simple graph");
+    std::vector<std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> batches(o.apply_edges_files.size());
+    for (size_t i = 0; i < batches.size(); i++) read_edge_batch(o.apply_edges_files[i], &batches[i].first, &batches[i].second);  // before a GPU is touched
+    if (gnnpe_device_count() <= 0) die("no HIP device: this tool has no CPU fallback");
+    gnnpe_ctx *ctx = gnnpe_create(0);
+    if (!ctx) die(std::string("gnnpe_create: ") + gnnpe_last_error());
+    check(load_graph_into(ctx, g), "load_csr");
+    const uint32_t n_labels = std::max<uint32_t>(g.labels_count, 1);
+    std::vector<double> table((size_t)n_labels * o.vde_dim);
+    check(gnnpe_host_label_table(n_labels, o.vde_dim, table.data()), "label table");
+    check(gnnpe_set_label_table(ctx, n_labels, o.vde_dim, table.data()), "set_label_table");
+    check(gnnpe_vde(ctx, nullptr, nullptr, nullptr), "vde");
+    void *online = open_online(o.tool);
+    const uint32_t mode = (o.distinct ? GNNPE_MATCH_DISTINCT : 0u) | (o.induced ? GNNPE_MATCH_INDUCED : 0u);
+    gnnpe_standing *sq = nullptr;
+    uint64_t count = 0;
+    double ms = 0.0;
+    check(ONLINE(gnnpe_standing_open)(ctx, o.query_graph.c_str(), o.path_length, 1e-6, mode, 0, &sq, &count, &ms), "standing_open");
+    printf("standing: %llu 0 0 %.3f\n", (unsigned long long)count, ms);
+    const auto apply = ONLINE(gnnpe_standing_apply_edges);
+    const auto result = ONLINE(gnnpe_standing_result);
+    for (size_t i = 0; i < batches.size(); i++) {
+        const std::vector<uint32_t> &ins = batches[i].first, &del = batches[i].second;
+        check(apply(ctx, ins.data(), ins.size() / 2, del.data(), del.size() / 2, &ms), ("--apply-edges " + o.apply_edges_files[i]).c_str());
+        uint64_t out[6];
+        check(result(sq, out), "standing_result");
+        printf("standing: %llu %llu %llu %.3f\n", (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], ms);
+    }
+    check(ONLINE(gnnpe_standing_close)(sq), "standing_close");
+    gnnpe_destroy(ctx);
+    return 0;
+}
+
 // Exact mode (--exact at -l 2, always at -l 3): the plan of gnnpe_host_query_plan_exact, every path tested in
 // both orientations, so that the refinement counts every embedding.  Same answer line and candidates.bin; --timing adds the plan
 // sizes by path width and the candidate count of every query vertex.
@@ -451,8 +515,11 @@ Refinement refine_online(const Options &o, gnnpe_ctx *ctx, const StaticGraph &g,
 // ids -- the reference's candidate_set, ready for its refinement (main.cpp:176-179).  -m online goes on with the
 // refinement on the device (refine_online) and prints the reference's answer line instead of writing the file, with --distinct
 // a second line `Automorphisms: K`.
+int run_standing(const Options &o);
+
 int run_filter(const Options &o)
 {
+    if (o.standing) return run_standing(o);
     const auto t0 = Clock::now();
     const bool exact = o.exact || o.path_length == 3;  // (main() admits -l 2 and -l 3 only)
     StaticGraph g;
@@ -605,18 +672,7 @@ int run_filter(const Options &o)
     }
     if (!o.apply_edges_file.empty()) {  // the whole query runs on the updated graph
         std::vector<uint32_t> ins, del;
-        FILE *af = fopen(o.apply_edges_file.c_str(), "r");
-        if (!af) die("cannot read " + o.apply_edges_file);
-        char sign = 0;
-        unsigned long long x = 0, y = 0;
-        for (int got; (got = fscanf(af, " %c %llu %llu", &sign, &x, &y)) != EOF;) {
-            if (got != 3 || (sign != '+' && sign != '-') || x > 0xFFFFFFFFull || y > 0xFFFFFFFFull)
-                die(o.apply_edges_file + ": one `+ x y` or `- x y` per line expected");
-            std::vector<uint32_t> &to = sign == '+' ? ins : del;
-            to.push_back((uint32_t)x);
-            to.push_back((uint32_t)y);
-        }
-        fclose(af);
+        read_edge_batch(o.apply_edges_file, &ins, &del);
         uint64_t entries = 0;
         std::vector<uint32_t> ends(ins);  // T: the end vertices of the batch
         ends.insert(ends.end(), del.begin(), del.end());
@@ -830,6 +886,12 @@ int main(int argc, char **argv)
     if (!o.apply_vertices_file.empty() && !((o.mode == "online" || o.mode == "filter") && (o.exact || o.path_length == 3)))
         die("--apply-vertices applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
             "made from the graph as it was");
+    if (o.standing) {
+        if (!(o.mode == "online" && (o.exact || o.path_length == 3)) || o.apply_edges_files.empty())
+            die("--standing applies to exact -m online (--exact or -l 3) with one or more --apply-edges FILE");
+        if (o.incremental || !o.apply_vertices_file.empty() || !o.set_labels_file.empty())
+            die("--standing carries edge batches only: --incremental, --apply-vertices and --set-labels do not go with it");
+    }
     if (o.incremental && o.apply_vertices_file.empty() && o.apply_edges_file.empty() && o.set_labels_file.empty())
         die("--incremental applies with --apply-vertices, --apply-edges or --set-labels: it carries the exact filter's support table "
             "across their batches");

@@ -673,6 +673,14 @@ int gnnpe_filter_support_exact_delta(gnnpe_ctx *ctx, uint32_t l, const uint32_t 
                                      int sign, void *dev_table, double *device_ms);
 int gnnpe_filter_support_bitmap(gnnpe_ctx *ctx, uint32_t n_query_vertices, const void *dev_table, uint32_t *host_bitmap,
                                 double *device_ms);
+/* gnnpe_filter_support_bitmap_device (headed by name, GNNPE_ABI_VERSION stays 20): the kernel of gnnpe_filter_support_bitmap into
+ * the CALLER's device buffer dev_bitmap (n_query_vertices x ceil(n/32) uint32, 4-byte aligned), on the context's stream.  Every word
+ * of every row is written; the bits at positions >= n of a row's last word are zero.  Nothing comes to the host and the call waits
+ * for nothing -- what follows on the context's stream sees the bitmap -- unless device_ms is given: the two events of a timed call
+ * are waited for.  Requirements and refusals as gnnpe_filter_support_bitmap.  The consumer is the standing exact query of
+ * include/gnnpe_online.h (gnnpe_standing_open), whose candidate sets never leave the device. */
+int gnnpe_filter_support_bitmap_device(gnnpe_ctx *ctx, uint32_t n_query_vertices, const void *dev_table, void *dev_bitmap,
+                                       double *device_ms);
 
 /* The refinement half of the reference's online step (custom.h:634-932) is outside SURVEY section 8's scope (frozen since round 1)
  * and ships in a library of its own since round 6: include/gnnpe_online.h, libgnnpe_online.so (gnnpe_refine, gnnpe_host_refine). */

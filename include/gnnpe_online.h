@@ -680,6 +680,87 @@ int gnnpe_refine_pages_open_delta_vertices(gnnpe_ctx *ctx, const char *query_gra
                                            const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint64_t page_rows,
                                            uint32_t mode, gnnpe_match_cursor **cursor);
 
+/* ---- the standing exact query: resident sets, one call per edge batch -------------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section and gnnpe_filter_support_bitmap_device of include/gnnpe_hip.h only add
+ * symbols.)
+ * The consumer of the update calls, the support tables and the delta searches: a query that stays open on a changing graph and is
+ * told, batch by batch, which matches were created and which destroyed.  Composed by hand (the loops of include/gnnpe_hip.h), every
+ * batch reads and plans the query file again for every refinement call, walks the nq x ceil(n/32) words of the candidate sets on the
+ * host, uploads them for every delta call and downloads them after every gnnpe_filter_support_bitmap.  A gnnpe_standing handle is
+ * opened once per (context, query, mode) and keeps on the device, for as long as it is open: the parsed query and its plans, the
+ * support table S, the candidate bitmap C and the exact match count |M|.  Per batch nothing proportional to n crosses to the host
+ * (what does: the batch itself, the plan of the support calls, 8 nq bytes of set sizes and the counter blocks).
+ *
+ * open: the exact plan of gnnpe_host_query_plan_exact at the context's e and the given l (2 or 3), S by gnnpe_filter_support_exact
+ *   into a table the handle owns, C from S on the device, and |M| in `mode` (any combination of GNNPE_MATCH_DISTINCT and
+ *   GNNPE_MATCH_INDUCED) by the search of gnnpe_refine_sets_mode on the resident sets, limit 2^64 - 1.  *count = |M|.  Requirements
+ *   and refusals are those of gnnpe_filter_support_exact and gnnpe_refine_sets_mode: the whole simple graph on the device, the label
+ *   table, a current gnnpe_vde, a connected query of 1..32 vertices; a slab context and the multigraph state are GNNPE_ERR_UNSUPPORTED.
+ *   At most 16 handles are open on a context (the 17th open is GNNPE_ERR_ARG); they are registered on it as the output pools are,
+ *   and gnnpe_destroy closes what is still open.
+ * open_sets: no filter.  host_bitmap (nq x ceil(n/32) uint32) is uploaded once and is C from then on.  It must be sound for every
+ *   graph the handle will see (a label bitmap is; a degree bitmap is not): the library does not maintain it.  set_bitmap replaces
+ *   it and takes the count again (open_sets handles only).  No label table and no gnnpe_vde are needed.
+ * rows_cap: the first rows_cap created and the first rows_cap destroyed rows of a batch (nq uint32 each, column = query vertex id)
+ *   are kept on the device until the next batch; a cap below the true number truncates the rows, never the counts.
+ *
+ * gnnpe_standing_apply_edges(ctx, I, D): gnnpe_csr_apply_edges for the graph AND every handle open on the context.  With T the end
+ *   vertices of the batch, for every handle
+ *       S -= S_T(G);  destroyed = Delta(G, C, D);  apply;  gnnpe_vde;  S += S_T(G');  C' = bitmap(S);  created = Delta(G', C', I)
+ *   and count += created - destroyed (Delta: gnnpe_refine_sets_delta; open_sets handles skip the S steps; gnnpe_vde runs where the
+ *   context has a label table, so the context comes back with current embeddings).
+ *   INDUCED handles also lose the matches that had a non-adjacent pair on an inserted edge and gain those on a deleted one (ABI 18):
+ *       destroyed += N(G, C, I) before the apply, created += N(G', C', D) after it       (N: gnnpe_refine_sets_delta_nonedges).
+ *   A MIXED batch (both lists non-empty) on a context with an induced handle is applied in two steps, D first and then I, for every
+ *   handle: a match of G can run through an edge of D and sit on a pair of I, and one step would count it twice.  created and
+ *   destroyed are summed over the two steps; a match that exists only on the graph in between is in both, so the count is exact and
+ *   created - destroyed is the change, while the two row lists can hold such a transient match each.  Without an induced handle, or
+ *   with one list empty, there is one apply and created / destroyed are exactly M(G') \ M(G) and M(G) \ M(G').
+ *   Every search runs with limit 2^64 - 1: the counts are exact.  *device_ms (may be NULL): the sum over the calls inside.
+ *   TRANSACTIONAL.  A pair of D that is not an edge, a pair of I that already is one, an edge in both lists, a loop, an id >= n
+ *   (GNNPE_ERR_ARG, decided on the host or by one lookup kernel before anything changes), or a device allocation that
+ *   gnnpe_csr_apply_edges is refused before its swap (its code): the graph and its generation, every handle's S and C byte for
+ *   byte, its count, created, destroyed and kept rows are what they were; where S had lost S_T(G) it is added back on the unchanged
+ *   graph.  (A failure of the device AFTER a swap -- the second step of a split batch, or a HIP error -- leaves the graph moved on
+ *   and the handles stale.)  The empty batch succeeds, touches neither graph nor generation, and reports created = destroyed = 0 with
+ *   no rows.  A context without a handle gets the plain apply (and gnnpe_vde).
+ *
+ * result: {count, created, destroyed, rows_created, rows_destroyed, graph generation}: the last two say how many rows are held.
+ * rows: which = 0 created, 1 destroyed: the first min(cap, held) kept rows to host_rows, *n_rows = held.
+ * set_sizes: |C(u)| for u < nq, as k_sets_sizes left them when C was last written.
+ * set_members: the ascending ids of C(u) from k_sets_members: the first min(cap, |C(u)|) to host_ids, *n_ids = |C(u)|.
+ * bitmap: C to the host (nq x ceil(n/32) uint32), for checks and for handing the sets to the other calls of this header.
+ * table: *dev_table = S (nq x n uint64, the handle's; NULL for an open_sets handle), valid until the handle is refreshed or closed.
+ *
+ * STALENESS.  A handle remembers the graph generation and the label table it is exact for.  gnnpe_set_vertex_labels,
+ *   gnnpe_csr_apply_vertices, gnnpe_load_csr (and the other loaders), gnnpe_set_label_table and a plain gnnpe_csr_apply_edges[_map]
+ *   behind its back make it stale: every call on it except refresh and close returns GNNPE_ERR_ARG with a message naming
+ *   gnnpe_standing_refresh, and gnnpe_standing_apply_edges on the context refuses as well, before touching anything.
+ * refresh: S, C and the count again from the graph as it is (it needs what open needs, a current gnnpe_vde included): the state of a
+ *   fresh open, no rows.  An open_sets handle keeps its bitmap, and is refused if n changed.
+ * close: frees everything; close(NULL) does nothing.
+ *
+ * Device code (csrc/gnnpe_standing.hip): k_sets_sizes and k_sets_members; the searches are the kernels of the one-shot calls, which
+ * take the resident bitmap through an optional argument of their host scaffold.  DESIGN.md section 3.7, profiles/online_standing.txt.
+ * Not yet: vertex and label batches through the handle (refresh serves them for now), count tables kept by the handle, a device plan
+ * handle for the support calls (their plan is uploaded per call), slab contexts, multigraph rows. */
+typedef struct gnnpe_standing gnnpe_standing;
+int gnnpe_standing_open(gnnpe_ctx *ctx, const char *query_graph_path, uint32_t l, double epsilon, uint32_t mode, uint64_t rows_cap,
+                        gnnpe_standing **sq, uint64_t *count, double *device_ms);
+int gnnpe_standing_open_sets(gnnpe_ctx *ctx, const char *query_graph_path, uint32_t mode, uint64_t rows_cap,
+                             const uint32_t *host_bitmap, gnnpe_standing **sq, uint64_t *count, double *device_ms);
+int gnnpe_standing_set_bitmap(gnnpe_standing *sq, const uint32_t *host_bitmap);
+int gnnpe_standing_apply_edges(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges,
+                               uint64_t n_delete, double *device_ms);
+int gnnpe_standing_result(gnnpe_standing *sq, uint64_t out[6]);
+int gnnpe_standing_rows(gnnpe_standing *sq, int which, uint32_t *host_rows, uint64_t cap, uint64_t *n_rows);
+int gnnpe_standing_set_sizes(gnnpe_standing *sq, uint64_t *sizes);
+int gnnpe_standing_set_members(gnnpe_standing *sq, uint32_t u, uint32_t *host_ids, uint64_t cap, uint64_t *n_ids);
+int gnnpe_standing_bitmap(gnnpe_standing *sq, uint32_t *host_bitmap);
+int gnnpe_standing_table(gnnpe_standing *sq, void **dev_table);
+int gnnpe_standing_refresh(gnnpe_standing *sq, uint64_t *count, double *device_ms);
+int gnnpe_standing_close(gnnpe_standing *sq);
+
 #ifdef __cplusplus
 }
 #endif
