@@ -57,6 +57,7 @@ SIGNATURES = {
     "gnnpe_host_csr_entry_map": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p]),
     "gnnpe_csr_apply_edges_map": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, C.POINTER(_vp), _f64p]),
     "gnnpe_csr_carry_entries": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _f64p]),
+    "gnnpe_table_fold": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _u64p, _f64p]),
     "gnnpe_set_vertex_labels": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _f64p]),
     "gnnpe_labels_download": (C.c_int, [_vp, _u32p]),
     "gnnpe_host_csr_apply_vertices": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint64, _u32p, _u32p, C.c_uint64,
@@ -168,6 +169,9 @@ ONLINE_SIGNATURES = {
     "gnnpe_standing_set_members": (C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint64, _u64p]),
     "gnnpe_standing_bitmap": (C.c_int, [_vp, _u32p]),
     "gnnpe_standing_table": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "gnnpe_standing_keep_counts": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _f64p]),
+    "gnnpe_standing_counts": (C.c_int, [_vp, C.c_uint32, _u64p, C.POINTER(_vp), _u64p, _u64p]),
+    "gnnpe_standing_count_changes": (C.c_int, [_vp, C.c_uint32, _u64p, C.POINTER(C.c_int64), C.c_uint64, _u64p]),
     "gnnpe_standing_refresh": (C.c_int, [_vp, _u64p, _f64p]),
     "gnnpe_standing_close": (C.c_int, [_vp]),
     "gnnpe_host_refine": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
@@ -969,6 +973,7 @@ class StandingQuery:
                                                       C.byref(self.handle), C.byref(count), C.byref(ms))
         eng._ck(rc)
         self.open_ms = ms.value
+        self.changes_cap = 0  # of keep_counts
         self.nq = len(self.set_sizes())
         eng._standing.append(self)
 
@@ -1028,6 +1033,54 @@ class StandingQuery:
         if not p:
             return None
         return self.eng.copy_to_host(p, self.nq * self.eng.n * 8).view(np.uint64).reshape(self.nq, self.eng.n)
+
+    VERTEX_COUNTS, EDGE_COUNTS = 1, 2
+
+    @staticmethod
+    def _which(which):
+        return {"vertex": 1, "edge": 2, "V": 1, "E": 2}.get(which, which)
+
+    def keep_counts(self, vertex=True, edge=False, changes_cap=0, timing=False):
+        """gnnpe_standing_keep_counts: from now on the handle keeps V (nq x n) and / or E (query edges x entries) exact across
+        standing_apply_edges, and per batch the list of the cells that changed (the first changes_cap of them are held).  May be
+        called again to add the other table or to change changes_cap.  Returns the device ms with timing."""
+        ms = C.c_double()
+        self.eng._ck(self.online.gnnpe_standing_keep_counts(self.handle, (1 if vertex else 0) | (2 if edge else 0), int(changes_cap),
+                                                            C.byref(ms) if timing else None))
+        self.changes_cap = int(changes_cap)
+        return ms.value if timing else None
+
+    def counts_ptr(self, which):
+        """(device address of the kept table, rows, columns); which: 1 / "vertex" or 2 / "edge".  Valid until the next batch,
+        refresh or close; 0 for a table without cells."""
+        p, rows, cols = _vp(), C.c_uint64(), C.c_uint64()
+        self.eng._ck(self.online.gnnpe_standing_counts(self.handle, self._which(which), None, C.byref(p), C.byref(rows), C.byref(cols)))
+        return p.value or 0, rows.value, cols.value
+
+    def counts(self, which):
+        """the kept table on the host: (nq, n) or (query edges, entries) uint64"""
+        _, rows, cols = self.counts_ptr(which)
+        out = np.zeros((rows, cols), np.uint64)
+        buf = out if out.size else np.zeros(1, np.uint64)
+        self.eng._ck(self.online.gnnpe_standing_counts(self.handle, self._which(which), _ptr(buf, _u64p), None, None, None))
+        return out
+
+    def count_changes(self, which, cap=None):
+        """the cells of the kept table the last batch changed: (cells uint64 ascending, deltas int64), the first min(cap,
+        changes_cap, n_changes(which)) pairs.  A V cell is u * n + v, an E cell k * entries + j on the current graph."""
+        which = self._which(which)
+        cap = self.n_changes(which) if cap is None else int(cap)
+        cells, deltas, n = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.int64), C.c_uint64()
+        self.eng._ck(self.online.gnnpe_standing_count_changes(self.handle, which, _ptr(cells, _u64p), deltas.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                              cap, C.byref(n)))
+        held = min(cap, self.changes_cap, n.value)
+        return cells[:held], deltas[:held]
+
+    def n_changes(self, which):
+        """how many cells of the kept table the last batch changed, whatever changes_cap holds of them"""
+        n = C.c_uint64()
+        self.eng._ck(self.online.gnnpe_standing_count_changes(self.handle, self._which(which), None, None, 0, C.byref(n)))
+        return int(n.value)
 
     def refresh(self, timing=False):
         """S, C and the count again from the graph as it is now: the state of a fresh open"""
@@ -1730,6 +1783,16 @@ class Engine:
         ptrs = [C.c_void_p(int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)) if p is not None else None for p in (src, dst)]
         self._ck(self.lib.gnnpe_csr_carry_entries(self.ctx, int(n_rows), int(elem_bytes), ptrs[0], ptrs[1], C.byref(ms) if timing else None))
         return ms.value if timing else None
+
+    def table_fold(self, table, delta, cells, change_cells=None, change_deltas=None, cap=0, timing=False):
+        """gnnpe_table_fold: table += delta (mod 2^64) and delta = 0 over `cells` uint64 cells, both device pointers (an int, a
+        tensor, or an object with data_ptr()); the first `cap` pairs (cell, int64 delta) of the nonzero delta cells, ascending, go
+        to the device arrays change_cells (uint64) / change_deltas (int64), which may be None only with cap == 0.  Returns the true
+        number of nonzero delta cells, with the device ms appended with timing=True."""
+        n, ms = C.c_uint64(), C.c_double()
+        self._ck(self.lib.gnnpe_table_fold(self.ctx, _dev(table), _dev(delta), int(cells), _dev(change_cells), _dev(change_deltas),
+                                           int(cap), C.byref(n), C.byref(ms) if timing else None))
+        return (n.value, ms.value) if timing else n.value
 
     def apply_vertices(self, remove=None, add_labels=None, entry_map=False, timing=False):
         """gnnpe_csr_apply_vertices: the vertices of `remove` (ids of the graph on the device, repeats tolerated) leave with their

@@ -305,6 +305,7 @@ struct gnnpe_ctx {
     gnnpe::DevBuf q_dvcounts, q_decounts;  // ... the tables of gnnpe_refine_sets_delta_vertex_counts / _edge_counts called without dev_accum
     gnnpe::DevBuf q_nvcounts, q_necounts;  // ... the tables of gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts called without dev_accum
     gnnpe::DevBuf q_vvcounts, q_evcounts;  // ... the tables of gnnpe_refine_sets_delta_vertices_vertex_counts / _edge_counts called without dev_accum
+    gnnpe::DevBuf fold_tiles;  // gnnpe_table_fold (gnnpe_table_fold.hip): the changed cells per tile and their exclusive sums
     bool have_deg_all = false;
     bool vkey_valid = false;
     uint32_t vkey_zb = 0, vkey_lb = 0, vkey_sbits = 32;  // sbits 32 = wide (64-bit) table only

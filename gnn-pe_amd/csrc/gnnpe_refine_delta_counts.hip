@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_ecount(SetsPlan P, Sets
 static int delta_edges_counts_call(const char *who, const char *tag, bool edge_table, gnnpe_ctx *c, const char *query_graph_path,
                                    const uint32_t *candidate_bitmap, const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit,
                                    uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, void *dev_accum,
-                                   int sign, double *device_ms)
+                                   int sign, double *device_ms, const SetsResident *res = nullptr)
 {
     return delta_counts_call(
         who, tag, edge_table, false, &gnnpe_ctx::q_dvcounts, &gnnpe_ctx::q_decounts, c, query_graph_path, candidate_bitmap, delta_edges,
@@ -177,14 +177,26 @@ static int delta_edges_counts_call(const char *who, const char *tag, bool edge_t
                 hipLaunchKernelGGL((k_refine_delta_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(A.blocks), dim3(kBlock), 0,
                                    c->stream, K.P, *A.older, *A.X, A.n_items, A.F.pairs, A.F.ent, A.F.keys, A.n_keys,
                                    c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
-                                   c->q_bitmap.as<uint32_t>(), A.words, c->revpos.as<uint32_t>(), A.limit, A.ctr, A.table, A.entries, A.one,
+                                   A.bitmap, A.words, c->revpos.as<uint32_t>(), A.limit, A.ctr, A.table, A.entries, A.one,
                                    ord...);
             else
                 hipLaunchKernelGGL((k_refine_delta_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(A.blocks), dim3(kBlock), 0,
                                    c->stream, K.P, *A.older, A.n_items, A.F.pairs, A.F.ent, A.F.keys, A.n_keys, c->adj_start.as<uint32_t>(),
-                                   c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
+                                   c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), A.bitmap,
                                    A.words, A.limit, A.ctr, A.table, A.n, A.one, ord...);
-        });
+        },
+        res);
+}
+
+// the same on resident sets, adding sign * counts to the caller's table, limit 2^64 - 1, for gnnpe_standing.hip (declared there)
+int refine_delta_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers,
+                                 const SetsResident *res, void *dev_accum, int sign, double *device_ms)
+{
+    int complete = 0;
+    return edge_table ? delta_edges_counts_call("gnnpe_refine_sets_delta_edge_counts", "refine_delta_ecount", true, c, nullptr, nullptr, edges, n_edges,
+                                                ~0ull, mode, answers, &complete, nullptr, nullptr, dev_accum, sign, device_ms, res)
+                      : delta_edges_counts_call("gnnpe_refine_sets_delta_vertex_counts", "refine_delta_vcount", false, c, nullptr, nullptr, edges,
+                                                n_edges, ~0ull, mode, answers, &complete, nullptr, nullptr, dev_accum, sign, device_ms, res);
 }
 
 }  // namespace gnnpe

@@ -33,20 +33,24 @@ struct DeltaCountsLaunch {
     uint64_t entries;  // the width of the edge table
     uint32_t n;        // the width of the vertex table
     unsigned long long one;
+    const uint32_t *bitmap;  // the sets the search reads: the call's upload, or a standing query's resident bitmap
 };
 
 // The four device entries that fill a table over F after their names: the argument checks, the preparation of
 // gnnpe_refine_sets_delta (with `nonedges` of gnnpe_refine_sets_delta_nonedges: the mode must be an induced one, the anchors of the
 // launches are the query's non-adjacent pairs and F must hold no edge), the table (the context's own -- `own_v` or `own_e`, zeroed
 // on the stream before the first launch -- or the caller's, untouched until a search kernel adds to it), the launches, the single
-// wait and what comes back.  launch(c, A, K, ord...) starts the table kernel of one launch with the plan K.P.
+// wait and what comes back.  launch(c, A, K, ord...) starts the table kernel of one launch with the plan K.P.  With `res` (a standing
+// query that keeps its count tables, gnnpe_standing.hip) the sets are on the device already: query_graph_path and candidate_bitmap are
+// not read, nothing of the sets is uploaded and the kernels read res->d_bitmap.
 template <class Launch>
 static int delta_counts_call(const char *who, const char *tag, bool edge_table, bool nonedges, DevBuf gnnpe_ctx::*own_v,
                              DevBuf gnnpe_ctx::*own_e, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
                              const uint32_t *delta_edges, uint64_t n_delta, uint64_t limit, uint32_t mode, uint64_t *answers, int *complete,
-                             uint64_t *host_counts, void **dev_counts, void *dev_accum, int sign, double *device_ms, Launch &&launch)
+                             uint64_t *host_counts, void **dev_counts, void *dev_accum, int sign, double *device_ms, Launch &&launch,
+                             const SetsResident *res = nullptr)
 {
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && complete && (delta_edges || n_delta == 0), GNNPE_ERR_ARG,
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers && complete && (delta_edges || n_delta == 0), GNNPE_ERR_ARG,
                   "%s: null argument", who);
     *answers = 0;
     *complete = 0;
@@ -60,7 +64,7 @@ static int delta_counts_call(const char *who, const char *tag, bool edge_table, 
     }
     SetsQuery Q;
     gnnpe_host::StaticGraph q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, &q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, &q, res);
     if (rc) return rc;
     DeltaPlans D;
     if ((rc = delta_plans(who, c, Q, q, delta_edges, n_delta, mode, &D, nonedges))) return rc;
@@ -87,7 +91,7 @@ static int delta_counts_call(const char *who, const char *tag, bool edge_table, 
         return GNNPE_OK;
     }
     const size_t n_keys = D.keys.size();
-    if ((rc = c->q_work.reserve(SetsWork::kCtrBytes)) || (rc = c->q_bitmap.reserve((size_t)nq * Q.words * 4)) ||
+    if ((rc = c->q_work.reserve(SetsWork::kCtrBytes)) || (!res && (rc = c->q_bitmap.reserve((size_t)nq * Q.words * 4))) ||
         (rc = c->q_delta.reserve(DeltaBuf::bytes(n_keys))))
         return rc;
     // the words of the plan edges, per launch as the plans are; position 1 of a plan anchored at a non-adjacent pair has no edge
@@ -100,7 +104,8 @@ static int delta_counts_call(const char *who, const char *tag, bool edge_table, 
     SetsCounters *ctr = c->q_work.as<SetsCounters>();
     const unsigned long long one = sign == 1 ? 1ull : ~0ull;
     SetsCall call(who, c, device_ms != nullptr);
-    const uint32_t blocks = delta_stage(call, c, Q, D, candidate_bitmap, nonedges);
+    const uint32_t blocks = delta_stage(call, c, Q, D, candidate_bitmap, nonedges, nullptr, nullptr, nullptr, res);
+    const uint32_t *d_bitmap = res ? res->d_bitmap : c->q_bitmap.as<uint32_t>();
     if (c->sw.debug) {
         fprintf(stderr, "[%s] edges=%zu items=%u launches=%zu blocks=%u pairs=%u nonedges=%u accum=%d sign=%d", tag, n_keys, D.n_items,
                 D.plans.size(), blocks, D.plans[0].n_pairs, D.plans[0].n_non, dev_accum != nullptr, sign);
@@ -110,7 +115,7 @@ static int delta_counts_call(const char *who, const char *tag, bool edge_table, 
     if (call.ok() && !dev_accum && table_bytes) call.he = hipMemsetAsync(table, 0, table_bytes, c->stream);  // once per call, before the first launch
     delta_launches(call, c, D, [&](size_t k, const SetsQuery &K, auto... ord) {
         const DeltaCountsLaunch A = {blocks, &D.older[k], edge_table ? &X[k] : nullptr, D.n_items, DeltaBuf(c->q_delta, n_keys),
-                                     (uint32_t)n_keys, Q.words, (unsigned long long)limit, ctr, table, entries, n, one};
+                                     (uint32_t)n_keys, Q.words, (unsigned long long)limit, ctr, table, entries, n, one, d_bitmap};
         launch(c, A, K, ord...);
     });
     call.wait(ctr, sizeof(SetsCounters));  // all of it: `bad` is in the second half

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_nonedges_ecount(SetsPla
 static int nonedges_counts_call(const char *who, const char *tag, bool edge_table, gnnpe_ctx *c, const char *query_graph_path,
                                 const uint32_t *candidate_bitmap, const uint32_t *pairs, uint64_t n_pairs, uint64_t limit, uint32_t mode,
                                 uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, void *dev_accum, int sign,
-                                double *device_ms)
+                                double *device_ms, const SetsResident *res = nullptr)
 {
     return delta_counts_call(
         who, tag, edge_table, true, &gnnpe_ctx::q_nvcounts, &gnnpe_ctx::q_necounts, c, query_graph_path, candidate_bitmap, pairs, n_pairs,
@@ -182,14 +182,27 @@ static int nonedges_counts_call(const char *who, const char *tag, bool edge_tabl
                 hipLaunchKernelGGL((k_refine_delta_nonedges_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(A.blocks),
                                    dim3(kBlock), 0, c->stream, K.P, *A.older, *A.X, A.n_items, A.F.pairs, A.F.ent, A.F.keys, A.n_keys,
                                    c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
-                                   c->q_bitmap.as<uint32_t>(), A.words, c->revpos.as<uint32_t>(), A.limit, A.ctr, A.table, A.entries, A.one,
+                                   A.bitmap, A.words, c->revpos.as<uint32_t>(), A.limit, A.ctr, A.table, A.entries, A.one,
                                    ord...);
             else
                 hipLaunchKernelGGL((k_refine_delta_nonedges_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(A.blocks),
                                    dim3(kBlock), 0, c->stream, K.P, *A.older, A.n_items, A.F.pairs, A.F.ent, A.F.keys, A.n_keys,
                                    c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
-                                   c->q_bitmap.as<uint32_t>(), A.words, A.limit, A.ctr, A.table, A.n, A.one, ord...);
-        });
+                                   A.bitmap, A.words, A.limit, A.ctr, A.table, A.n, A.one, ord...);
+        },
+        res);
+}
+
+// the same on resident sets, adding sign * counts to the caller's table, limit 2^64 - 1, for gnnpe_standing.hip (declared there)
+int refine_delta_nonedges_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *pairs, uint64_t n_pairs, uint32_t mode,
+                                          uint64_t *answers, const SetsResident *res, void *dev_accum, int sign, double *device_ms)
+{
+    int complete = 0;
+    return edge_table ? nonedges_counts_call("gnnpe_refine_sets_delta_nonedges_edge_counts", "refine_delta_nonedges_ecount", true, c, nullptr, nullptr,
+                                             pairs, n_pairs, ~0ull, mode, answers, &complete, nullptr, nullptr, dev_accum, sign, device_ms, res)
+                      : nonedges_counts_call("gnnpe_refine_sets_delta_nonedges_vertex_counts", "refine_delta_nonedges_vcount", false, c, nullptr,
+                                             nullptr, pairs, n_pairs, ~0ull, mode, answers, &complete, nullptr, nullptr, dev_accum, sign, device_ms,
+                                             res);
 }
 
 }  // namespace gnnpe

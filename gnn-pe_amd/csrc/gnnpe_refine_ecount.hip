@@ -120,18 +120,20 @@ __global__ __launch_bounds__(kBlock) void k_refine_ecount(SetsPlan P, EcountEdge
 
 using namespace gnnpe;
 
-extern "C" int gnnpe_refine_sets_edge_counts(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
-                                             uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
-                                             void **dev_counts, double *device_ms)
+// the body of gnnpe_refine_sets_edge_counts; `res` (a standing query, gnnpe_standing.hip): the sets are on the device already and
+// the table is the handle's `dev_table` (query edges x entries uint64)
+static int refine_ecount_run(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
+                             uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, double *device_ms,
+                             const SetsResident *res = nullptr, void *dev_table = nullptr)
 {
     const char *who = "gnnpe_refine_sets_edge_counts";
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && complete, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers && complete, GNNPE_ERR_ARG, "%s: null argument", who);
     *answers = 0;
     *complete = 0;
     if (dev_counts) *dev_counts = nullptr;
     if (device_ms) *device_ms = 0.0;
     SetsQuery Q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, nullptr, res);
     if (rc || limit == 0) return rc;  // limit 0: nothing is launched, and nothing is complete
     const uint32_t nq = Q.nq, n_cand = Q.n_cand;
     const uint64_t entries = c->nbr_used;  // offsets[n] of gnnpe_load_csr: adj_start[x] = offsets[x], nbrs as handed over
@@ -144,19 +146,22 @@ extern "C" int gnnpe_refine_sets_edge_counts(gnnpe_ctx *c, const char *query_gra
         // an empty set: the table's height still has to be known for the zeros
         gnnpe_host::StaticGraph q;
         std::string err;
-        if (q.load(query_graph_path, &err) != 0) {
+        if (!res && q.load(query_graph_path, &err) != 0) {
             set_error("%s", err.c_str());
             return GNNPE_ERR_ARG;
         }
-        nqe = (uint32_t)gnnpe_host::query_edges(q).size();
+        nqe = (uint32_t)gnnpe_host::query_edges(res ? *res->query : q).size();
     }
     const size_t cells = (size_t)nqe * entries;
     unsigned long long *d_counts = nullptr;
-    if (cells) {
+    if (cells && dev_table) {
+        d_counts = static_cast<unsigned long long *>(dev_table);
+    } else if (cells) {
         // context-owned, grow-only, of its own: a vertex-count call in between leaves it alone
         if ((rc = c->q_ecounts.reserve(cells * 8))) return rc;
         d_counts = c->q_ecounts.as<unsigned long long>();
     }
+    const uint32_t *d_bitmap = res ? res->d_bitmap : nullptr;  // (q_bitmap is reserved by the staging)
     return sets_count_call(
         who, c, &Q, candidate_bitmap, limit, d_counts, cells, answers, complete, host_counts, dev_counts, device_ms,
         [&] {
@@ -167,14 +172,31 @@ extern "C" int gnnpe_refine_sets_edge_counts(gnnpe_ctx *c, const char *query_gra
         [&](const SetsWork &W, auto... ord) {
             hipLaunchKernelGGL((k_refine_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)),
                                dim3(kBlock), 0, c->stream, Q.P, X, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(),
-                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
-                               Q.words, c->revpos.as<uint32_t>(), (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr),
-                               d_counts, entries, ord...);
+                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
+                               d_bitmap ? d_bitmap : c->q_bitmap.as<uint32_t>(), Q.words, c->revpos.as<uint32_t>(),
+                               (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr), d_counts, entries, ord...);
         },
         [&](unsigned long long finds, unsigned long long flush_adds) {
             // every atomic on the table: deg_Q(last position) leaf adds per find, and the flushes
             const uint32_t leaf_deg = nq > 1 ? 1u + Q.P.back_off[nq] - Q.P.back_off[nq - 1] : 0u;
             fprintf(stderr, "[refine_ecount] finds=%llu flush_adds=%llu leaf_adds=%llu complete=%d\n", finds, flush_adds, finds * leaf_deg,
                     *complete);
-        });
+        },
+        res);
 }
+
+extern "C" int gnnpe_refine_sets_edge_counts(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                             uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
+                                             void **dev_counts, double *device_ms)
+{
+    return refine_ecount_run(c, query_graph_path, candidate_bitmap, limit, mode, answers, complete, host_counts, dev_counts, device_ms);
+}
+
+// the same on resident sets into the caller's table, limit 2^64 - 1, for gnnpe_standing.hip (declared there)
+namespace gnnpe {
+int refine_ecount_resident(gnnpe_ctx *c, uint32_t mode, uint64_t *answers, const SetsResident *res, void *dev_table, double *device_ms)
+{
+    int complete = 0;
+    return refine_ecount_run(c, nullptr, nullptr, ~0ull, mode, answers, &complete, nullptr, nullptr, device_ms, res, dev_table);
+}
+}  // namespace gnnpe

@@ -668,11 +668,13 @@ struct SetsCall {
 // (null if cells == 0).  An empty set or no start candidate: a zeroed table is the whole answer.  Otherwise the table is zeroed on
 // the stream, launch(W, ord...) starts the kernel, and after the wait *complete = total < limit; the table comes back to
 // host_counts only where it is asked for and means something.  With GNNPE_DEBUG staged() prints the call's line after the staging
-// and done(finds, flush_adds) its line after the wait.
+// and done(finds, flush_adds) its line after the wait.  With `res` (a standing query that keeps its count tables) the sets are on
+// the device already: nothing is uploaded, and launch() hands its kernel res->d_bitmap.
 template <class Staged, class Launch, class Done>
 static inline int sets_count_call(const char *who, gnnpe_ctx *c, SetsQuery *Q, const uint32_t *bitmap, uint64_t limit,
                                   unsigned long long *d_counts, size_t cells, uint64_t *answers, int *complete, uint64_t *host_counts,
-                                  void **dev_counts, double *device_ms, Staged &&staged, Launch &&launch, Done &&done)
+                                  void **dev_counts, double *device_ms, Staged &&staged, Launch &&launch, Done &&done,
+                                  const SetsResident *res = nullptr)
 {
     const size_t table_bytes = cells * 8;
     if (dev_counts) *dev_counts = d_counts;
@@ -686,7 +688,7 @@ static inline int sets_count_call(const char *who, gnnpe_ctx *c, SetsQuery *Q, c
         return GNNPE_OK;
     }
     SetsCall call(who, c, device_ms != nullptr);
-    if (call.ok()) call.rc = sets_stage_items(c, Q, bitmap, c->q_work, c->q_bitmap, c->q_tmp, call.ev0);
+    if (call.ok()) call.rc = sets_stage_items(c, Q, bitmap, c->q_work, c->q_bitmap, c->q_tmp, call.ev0, res);
     if (c->sw.debug) staged();
     if (call.ok() && table_bytes) call.he = hipMemsetAsync(d_counts, 0, table_bytes, c->stream);
     call.launch([&] {

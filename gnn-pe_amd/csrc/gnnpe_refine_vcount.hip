@@ -102,23 +102,26 @@ __global__ __launch_bounds__(kBlock) void k_refine_vcount(SetsPlan P, uint32_t n
 
 using namespace gnnpe;
 
-extern "C" int gnnpe_refine_sets_vertex_counts(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
-                                               uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
-                                               void **dev_counts, double *device_ms)
+// the body of gnnpe_refine_sets_vertex_counts; `res` (a standing query, gnnpe_standing.hip): the sets are on the device already and
+// the table is the handle's `dev_table` (nq x n uint64)
+static int refine_vcount_run(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, uint64_t limit, uint32_t mode,
+                             uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, double *device_ms,
+                             const SetsResident *res = nullptr, void *dev_table = nullptr)
 {
     const char *who = "gnnpe_refine_sets_vertex_counts";
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && complete, GNNPE_ERR_ARG, "%s: null argument", who);
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers && complete, GNNPE_ERR_ARG, "%s: null argument", who);
     *answers = 0;
     *complete = 0;
     if (dev_counts) *dev_counts = nullptr;
     if (device_ms) *device_ms = 0.0;
     SetsQuery Q;
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q);
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &Q, nullptr, res);
     if (rc || limit == 0) return rc;  // limit 0: nothing is launched, and nothing is complete
     const uint32_t nq = Q.nq, n_cand = Q.n_cand, n = c->n;
     // context-owned, grow-only: the table beside the work buffer and the bitmap
-    if ((rc = c->q_vcounts.reserve((size_t)nq * n * 8))) return rc;
-    unsigned long long *d_counts = c->q_vcounts.as<unsigned long long>();
+    if (!dev_table && (rc = c->q_vcounts.reserve((size_t)nq * n * 8))) return rc;
+    unsigned long long *d_counts = dev_table ? static_cast<unsigned long long *>(dev_table) : c->q_vcounts.as<unsigned long long>();
+    const uint32_t *d_bitmap = res ? res->d_bitmap : nullptr;  // (q_bitmap is reserved by the staging)
     return sets_count_call(
         who, c, &Q, candidate_bitmap, limit, d_counts, (size_t)nq * n, answers, complete, host_counts, dev_counts, device_ms,
         [&] {
@@ -128,10 +131,28 @@ extern "C" int gnnpe_refine_sets_vertex_counts(gnnpe_ctx *c, const char *query_g
         [&](const SetsWork &W, auto... ord) {
             hipLaunchKernelGGL((k_refine_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(sets_grid_blocks(c, nq, n_cand)),
                                dim3(kBlock), 0, c->stream, Q.P, n_cand, W.cand, W.item_off, Q.w_shift, c->adj_start.as<uint32_t>(),
-                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(),
-                               Q.words, (unsigned long long)limit, static_cast<SetsCounters *>(W.ctr), d_counts, n, ord...);
+                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
+                               d_bitmap ? d_bitmap : c->q_bitmap.as<uint32_t>(), Q.words, (unsigned long long)limit,
+                               static_cast<SetsCounters *>(W.ctr), d_counts, n, ord...);
         },
         [&](unsigned long long finds, unsigned long long flush_adds) {  // every atomic on the table: one leaf add per find, and the flushes
             fprintf(stderr, "[refine_vcount] finds=%llu flush_adds=%llu complete=%d\n", finds, flush_adds, *complete);
-        });
+        },
+        res);
 }
+
+extern "C" int gnnpe_refine_sets_vertex_counts(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                               uint64_t limit, uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts,
+                                               void **dev_counts, double *device_ms)
+{
+    return refine_vcount_run(c, query_graph_path, candidate_bitmap, limit, mode, answers, complete, host_counts, dev_counts, device_ms);
+}
+
+// the same on resident sets into the caller's table, limit 2^64 - 1, for gnnpe_standing.hip (declared there)
+namespace gnnpe {
+int refine_vcount_resident(gnnpe_ctx *c, uint32_t mode, uint64_t *answers, const SetsResident *res, void *dev_table, double *device_ms)
+{
+    int complete = 0;
+    return refine_vcount_run(c, nullptr, nullptr, ~0ull, mode, answers, &complete, nullptr, nullptr, device_ms, res, dev_table);
+}
+}  // namespace gnnpe

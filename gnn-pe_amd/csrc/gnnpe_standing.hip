@@ -23,6 +23,14 @@
 //   word of the row is masked to the bits below n.  One workgroup is enough for what calls it: the start candidates of a full count
 //   at open and refresh, and gnnpe_standing_set_members; no batch runs it.
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) and the measurement: profiles/online_standing.txt.
+//
+// COUNT TABLES (gnnpe_standing_keep_counts): a handle can keep V (nq x n) and E (query edges x entries) exact across the batches.
+// Per kept table it owns T, a scratch table D that is all zeros between batches, for E a spare for the out-of-place carry, and the
+// change arrays.  A step runs the delta count kernels of the one-shot calls on the resident sets with D as dev_accum (sign -1 before
+// the apply, +1 after it), the apply hands out the entry map where a handle on the context keeps E, T and D of E go through
+// gnnpe_csr_carry_entries, and after the last step one gnnpe_table_fold per table does T += D, D = 0 and writes the change list
+// (csrc/gnnpe_table_fold.hip says why D exists).  T, D and the spare of E take turns, so all three are sized for the largest graph
+// of the batch before its first step (standing_size_edge_tables): nothing is allocated behind a swap.  profiles/online_standing_counts.txt.
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_dpp.hip.h"
 #include "gnnpe_refine_delta.hip.h"
@@ -107,8 +115,37 @@ int refine_delta_resident(gnnpe_ctx *c, const uint32_t *edges, uint64_t n_edges,
                           double *device_ms);
 int refine_delta_nonedges_resident(gnnpe_ctx *c, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers,
                                    SetsResident *res, double *device_ms);
+// gnnpe_refine_vcount.hip, gnnpe_refine_ecount.hip: the full count tables on resident sets into the handle's table; and
+// gnnpe_refine_delta_counts.hip, gnnpe_refine_delta_nonedges_counts.hip: sign * (the tables over a set of edges / non-edges) added to
+// the handle's scratch table (`edge_table`: the per-entry table, otherwise the per-vertex one)
+int refine_vcount_resident(gnnpe_ctx *c, uint32_t mode, uint64_t *answers, const SetsResident *res, void *dev_table, double *device_ms);
+int refine_ecount_resident(gnnpe_ctx *c, uint32_t mode, uint64_t *answers, const SetsResident *res, void *dev_table, double *device_ms);
+int refine_delta_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers,
+                                 const SetsResident *res, void *dev_accum, int sign, double *device_ms);
+int refine_delta_nonedges_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *pairs, uint64_t n_pairs, uint32_t mode,
+                                          uint64_t *answers, const SetsResident *res, void *dev_accum, int sign, double *device_ms);
 
-constexpr size_t kStandingMax = 16;       // handles open on one context
+// A count table a handle keeps (gnnpe_standing_keep_counts): T, the scratch table D the delta count kernels of a batch add into and
+// gnnpe_table_fold empties, for the per-entry table the spare of the out-of-place carry, and the change list of the last batch.
+struct StandingCounts {
+    bool kept = false;
+    DevBuf table, delta, spare, ch_cells, ch_deltas;
+    uint64_t rows = 0, cols = 0;  // of T as it stands: nq x n, or query edges x entries of the current graph
+    uint64_t n_changes = 0;       // of the last batch, whatever the change arrays hold
+    uint64_t cells() const { return rows * cols; }
+    static void swap(DevBuf &a, DevBuf &b)
+    {
+        std::swap(a.p, b.p);
+        std::swap(a.bytes, b.bytes);
+    }
+    void swap_with(StandingCounts &o)
+    {
+        std::swap(kept, o.kept), std::swap(rows, o.rows), std::swap(cols, o.cols), std::swap(n_changes, o.n_changes);
+        swap(table, o.table), swap(delta, o.delta), swap(spare, o.spare), swap(ch_cells, o.ch_cells), swap(ch_deltas, o.ch_deltas);
+    }
+};
+
+constexpr size_t kStandingMax = 16;      // handles open on one context
 constexpr uint64_t kStandingPoison = ~0ull;  // a generation no context has: the handle is stale whatever happens
 constexpr uint32_t kMembersCanary = 16;   // words behind the ids of gnnpe_standing_set_members that must stay as they were
 
@@ -139,6 +176,10 @@ struct gnnpe_standing {
     uint64_t graph_gen = 0, table_gen = 0;  // the state of the context the handle is exact for
     // the batch being applied, committed when every handle got through
     uint64_t p_created = 0, p_destroyed = 0, p_held[2] = {0, 0};
+    // gnnpe_standing_keep_counts: [0] V (nq x n), [1] E (query edges x entries); changes_cap pairs of a batch's change list are held
+    StandingCounts kc[2];
+    uint32_t nqe = 0;  // the query's edges: the rows of E
+    uint64_t changes_cap = 0;
     ~gnnpe_standing()
     {
         gnnpe_host_free(qv);
@@ -207,6 +248,33 @@ int standing_support_delta(gnnpe_standing *h, const std::vector<uint32_t> &T, in
     return rc;
 }
 
+// A count table of the handle from the context's graph as it is, into K (the handle's own at a refresh, a local one in
+// gnnpe_standing_keep_counts, which hands it over only when everything is in place): the buffers sized for the graph, D zeroed once,
+// the change arrays of `cap` pairs, and T by the full count search on the resident sets.  The search's answer must be the count.
+int standing_counts_build(const char *who, gnnpe_standing *h, bool edge, uint64_t cap, StandingCounts &K, double *ms)
+{
+    gnnpe_ctx *c = h->c;
+    K.rows = edge ? h->nqe : h->nq;
+    K.cols = edge ? c->nbr_used : c->n;
+    const size_t bytes = std::max<uint64_t>(K.cells() * 8, 8), list = std::max<uint64_t>(cap * 8, 8);
+    GNNPE_REQUIRE(cap <= (1ull << 40), GNNPE_ERR_ARG, "%s: changes_cap %llu", who, (unsigned long long)cap);
+    int rc;
+    if ((rc = K.table.reserve(bytes)) || (rc = K.delta.reserve(bytes)) || (edge && (rc = K.spare.reserve(bytes))) ||
+        (rc = K.ch_cells.reserve(list)) || (rc = K.ch_deltas.reserve(list)))
+        return rc;
+    GNNPE_HIP_TRY(hipMemsetAsync(K.delta.p, 0, bytes, c->stream));
+    const SetsResident R = standing_sets(h);
+    uint64_t found = 0;
+    double ms1 = 0.0;
+    if ((rc = (edge ? refine_ecount_resident : refine_vcount_resident)(c, h->mode, &found, &R, K.table.p, ms ? &ms1 : nullptr))) return rc;
+    if (ms) *ms += ms1;
+    GNNPE_REQUIRE(found == h->count, GNNPE_ERR_HIP, "%s: internal error: the table's search found %llu matches, the count is %llu", who,
+                  (unsigned long long)found, (unsigned long long)h->count);
+    K.n_changes = 0;
+    K.kept = true;
+    return GNNPE_OK;
+}
+
 // S, C and |M| from the context's graph as it is: what open leaves, and refresh.  The buffers are sized for the graph's n.
 int standing_compute(const char *who, gnnpe_standing *h, double *ms)
 {
@@ -244,6 +312,9 @@ int standing_compute(const char *who, gnnpe_standing *h, double *ms)
     if (ms) *ms += ms1;
     h->count = count;
     h->created = h->destroyed = h->held[0] = h->held[1] = 0;
+    // every kept count table again, with empty change lists
+    for (int t = 0; t < 2; t++)
+        if (h->kc[t].kept && (rc = standing_counts_build(who, h, t == 1, h->changes_cap, h->kc[t], ms))) return rc;
     h->graph_gen = c->graph_gen;
     h->table_gen = c->table_gen;
     return GNNPE_OK;
@@ -288,6 +359,7 @@ int standing_open(const char *who, gnnpe_ctx *c, const char *query_graph_path, u
         return rc;
     }
     h->nq = h->query.n;
+    h->nqe = (uint32_t)gnnpe_host::query_edges(h->query).size();
     GNNPE_REQUIRE(h->nq >= 1 && h->nq <= (uint32_t)kSetsMaxQ, GNNPE_ERR_UNSUPPORTED, "query graphs of 1..%d vertices (got %u)", kSetsMaxQ, h->nq);
     GNNPE_REQUIRE(rows_cap <= (1ull << 40) / ((uint64_t)h->nq * 4), GNNPE_ERR_ARG, "%s: rows_cap %llu", who, (unsigned long long)rows_cap);
     h->n = c->n;
@@ -311,30 +383,71 @@ int standing_open(const char *who, gnnpe_ctx *c, const char *query_graph_path, u
 
 // one delta search of a handle on the graph as it is: Delta (nonedges false) or N (true) of `edges`, the rows behind the p_held[which]
 // rows of the batch's buffer.  Adds to *sum.
+// A handle that keeps count tables runs the table kernels of the same search with its scratch tables as dev_accum: sign -1 for what
+// the step destroys (which == 1), +1 for what it creates.  Their answers are the search's, so with rows_cap == 0 the row search is
+// left out and no match is searched twice; with rows it runs as well, and must agree.
 int standing_delta(gnnpe_standing *h, bool nonedges, const std::vector<uint32_t> &edges, int which, uint64_t *sum, double *ms)
 {
     if (edges.empty()) return GNNPE_OK;
-    SetsResident R = standing_sets(h);
-    const uint64_t at = h->p_held[which];
-    if (h->rows_cap > at) {
-        R.d_rows = h->rows[which][h->cur ^ 1].as<uint32_t>() + at * h->nq;
-        R.rows_cap = h->rows_cap - at;
-    }
+    const char *who = "gnnpe_standing_apply_edges";
     uint64_t found = 0;
-    double ms1 = 0.0;
-    const int rc = (nonedges ? refine_delta_nonedges_resident : refine_delta_resident)(h->c, edges.data(), edges.size() / 2, h->mode, &found, &R,
-                                                                                      ms ? &ms1 : nullptr);
-    if (rc) return rc;
-    if (ms) *ms += ms1;
+    bool have = false;
+    for (int t = 0; t < 2; t++) {
+        if (!h->kc[t].kept) continue;
+        const SetsResident R = standing_sets(h);
+        uint64_t got = 0;
+        double ms1 = 0.0;
+        const int rc = (nonedges ? refine_delta_nonedges_counts_resident : refine_delta_counts_resident)(
+            h->c, t == 1, edges.data(), edges.size() / 2, h->mode, &got, &R, h->kc[t].delta.p, which == 1 ? -1 : 1, ms ? &ms1 : nullptr);
+        if (rc) return rc;
+        if (ms) *ms += ms1;
+        GNNPE_REQUIRE(!have || got == found, GNNPE_ERR_HIP, "%s: internal error: the two table searches found %llu and %llu matches", who,
+                      (unsigned long long)found, (unsigned long long)got);
+        found = got;
+        have = true;
+    }
+    if (!have || h->rows_cap) {
+        SetsResident R = standing_sets(h);
+        const uint64_t at = h->p_held[which];
+        if (h->rows_cap > at) {
+            R.d_rows = h->rows[which][h->cur ^ 1].as<uint32_t>() + at * h->nq;
+            R.rows_cap = h->rows_cap - at;
+        }
+        uint64_t rows_found = 0;
+        double ms1 = 0.0;
+        const int rc = (nonedges ? refine_delta_nonedges_resident : refine_delta_resident)(h->c, edges.data(), edges.size() / 2, h->mode, &rows_found,
+                                                                                          &R, ms ? &ms1 : nullptr);
+        if (rc) return rc;
+        if (ms) *ms += ms1;
+        GNNPE_REQUIRE(!have || rows_found == found, GNNPE_ERR_HIP, "%s: internal error: the row search found %llu matches, the table search %llu",
+                      who, (unsigned long long)rows_found, (unsigned long long)found);
+        found = rows_found;
+        h->p_held[which] += R.rows_held;
+    }
     *sum += found;
-    h->p_held[which] += R.rows_held;
+    return GNNPE_OK;
+}
+
+// D = 0 for every kept table of the handles: the roll-back of a step that was refused before its swap
+int standing_zero_deltas(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H)
+{
+    bool any = false;
+    for (gnnpe_standing *h : H)
+        for (StandingCounts &K : h->kc)
+            if (K.kept && K.cells()) {
+                GNNPE_HIP_TRY(hipMemsetAsync(K.delta.p, 0, K.cells() * 8, c->stream));
+                any = true;
+            }
+    if (any) GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
     return GNNPE_OK;
 }
 
 // One apply of the context's graph with every handle carried through it (the header has the loop).  Returns the first failure; with
 // *swapped false the graph is what it was and every S has been put back.
+// `want_map` (a handle on the context keeps E): the apply is gnnpe_csr_apply_edges_map, and T and D of every kept E go through the
+// entry map before the searches on the new graph add to D.
 int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const std::vector<uint32_t> &I, const std::vector<uint32_t> &D, bool *swapped,
-                  double *ms)
+                  double *ms, bool want_map)
 {
     *swapped = false;
     std::vector<uint32_t> T(I);  // the end vertices of the step, each once
@@ -351,16 +464,30 @@ int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const st
         if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(h, true, I, 1, &h->p_destroyed, ms);
     }
     double ms1 = 0.0;
-    if (!rc) rc = gnnpe_csr_apply_edges(c, I.data(), I.size() / 2, D.data(), D.size() / 2, nullptr, ms ? &ms1 : nullptr);
+    void *map = nullptr;
+    if (!rc && want_map) rc = gnnpe_csr_apply_edges_map(c, I.data(), I.size() / 2, D.data(), D.size() / 2, nullptr, nullptr, &map, ms ? &ms1 : nullptr);
+    else if (!rc) rc = gnnpe_csr_apply_edges(c, I.data(), I.size() / 2, D.data(), D.size() / 2, nullptr, ms ? &ms1 : nullptr);
     if (rc) {  // nothing of the context has changed: S is put back on the unchanged graph (the message of the failure is kept)
         const std::string why = gnnpe_last_error();
         for (gnnpe_standing *h : reduced)
             if (standing_support_delta(h, T, +1, nullptr)) h->graph_gen = kStandingPoison;
+        if (standing_zero_deltas(c, H))  // the scratch tables lose what the searches on the unchanged graph subtracted
+            for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
         set_error("%s", why.c_str());
         return rc;
     }
     *swapped = true;
     if (ms) *ms += ms1;
+    for (gnnpe_standing *h : H) {  // the buffers were sized for the batch before its first step (standing_size_edge_tables)
+        StandingCounts &K = h->kc[1];
+        if (!K.kept) continue;
+        for (DevBuf *buf : {&K.table, &K.delta}) {
+            if ((rc = gnnpe_csr_carry_entries(c, (uint32_t)K.rows, 8, buf->p, K.spare.p, ms ? &ms1 : nullptr))) return rc;
+            if (ms) *ms += ms1;
+            StandingCounts::swap(*buf, K.spare);
+        }
+        K.cols = c->nbr_used;
+    }
     if (c->have_table && (rc = gnnpe_vde(c, nullptr, nullptr, nullptr))) return rc;
     for (size_t i = 0; i < H.size() && !rc; i++)
         if (H[i]->filter && !(rc = standing_support_delta(H[i], T, +1, ms))) rc = standing_derive(H[i], ms);
@@ -370,6 +497,34 @@ int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const st
         if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(h, true, D, 0, &h->p_created, ms);
     }
     return rc;
+}
+
+// Before the first step of a batch: T, D and the spare of every kept E get room for the largest graph the batch passes through
+// (`entries_max` entries), so that no carry needs an allocation behind a swap -- the three buffers take turns as the spare.  A spare
+// holds nothing; D is all zeros between batches; T moves into the spare when it has to grow.  A refusal leaves every table intact.
+int standing_size_edge_tables(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, uint64_t entries_max)
+{
+    for (gnnpe_standing *h : H) {
+        StandingCounts &K = h->kc[1];
+        if (!K.kept) continue;
+        const size_t need = std::max<uint64_t>(K.rows * entries_max * 8, 8);
+        int rc = K.spare.reserve(need);
+        if (rc) return rc;
+        if (K.delta.bytes < need) {
+            if ((rc = K.delta.reserve(need))) {
+                h->graph_gen = kStandingPoison;  // (a refused reserve has given the old buffer back: the handle is without its D)
+                return rc;
+            }
+            GNNPE_HIP_TRY(hipMemsetAsync(K.delta.p, 0, need, c->stream));
+        }
+        if (K.table.bytes < need) {
+            GNNPE_HIP_TRY(hipMemcpyAsync(K.spare.p, K.table.p, K.cells() * 8, hipMemcpyDeviceToDevice, c->stream));
+            GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+            StandingCounts::swap(K.table, K.spare);
+            if ((rc = K.spare.reserve(need))) return rc;
+        }
+    }
+    return GNNPE_OK;
 }
 
 // the refusals of a batch that are decided before anything changes: a loop, an id >= n, an edge in both lists (host); a deletion
@@ -473,16 +628,30 @@ int gnnpe_standing_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges, uint6
     if ((rc = standing_check_batch(who, c, I, D))) return rc;
     for (gnnpe_standing *h : H) h->p_created = h->p_destroyed = h->p_held[0] = h->p_held[1] = 0;
     if (n_insert || n_delete) {
+        bool want_map = false;  // a handle on the context keeps E: the applies hand out the entry map
+        for (gnnpe_standing *h : H) want_map = want_map || h->kc[1].kept;
+        if (want_map && (rc = standing_size_edge_tables(c, H, c->nbr_used + 2 * I.size()))) return rc;  // (each pair of I is two words)
         // an induced handle and a mixed batch: D first, then I (the header says why); otherwise one apply
         const bool split = induced && n_insert && n_delete;
         bool swapped = false;
-        rc = standing_step(c, H, split ? none : I, D, &swapped, device_ms);
+        rc = standing_step(c, H, split ? none : I, D, &swapped, device_ms, want_map);
         if (rc && !swapped) return rc;  // refused with everything as it was
-        if (!rc && split) rc = standing_step(c, H, I, none, &swapped, device_ms);
+        if (!rc && split) rc = standing_step(c, H, I, none, &swapped, device_ms, want_map);
+        // the batch is through: one fold per kept table moves D into T and leaves the batch's change list, in the cells of G'
+        for (size_t i = 0; i < H.size() && !rc; i++)
+            for (StandingCounts &K : H[i]->kc) {
+                if (!K.kept || rc) continue;
+                double ms1 = 0.0;
+                rc = gnnpe_table_fold(c, K.table.p, K.delta.p, K.cells(), K.ch_cells.p, K.ch_deltas.p, H[i]->changes_cap, &K.n_changes,
+                                      device_ms ? &ms1 : nullptr);
+                if (device_ms) *device_ms += ms1;
+            }
         if (rc) {  // a failure behind a swap: the graph has moved on and the handles have not
             for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
             return rc;
         }
+    } else {
+        for (gnnpe_standing *h : H) h->kc[0].n_changes = h->kc[1].n_changes = 0;  // the empty batch changes no cell
     }
     for (gnnpe_standing *h : H) {
         h->created = h->p_created;
@@ -572,6 +741,94 @@ int gnnpe_standing_table(gnnpe_standing *h, void **dev_table)
     STANDING_LIVE(who, h);
     GNNPE_REQUIRE(dev_table, GNNPE_ERR_ARG, "%s: null argument", who);
     *dev_table = h->filter ? h->table.p : nullptr;
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_keep_counts(gnnpe_standing *h, uint32_t which, uint64_t changes_cap, double *device_ms)
+{
+    const char *who = "gnnpe_standing_keep_counts";
+    if (device_ms) *device_ms = 0.0;
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(which && (which & ~(GNNPE_STANDING_VERTEX_COUNTS | GNNPE_STANDING_EDGE_COUNTS)) == 0, GNNPE_ERR_ARG,
+                  "%s: which = 0x%x (GNNPE_STANDING_VERTEX_COUNTS, GNNPE_STANDING_EDGE_COUNTS or both)", who, which);
+    gnnpe_ctx *c = h->c;
+    int rc = standing_whole_graph(who, c);
+    if (rc) return rc;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    // everything is made aside and handed over at the end: a refusal leaves the handle as it was
+    StandingCounts fresh[2];
+    DevBuf lists[2][2];
+    const size_t list = std::max<uint64_t>(changes_cap * 8, 8);
+    GNNPE_REQUIRE(changes_cap <= (1ull << 40), GNNPE_ERR_ARG, "%s: changes_cap %llu", who, (unsigned long long)changes_cap);
+    for (int t = 0; t < 2; t++) {
+        if (!h->kc[t].kept && (which >> t & 1u)) {
+            if ((rc = standing_counts_build(who, h, t == 1, changes_cap, fresh[t], device_ms))) return rc;
+        } else if (h->kc[t].kept && changes_cap != h->changes_cap) {
+            if ((rc = lists[t][0].reserve(list)) || (rc = lists[t][1].reserve(list))) return rc;
+        }
+    }
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int t = 0; t < 2; t++) {
+        if (fresh[t].kept) {
+            h->kc[t].swap_with(fresh[t]);
+        } else if (lists[t][0].p) {  // a table kept before, under a new cap: new change arrays, and the last batch's list is gone
+            StandingCounts::swap(h->kc[t].ch_cells, lists[t][0]);
+            StandingCounts::swap(h->kc[t].ch_deltas, lists[t][1]);
+            h->kc[t].n_changes = 0;
+        }
+    }
+    h->changes_cap = changes_cap;
+    return GNNPE_OK;
+}
+
+// the kept table a call names with exactly one bit of `which`
+static int standing_kept(const char *who, gnnpe_standing *h, uint32_t which, StandingCounts **K)
+{
+    GNNPE_REQUIRE(which == GNNPE_STANDING_VERTEX_COUNTS || which == GNNPE_STANDING_EDGE_COUNTS, GNNPE_ERR_ARG,
+                  "%s: which = 0x%x (GNNPE_STANDING_VERTEX_COUNTS or GNNPE_STANDING_EDGE_COUNTS)", who, which);
+    *K = &h->kc[which == GNNPE_STANDING_EDGE_COUNTS ? 1 : 0];
+    GNNPE_REQUIRE((*K)->kept, GNNPE_ERR_ARG, "%s: the handle does not keep that table (gnnpe_standing_keep_counts)", who);
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_counts(gnnpe_standing *h, uint32_t which, uint64_t *host_counts, void **dev_counts, uint64_t *n_rows, uint64_t *n_cols)
+{
+    const char *who = "gnnpe_standing_counts";
+    if (dev_counts) *dev_counts = nullptr;
+    if (n_rows) *n_rows = 0;
+    if (n_cols) *n_cols = 0;
+    STANDING_LIVE(who, h);
+    StandingCounts *K = nullptr;
+    const int rc = standing_kept(who, h, which, &K);
+    if (rc) return rc;
+    if (dev_counts) *dev_counts = K->cells() ? K->table.p : nullptr;
+    if (n_rows) *n_rows = K->rows;
+    if (n_cols) *n_cols = K->cols;
+    if (host_counts && K->cells()) {
+        GNNPE_HIP_TRY(hipSetDevice(h->c->device));
+        GNNPE_HIP_TRY(hipStreamSynchronize(h->c->stream));
+        GNNPE_HIP_TRY(hipMemcpy(host_counts, K->table.p, K->cells() * 8, hipMemcpyDeviceToHost));
+    }
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_count_changes(gnnpe_standing *h, uint32_t which, uint64_t *host_cells, int64_t *host_deltas, uint64_t cap, uint64_t *n_changes)
+{
+    const char *who = "gnnpe_standing_count_changes";
+    if (n_changes) *n_changes = 0;
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(n_changes && ((host_cells && host_deltas) || cap == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    StandingCounts *K = nullptr;
+    const int rc = standing_kept(who, h, which, &K);
+    if (rc) return rc;
+    *n_changes = K->n_changes;
+    const uint64_t take = std::min(std::min(cap, h->changes_cap), K->n_changes);
+    if (take) {
+        GNNPE_HIP_TRY(hipSetDevice(h->c->device));
+        GNNPE_HIP_TRY(hipStreamSynchronize(h->c->stream));
+        GNNPE_HIP_TRY(hipMemcpy(host_cells, K->ch_cells.p, take * 8, hipMemcpyDeviceToHost));
+        GNNPE_HIP_TRY(hipMemcpy(host_deltas, K->ch_deltas.p, take * 8, hipMemcpyDeviceToHost));
+    }
     return GNNPE_OK;
 }
 

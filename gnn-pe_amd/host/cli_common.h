@@ -68,6 +68,9 @@ struct Options {
     std::string apply_edges_file;
     std::vector<std::string> apply_edges_files;  // every --apply-edges in the order given: the batches of --standing
     bool standing = false;  // --standing: a standing exact query carried through the batches (gnnpe_standing_* of include/gnnpe_online.h)
+    // --standing-vertex-counts FILE, --standing-edge-counts FILE (need --standing): the handle keeps the table (gnnpe_standing_keep_counts),
+    // every batch prints `changes: <n>`, and the table after the last batch is written in the format of --vertex-counts / --edge-counts
+    std::string standing_vertex_counts_file, standing_edge_counts_file;
     // --delta-vertices FILE (needs --refine sets; with --distinct, --induced and --matches, not with --delta-edges, --delta-nonedges,
     // --all-matches, --vertex-counts or --edge-counts): one data vertex id per line; the answer is the matches with at least one image
     // among them, each once (gnnpe_refine_sets_delta_vertices); --delta-vertex-counts / --delta-edge-counts write their tables
@@ -206,7 +209,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       change; applied on the device first, so that --apply-edges, --set-labels and --delta-vertices name the new ids\n"
                    "       --incremental (with --apply-edges, --set-labels or --apply-vertices): the candidate sets come from the exact\n"
                    "       filter's support table, built on the graph as loaded and patched around every batch, not from a filter pass over\n"
-                   "       the updated graph; same sets, same answer\n",
+                   "       the updated graph; same sets, same answer\n"
+                   "       --standing-vertex-counts FILE, --standing-edge-counts FILE (need --standing; either or both): the standing query\n"
+                   "       keeps the table across the --apply-edges batches, prints `changes: <n>` per batch (the cells the batch changed,\n"
+                   "       over the kept tables) and writes the table after the last batch as --vertex-counts / --edge-counts do\n",
                    tool, tool);
             exit(0);
         }
@@ -226,8 +232,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges" ||
             a == "--delta-nonedges" ||
             a == "--apply-edges" || a == "--delta-vertex-counts" || a == "--delta-edge-counts" || a == "--delta-vertices" ||
-            a == "--set-labels" || a == "--apply-vertices") {
+            a == "--set-labels" || a == "--apply-vertices" || a == "--standing-vertex-counts" || a == "--standing-edge-counts") {
             if (i + 1 >= argc) die(a + " needs a value");
+            if (a == "--standing-vertex-counts") { o.standing_vertex_counts_file = argv[++i]; continue; }
+            if (a == "--standing-edge-counts") { o.standing_edge_counts_file = argv[++i]; continue; }
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }
             if (a == "--vertex-counts") { o.vertex_counts_file = argv[++i]; continue; }
             if (a == "--edge-counts") { o.edge_counts_file = argv[++i]; continue; }

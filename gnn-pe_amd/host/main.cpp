@@ -490,14 +490,53 @@ int run_standing(const Options &o)
     double ms = 0.0;
     check(ONLINE(gnnpe_standing_open)(ctx, o.query_graph.c_str(), o.path_length, 1e-6, mode, 0, &sq, &count, &ms), "standing_open");
     printf("standing: %llu 0 0 %.3f\n", (unsigned long long)count, ms);
+    // --standing-vertex-counts / --standing-edge-counts: the handle keeps the tables; only the number of changed cells is asked for
+    const uint32_t keep = (o.standing_vertex_counts_file.empty() ? 0u : GNNPE_STANDING_VERTEX_COUNTS) |
+                          (o.standing_edge_counts_file.empty() ? 0u : GNNPE_STANDING_EDGE_COUNTS);
+    if (keep) check(ONLINE(gnnpe_standing_keep_counts)(sq, keep, 0, nullptr), "standing_keep_counts");
     const auto apply = ONLINE(gnnpe_standing_apply_edges);
     const auto result = ONLINE(gnnpe_standing_result);
+    const auto changes = ONLINE(gnnpe_standing_count_changes);
     for (size_t i = 0; i < batches.size(); i++) {
         const std::vector<uint32_t> &ins = batches[i].first, &del = batches[i].second;
         check(apply(ctx, ins.data(), ins.size() / 2, del.data(), del.size() / 2, &ms), ("--apply-edges " + o.apply_edges_files[i]).c_str());
         uint64_t out[6];
         check(result(sq, out), "standing_result");
         printf("standing: %llu %llu %llu %.3f\n", (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], ms);
+        if (keep) {
+            uint64_t total = 0;
+            for (uint32_t which : {GNNPE_STANDING_VERTEX_COUNTS, GNNPE_STANDING_EDGE_COUNTS}) {
+                uint64_t n_changes = 0;
+                if (keep & which) check(changes(sq, which, nullptr, nullptr, 0, &n_changes), "standing_count_changes");
+                total += n_changes;
+            }
+            printf("changes: %llu\n", (unsigned long long)total);
+        }
+    }
+    if (keep) {  // the tables after the last batch, on the graph as it is now
+        uint64_t entries = 0;
+        g.offsets.assign((size_t)g.n + 1, 0);
+        (void)gnnpe_csr_download(ctx, g.offsets.data(), nullptr, 0, &entries);  // no room: refused with the entry count set
+        g.neighbors.assign(entries, 0);
+        check(gnnpe_csr_download(ctx, g.offsets.data(), g.neighbors.data(), entries, &entries), "csr_download");
+        const auto counts = ONLINE(gnnpe_standing_counts);
+        uint64_t rows = 0, cols = 0;
+        if (keep & GNNPE_STANDING_VERTEX_COUNTS) {
+            check(counts(sq, GNNPE_STANDING_VERTEX_COUNTS, nullptr, nullptr, &rows, &cols), "standing_counts");
+            std::vector<uint64_t> table(rows * cols);
+            check(counts(sq, GNNPE_STANDING_VERTEX_COUNTS, table.data(), nullptr, nullptr, nullptr), "standing_counts");
+            write_vertex_table(o.standing_vertex_counts_file, g, (uint32_t)rows, table);
+        }
+        if (keep & GNNPE_STANDING_EDGE_COUNTS) {
+            check(counts(sq, GNNPE_STANDING_EDGE_COUNTS, nullptr, nullptr, &rows, &cols), "standing_counts");
+            if (cols != entries) die("--standing-edge-counts: the table has " + std::to_string(cols) + " columns, the graph " + std::to_string(entries) + " entries");
+            std::vector<uint64_t> table(rows * cols);
+            check(counts(sq, GNNPE_STANDING_EDGE_COUNTS, table.data(), nullptr, nullptr, nullptr), "standing_counts");
+            uint32_t nqe = 0;
+            std::vector<uint32_t> qe(2 * (size_t)rows + 2);
+            check(ONLINE(gnnpe_host_query_edges)(o.query_graph.c_str(), qe.data(), (uint32_t)(qe.size() / 2), &nqe), "host_query_edges");
+            write_edge_table(o.standing_edge_counts_file, g, nqe, qe, table);
+        }
     }
     check(ONLINE(gnnpe_standing_close)(sq), "standing_close");
     gnnpe_destroy(ctx);
@@ -891,7 +930,8 @@ int main(int argc, char **argv)
             die("--standing applies to exact -m online (--exact or -l 3) with one or more --apply-edges FILE");
         if (o.incremental || !o.apply_vertices_file.empty() || !o.set_labels_file.empty())
             die("--standing carries edge batches only: --incremental, --apply-vertices and --set-labels do not go with it");
-    }
+    } else if (!o.standing_vertex_counts_file.empty() || !o.standing_edge_counts_file.empty())
+        die("--standing-vertex-counts and --standing-edge-counts need --standing");
     if (o.incremental && o.apply_vertices_file.empty() && o.apply_edges_file.empty() && o.set_labels_file.empty())
         die("--incremental applies with --apply-vertices, --apply-edges or --set-labels: it carries the exact filter's support table "
             "across their batches");

@@ -235,6 +235,23 @@ int gnnpe_csr_apply_edges_map(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint
 int gnnpe_csr_carry_entries(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes,
                             const void *dev_src, void *dev_dst, double *device_ms);
 
+/* ---- folding a scratch table into a count table -----------------------------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section only adds a symbol.)
+ * gnnpe_table_fold: dev_table and dev_delta are `cells` uint64 each on the context's device, 8-byte aligned, not overlapping.
+ *   After the call table[i] = table[i] + delta[i] mod 2^64 for every i and delta is all zeros.  With n the number of nonzero
+ *   delta[i], the first min(cap, n) pairs (i, (int64) delta[i]), in ascending i, sit in dev_change_cells (uint64) and
+ *   dev_change_deltas (int64); nothing behind min(cap, n) is written; *n_changes = n whatever cap is.  The change arrays may be NULL
+ *   iff cap == 0.  GNNPE_ERR_ARG before any launch: a null or misaligned pointer, ranges that overlap (any two of the four), a
+ *   missing change array with cap > 0.  cells == 0 succeeds with *n_changes = 0.  The work runs on the context's stream with one
+ *   host wait, for n_changes.
+ *   The consumer is the standing exact query that keeps its count tables (gnnpe_standing_keep_counts of include/gnnpe_online.h):
+ *   the delta count kernels of a batch add into a scratch table, the fold moves it into the table.  The zeroing happens inside the
+ *   fold, so no batch pays a memset of the table's size; a refused batch is one memset of the scratch with the table untouched; and
+ *   the list of changed cells comes out of the same pass.  Two passes over fixed tiles (csrc/gnnpe_table_fold.hip): a tile without a
+ *   nonzero cell costs the second pass one word. */
+int gnnpe_table_fold(gnnpe_ctx *ctx, void *dev_table, void *dev_delta, uint64_t cells, void *dev_change_cells, void *dev_change_deltas,
+                     uint64_t cap, uint64_t *n_changes, double *device_ms);
+
 /* ---- vertex relabel on the resident graph -----------------------------------------------------------------------------------------
  * (Headed by name: GNNPE_ABI_VERSION stays 20, this section and gnnpe_refine_sets_delta_vertices of include/gnnpe_online.h only add
  * symbols.)

@@ -742,8 +742,53 @@ int gnnpe_refine_pages_open_delta_vertices(gnnpe_ctx *ctx, const char *query_gra
  *
  * Device code (csrc/gnnpe_standing.hip): k_sets_sizes and k_sets_members; the searches are the kernels of the one-shot calls, which
  * take the resident bitmap through an optional argument of their host scaffold.  DESIGN.md section 3.7, profiles/online_standing.txt.
- * Not yet: vertex and label batches through the handle (refresh serves them for now), count tables kept by the handle, a device plan
- * handle for the support calls (their plan is uploaded per call), slab contexts, multigraph rows. */
+ *
+ * COUNT TABLES KEPT BY THE HANDLE (GNNPE_ABI_VERSION stays 20: symbols are added, and a handle that never calls keep_counts does,
+ * byte for byte and launch for launch, what it did before).  The tables of ABI 13 and 14 on a changing graph, without the loop
+ * `T -= ED(G, D); apply_map; T = carry(T); T += ED(G', I)` written by hand and without its per-call query file, host walk over C and
+ * upload:
+ *     V[u][v]: in how many matches of the handle's mode data vertex v is the image of query vertex u (nq x n uint64);
+ *     E[k][j]: the same per adjacency entry j of the current graph and query edge k (query edges x entries uint64).
+ * keep_counts(which, changes_cap): `which` is GNNPE_STANDING_VERTEX_COUNTS, GNNPE_STANDING_EDGE_COUNTS or both.  The tables are
+ *   built now, on the graph as it is, by the searches of gnnpe_refine_sets_vertex_counts / _edge_counts on the resident sets, in the
+ *   handle's mode, limit 2^64 - 1, into buffers the handle owns; per table it also reserves a scratch table D of the same size,
+ *   zeroed once, for E one spare of the same size (the carry is out of place), and change arrays of changes_cap pairs.  It may be
+ *   called again to add the other table or to change changes_cap (a table kept already stays as it is; a new cap empties the held
+ *   change lists).  A stale handle is refused; an allocation the device refuses returns its code and leaves the handle as it was,
+ *   without the table.
+ * gnnpe_standing_apply_edges with such a handle: every step of the loop above also does, with D as dev_accum of the delta count
+ *   kernels (ABI 17 and 19),
+ *       D -= counts of Delta(G, C, D-list)  [induced: D -= counts of N(G, C, I)]      before the apply,
+ *       T and D of E carried through the entry map (gnnpe_csr_carry_entries)           after it,
+ *       D += counts of Delta(G', C', I)     [induced: D += counts of N(G', C', D-list)]
+ *   the apply being gnnpe_csr_apply_edges_map if any handle on the context keeps E and the plain one otherwise.  After the last step
+ *   ONE gnnpe_table_fold (include/gnnpe_hip.h) per kept table moves D into T and leaves the change list; a split induced mixed
+ *   batch carries D through both applies and still folds once, so a batch has one change list, in the cells of the graph after it.
+ *   The count kernels' answers are the searches' created / destroyed: with rows_cap == 0 the row searches are left out and no match
+ *   is searched twice; with rows_cap > 0 both run (and must agree).  A refused batch leaves T and the last batch's change list byte
+ *   for byte as they were and D all zeros (one memset); a failure behind a swap makes the handle stale, as before.  refresh (and
+ *   set_bitmap) rebuild every kept table and empty the change lists.
+ * counts(which: one bit): the table to host_counts (may be NULL), *dev_counts = T (valid until the next batch, refresh or close),
+ *   *n_rows x *n_cols its shape.  A single-vertex query has an E of no rows (and *dev_counts = NULL) and a V no edge batch changes.
+ * count_changes(which: one bit): the cells the last batch changed, ascending, with new - old as int64: the first
+ *   min(cap, changes_cap, n) pairs to host_cells / host_deltas, *n_changes = n, the true number.  A V cell is u * n + v.  An E cell is
+ *   k * entries + j with j an entry of the CURRENT graph: entries the batch deleted are gone and not listed, an inserted entry's
+ *   delta is its new value, and a cell whose created and destroyed parts cancel is not listed.
+ *   counts and count_changes on a handle that does not keep `which` are GNNPE_ERR_ARG.
+ * WHY THE TABLES STAY EXACT WHILE C CHANGES.  With the filter, the steps of one batch search with different sets: C before the
+ *   apply, C' after it.  Both are SOUND: they hold f(u) for every match f of their graph (in every mode: the filter keeps every
+ *   embedding).  A search restricted to a sound set finds exactly the matches of the unrestricted search, so V_m(C) and E_m(C) are
+ *   the tables V_m and E_m of the graph itself, whichever sound set was used.  The identities the loop rests on are statements
+ *   about those: with M(G) the matches, M(G) \ M(G') is what Delta(G, ., D) (and N(G, ., I)) finds and M(G') \ M(G) what
+ *   Delta(G', ., I) (and N(G', ., D)) finds (ABI 17 and 19), so T(G') = T(G) - table(M(G) \ M(G')) + table(M(G') \ M(G)) holds
+ *   across the two different sound sets.  open_sets handles rely on the caller's promise above that the bitmap is sound for every
+ *   graph the handle will see.
+ *
+ * Not yet: vertex and label batches through the handle (refresh serves them for now), a fused carry-and-fold for E (T and D of E are
+ * carried as two gathers per apply), paged change lists (what is behind changes_cap is counted, not held), a device plan handle for
+ * the support calls (their plan is uploaded per call), slab contexts, multigraph rows. */
+#define GNNPE_STANDING_VERTEX_COUNTS 1u
+#define GNNPE_STANDING_EDGE_COUNTS 2u
 typedef struct gnnpe_standing gnnpe_standing;
 int gnnpe_standing_open(gnnpe_ctx *ctx, const char *query_graph_path, uint32_t l, double epsilon, uint32_t mode, uint64_t rows_cap,
                         gnnpe_standing **sq, uint64_t *count, double *device_ms);
@@ -758,6 +803,11 @@ int gnnpe_standing_set_sizes(gnnpe_standing *sq, uint64_t *sizes);
 int gnnpe_standing_set_members(gnnpe_standing *sq, uint32_t u, uint32_t *host_ids, uint64_t cap, uint64_t *n_ids);
 int gnnpe_standing_bitmap(gnnpe_standing *sq, uint32_t *host_bitmap);
 int gnnpe_standing_table(gnnpe_standing *sq, void **dev_table);
+int gnnpe_standing_keep_counts(gnnpe_standing *sq, uint32_t which, uint64_t changes_cap, double *device_ms);
+int gnnpe_standing_counts(gnnpe_standing *sq, uint32_t which, uint64_t *host_counts, void **dev_counts, uint64_t *n_rows,
+                          uint64_t *n_cols);
+int gnnpe_standing_count_changes(gnnpe_standing *sq, uint32_t which, uint64_t *host_cells, int64_t *host_deltas, uint64_t cap,
+                                 uint64_t *n_changes);
 int gnnpe_standing_refresh(gnnpe_standing *sq, uint64_t *count, double *device_ms);
 int gnnpe_standing_close(gnnpe_standing *sq);
 
