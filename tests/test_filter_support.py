@@ -8,7 +8,8 @@ set_order and vde.  The engines under test never get an order: the support calls
 
 Shapes: G(300, 1500) with 4 labels plus one hub joined to 150 vertices (n = 301: a multiple of neither 32 nor 64; the hub's row is
 three chunks of 64 lanes, the last one partial), one vertex isolated; e in {1, 2, 3}, l in {2, 3}.  The edge loop wants a row that goes
-from 64 to 65 entries and back, so its graph has the hub joined to 64 vertices instead."""
+from 64 to 65 entries and back, so its graph has the hub joined to 64 vertices instead.  The slices of k_support_walk want more
+than 2^18 items and a row of more than 128 entries: 350 000 vertices, nearly all isolated, and a hub of 300 (sparse_hub_graph)."""
 import os
 import re
 import subprocess
@@ -463,6 +464,96 @@ def test_gpu_vertex_loop(oracle, tmp_path, l, e):
             before = after
         eng.close()
     moves.check()
+
+
+# ---- 5b. the slices of an anchor's row -----------------------------------------------------------------------------------------------
+
+_SPARSE = {}
+SPARSE_N, SPARSE_CORE, SPARSE_HUB_DEG = 350000, 600, 300
+
+
+def sparse_hub_graph():
+    """350 000 vertices, all but the first 600 isolated: G(600, 900) with four labels, vertex 300 (label 1) joined to 300 of the
+    others -- a row of five chunks of 64 lanes.  The yardstick's path join drops the isolated vertices at its first step."""
+    if not _SPARSE:
+        from gnnpe_amd import synth
+        g0 = synth.gnm_graph(SPARSE_CORE, 900, n_labels=NL, seed=13)
+        rng = np.random.default_rng(14)
+        edges = {(int(a), int(b)) for a, b in zip(g0["eu"], g0["ev"])}
+        others = np.setdiff1d(np.arange(SPARSE_CORE), [HUB])
+        keep = {e for e in edges if HUB not in e}
+        keep |= {(min(int(v), HUB), max(int(v), HUB)) for v in rng.choice(others, SPARSE_HUB_DEG, replace=False)}
+        labels = np.concatenate([g0["labels"], rng.integers(0, NL, SPARSE_N - SPARSE_CORE)]).astype(np.uint32)
+        labels[HUB] = 1
+        core = graph_of(SPARSE_CORE, keep, labels[:SPARSE_CORE])  # (the CSR of the core, then 349 400 empty rows)
+        offsets = np.concatenate([core["offsets"], np.full(SPARSE_N - SPARSE_CORE, core["offsets"][-1], np.uint32)])
+        _SPARSE["g"] = dict(core, n=SPARSE_N, offsets=offsets, labels=labels)
+    return _SPARSE["g"]
+
+
+def sparse_vde(oracle, g, e):
+    """the oracle's embeddings of sparse_hub_graph in milliseconds: an embedding is made of the vertex' label and its row, so an
+    isolated vertex has the embedding of its label.  The oracle runs on the core with one isolated vertex per label appended, and
+    the 349 400 isolated vertices take the row of their label (equal to the oracle's run on the whole graph bit for bit; that run
+    takes more than a second)"""
+    C = SPARSE_CORE
+    offs = np.concatenate([g["offsets"][:C + 1], np.full(NL, g["offsets"][C], np.uint32)])
+    small = oracle.gen_vde(offs, g["nbrs"], np.concatenate([g["labels"][:C], np.arange(NL)]).astype(np.uint32), e)[2]
+    vde = small[C:][g["labels"]]
+    vde[:C] = small[:C]
+    return vde
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("want_slices", [3, 2])
+@pytest.mark.parametrize("l", [2, 3])
+def test_gpu_delta_slices_stride_over_a_long_row(oracle, tmp_path, l, want_slices):
+    """k_support_walk cuts the anchor's own row into slices: slice s of n_slices takes the chunks s, s + n_slices, ...  With a list
+    of more than 2^18 ids the host gives every item 2 or 3 slices (about 2^20 waves in all), and the hub's row of 300 entries has
+    five chunks: a slice takes a SECOND chunk, n_slices lanes-of-64 further on.  Every other test has at most 301 items (64 slices)
+    and rows of at most 150 entries, so there the stride never ran.  S_T against np_support, sign +1 and back with -1.
+    Wall time on one MI355X (pytest --durations, call phase, the cases in the order of this file, beside test_gpu_counts_loop_
+    against_brute_force of tests/test_standing_counts.py, whose slowest case took 0.22 - 0.34 s): [2-3] 0.08 s, [2-2] 0.07 s, [3-3]
+    0.20 s, [3-2] 0.09 s; no case may take more than twice that test's slowest case.  (Run as the first GPU test of a process, a
+    case also pays the start-up of the runtime, about 0.4 s, as any first test does.)"""
+    from gnnpe_amd import binding
+    e = 2
+    g = sparse_hub_graph()
+    n, deg = g["n"], np.diff(g["offsets"].astype(np.int64))
+    assert deg[HUB] == SPARSE_HUB_DEG and (deg[SPARSE_CORE:] == 0).all()
+    vde = sparse_vde(oracle, g, e)
+    eng = open_engine(g, e)
+    assert eng.rows_held()[2] >= 1, "no hub row: the host would not slice"
+    qp = str(tmp_path / "star.graph")
+    _write_query(qp, 4, {(0, 1), (0, 2), (0, 3)}, [1, 0, 2, 1])
+    P = fields.path_index(g, l + 1).P
+    through = P[(P == HUB).any(axis=1)]
+    rng = np.random.default_rng(15)
+    picked = through[rng.choice(len(through), 3, replace=False)]
+    assert len(set(np.argmax(through == HUB, axis=1).tolist())) == l + 1  # the hub at every position: every anchor J walks its row
+    plans = [binding.host_query_plan_exact(qp, e, l), fields.make_plan(l, e, [fields._case(g, vde, r) for r in picked], [])]
+    row = nbrs_of(g, HUB)
+    isolated = np.arange(SPARSE_CORE, n)
+    if want_slices == 3:
+        T = np.concatenate([isolated[:(1 << 18) + 60], [HUB], row[::7], [5, 9]])
+    else:
+        T = np.concatenate([isolated, [HUB], row[::3], np.arange(0, SPARSE_CORE, 2)])
+    T = np.unique(T)
+    n_slices = min(64, max(1, (1 << 20) // len(T)))  # the host's rule for a list on a graph with hub rows
+    assert len(T) > 1 << 18 and n_slices == want_slices, (len(T), n_slices)
+    assert deg[HUB] > n_slices * 64, "no slice would take a second chunk"
+    assert HUB in T and np.isin(row, T).any() and not np.isin(row, T).all()
+    for k, plan in enumerate(plans):
+        nq = int(plan["n_vertices"])
+        want = np_support(g, vde, plan, T)
+        assert want[:, HUB].any() and want[:, row[n_slices * 64:]].any(), (l, k, "the yardstick has nothing behind the first chunks")
+        table, pat = pattern(nq, n)
+        eng.filter_support_delta(plan, T, +1, table)
+        got = to_np(table) - pat  # wrapping
+        assert np.array_equal(got, want), (l, k, n_slices, int((got != want).sum()), int(got.sum()), int(want.sum()))
+        eng.filter_support_delta(plan, T, -1, table)
+        assert np.array_equal(to_np(table), pat), (l, k, n_slices, "restored")
+    eng.close()
 
 
 # ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------
