@@ -121,6 +121,10 @@ SIGNATURES = {
                                              _f64p]),
     "gnnpe_filter_support_exact_delta": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double,
                                                    _u32p, C.c_uint64, C.c_int, _vp, _f64p]),
+    "gnnpe_filter_support_exact_delta_device": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _f64p, C.c_uint32, C.c_double,
+                                                          _vp, _vp, C.c_uint64, C.c_int, _vp, _f64p]),
+    "gnnpe_csr_closed_neighbourhood": (C.c_int, [_vp, _u32p, C.c_uint64, _vp, _vp, C.c_uint64, _u64p, _f64p]),
+    "gnnpe_csr_carry_vertex_set": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_uint64, _u64p, _f64p]),
     "gnnpe_filter_support_bitmap": (C.c_int, [_vp, C.c_uint32, _vp, _u32p, _f64p]),
     "gnnpe_filter_support_bitmap_device": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _f64p]),
     "gnnpe_build_index_device": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _vp, C.POINTER(_vp), _u64p,
@@ -163,6 +167,8 @@ ONLINE_SIGNATURES = {
     "gnnpe_standing_open_sets": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.c_uint64, _u32p, C.POINTER(_vp), _u64p, _f64p]),
     "gnnpe_standing_set_bitmap": (C.c_int, [_vp, _u32p]),
     "gnnpe_standing_apply_edges": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_standing_set_labels": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _f64p]),
+    "gnnpe_standing_apply_vertices": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u32p, _f64p]),
     "gnnpe_standing_result": (C.c_int, [_vp, _u64p]),
     "gnnpe_standing_rows": (C.c_int, [_vp, C.c_int, _u32p, C.c_uint64, _u64p]),
     "gnnpe_standing_set_sizes": (C.c_int, [_vp, _u64p]),
@@ -1369,6 +1375,50 @@ class Engine:
                                                            len(t), int(sign), _table_ptr(table), C.byref(ms)))
         return ms.value
 
+    def filter_support_delta_device(self, plan, bits, ids, n_ids, sign, table, eps=1e-6):
+        """gnnpe_filter_support_exact_delta_device: filter_support_delta with T taken from the device -- `bits` its bitmap
+        (ceil(n / 32) uint32) and `ids` its n_ids ascending ids, as closed_neighbourhood and carry_vertex_set leave them (torch
+        tensors, objects with data_ptr() or device addresses).  No sort, no upload of the list; for the same T the table's bytes
+        are those of filter_support_delta.  Returns the device ms."""
+        l, counts, v, lb, d, pde, nv = self._exact_plan_args(plan)
+        ms = C.c_double()
+        self._ck(self.lib.gnnpe_filter_support_exact_delta_device(self.ctx, l, counts, _ptr(v, _u32p), _ptr(lb, _u32p), _ptr(d, _u32p),
+                                                                  _ptr(pde, _f64p), nv, float(eps), _table_ptr(bits), _table_ptr(ids),
+                                                                  int(n_ids), int(sign), _table_ptr(table), C.byref(ms)))
+        return ms.value
+
+    def closed_neighbourhood(self, vertices, bits, ids, ids_cap=None, timing=False):
+        """gnnpe_csr_closed_neighbourhood: T = R u N(R) of the graph on the device for R = `vertices` (repeats tolerated), written
+        to the caller's device arrays `bits` (ceil(n / 32) uint32: every word, the bits at and above n zero) and `ids` (ascending,
+        room for ids_cap of them: by default the length of a torch tensor).  Returns |T|, with the device ms appended with
+        timing=True.  More than ids_cap vertices raise GnnpeError with the bitmap written; self.last_set_size holds |T| then."""
+        r = _vertex_ids(vertices)
+        return self._touched_call(lambda n, ms: self.lib.gnnpe_csr_closed_neighbourhood(
+            self.ctx, _ptr(r, _u32p) if len(r) else None, len(r), _table_ptr(bits), _table_ptr(ids) if ids is not None else None,
+            self._ids_cap(ids, ids_cap), n, ms), timing)
+
+    def carry_vertex_set(self, bits_old, bits_new, ids, with_added=False, ids_cap=None, timing=False):
+        """gnnpe_csr_carry_vertex_set: a vertex set of the graph before the last apply_vertices moved through its vertex map: bit
+        v' of bits_new (ceil(n' / 32) uint32) is set where the old id of v' is in bits_old and, with with_added, where v' was
+        added; `ids` receives the ascending ids.  Device arrays as closed_neighbourhood takes them; the same return value.
+        Without a valid vertex map the call raises GnnpeError and launches nothing."""
+        return self._touched_call(lambda n, ms: self.lib.gnnpe_csr_carry_vertex_set(
+            self.ctx, _table_ptr(bits_old), 1 if with_added else 0, _table_ptr(bits_new), _table_ptr(ids) if ids is not None else None,
+            self._ids_cap(ids, ids_cap), n, ms), timing)
+
+    @staticmethod
+    def _ids_cap(ids, ids_cap):
+        if ids_cap is not None:
+            return int(ids_cap)
+        return int(ids.numel()) if hasattr(ids, "numel") else 0
+
+    def _touched_call(self, call, timing):
+        n, ms = C.c_uint64(), C.c_double()
+        rc = call(C.byref(n), C.byref(ms) if timing else None)
+        self.last_set_size = int(n.value)
+        self._ck(rc)
+        return (int(n.value), ms.value) if timing else int(n.value)
+
     def support_bitmap(self, table, n_query_vertices):
         """gnnpe_filter_support_bitmap: (bitmap, device ms), bit v of row u set where table[u, v] != 0 -- the candidate sets of
         filter_candidates_exact on the graph the table is current for, in the layout every refinement call takes."""
@@ -1741,6 +1791,44 @@ class Engine:
             self.slab = (0, self.n)
             self.entries = self.rows_held()[1]
         return ms.value if timing else None
+
+    def standing_set_labels(self, vertices, labels, timing=False):
+        """gnnpe_standing_set_labels: set_vertex_labels that carries every open StandingQuery through the relabel (and runs
+        vde()): afterwards each handle reports the matches the new labels created and destroyed, its rows and the change lists of
+        its kept tables.  Pairs that change nothing are dropped; if none is left neither the graph nor its generation changes.  A
+        refused batch raises GnnpeError and changes nothing, neither the graph nor a handle.  Returns the device ms with timing."""
+        v, lab = _vertex_ids(vertices), _vertex_ids(labels)
+        if len(v) != len(lab):
+            raise GnnpeError("standing_set_labels: one label per vertex expected")
+        ms = C.c_double()
+        live = [sq for sq in self._standing if sq.handle]
+        gen = live[0].result()[5] if live else None  # (a stale handle is refused by the call below as well)
+        self._ck(load_online().gnnpe_standing_set_labels(self.ctx, _ptr(v, _u32p) if len(v) else None, _ptr(lab, _u32p) if len(v) else None,
+                                                         len(v), C.byref(ms) if timing else None))
+        # a batch of nothing but no-ops leaves graph and generation alone: the caller's device views stay valid
+        if len(v) and (gen is None or live[0].result()[5] != gen):
+            self._rows_gen += 1  # device views of the count tables are stale where a label changed
+            self.slab = (0, self.n)
+        return ms.value if timing else None
+
+    def standing_apply_vertices(self, remove=None, add_labels=None, timing=False):
+        """gnnpe_standing_apply_vertices: apply_vertices that carries every open StandingQuery through the batch (and runs vde()).
+        The destroyed rows are in the ids of the graph before, the created rows and the change lists in those of the graph after.
+        A refused batch (a StandingQuery opened with a bitmap is one reason) raises GnnpeError and changes nothing.  Returns
+        n_after, with the device ms appended with timing."""
+        rem, add = _vertex_ids([] if remove is None else remove), _vertex_ids([] if add_labels is None else add_labels)
+        n2, ms = C.c_uint32(), C.c_double()
+        self._map_call += 1
+        self._ck(load_online().gnnpe_standing_apply_vertices(self.ctx, _ptr(rem, _u32p) if len(rem) else None, len(rem),
+                                                             _ptr(add, _u32p) if len(add) else None, len(add), C.byref(n2),
+                                                             C.byref(ms) if timing else None))
+        if len(rem) or len(add):
+            self._rows_gen += 1
+            self.total = None
+        self.n = int(n2.value)
+        self.slab = (0, self.n)
+        self.entries = self.rows_held()[1]
+        return (self.n, ms.value) if timing else self.n
 
     def apply_edges_map(self, insert=None, delete=None, timing=False):
         """gnnpe_csr_apply_edges_map: apply_edges that also leaves the batch's entry map on the device.  Returns (entries_before,

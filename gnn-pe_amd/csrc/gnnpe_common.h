@@ -305,6 +305,9 @@ struct gnnpe_ctx {
     gnnpe::DevBuf q_dvcounts, q_decounts;  // ... the tables of gnnpe_refine_sets_delta_vertex_counts / _edge_counts called without dev_accum
     gnnpe::DevBuf q_nvcounts, q_necounts;  // ... the tables of gnnpe_refine_sets_delta_nonedges_vertex_counts / _edge_counts called without dev_accum
     gnnpe::DevBuf q_vvcounts, q_evcounts;  // ... the tables of gnnpe_refine_sets_delta_vertices_vertex_counts / _edge_counts called without dev_accum
+    // gnnpe_standing_set_labels / gnnpe_standing_apply_vertices (libgnnpe_online.so): the touched sets T and T' of a batch, each a bitmap
+    // and its ascending ids, for the larger of n and n'; in front of them the batch's ids and the labels gathered for them
+    gnnpe::DevBuf q_touched;
     gnnpe::DevBuf fold_tiles;  // gnnpe_table_fold (gnnpe_table_fold.hip): the changed cells per tile and their exclusive sums
     bool have_deg_all = false;
     bool vkey_valid = false;

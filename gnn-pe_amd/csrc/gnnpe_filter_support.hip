@@ -395,6 +395,31 @@ static int support_result(const char *who, hipError_t he)
     return GNNPE_ERR_HIP;
 }
 
+// The body of gnnpe_filter_support_exact_delta and gnnpe_filter_support_exact_delta_device after their checks and reserves: the
+// plan's upload, then table += sign * S_T with T as the bitmap d_tbits and the ascending ids d_ids.  With host_ids (the host-list call)
+// T is put on the device first, into the context's buffers the two pointers name: the upload, a zeroed bitmap, a bit per id.
+static int support_delta_run(const char *who, gnnpe_ctx *c, SupportPlan &P, const uint32_t *q_vids, const uint32_t *q_labels,
+                             const uint32_t *q_degrees, const double *q_pde, double eps, const uint32_t *host_ids, const uint32_t *d_tbits,
+                             const uint32_t *d_ids, uint32_t n_ids, int sign, void *dev_table, double *device_ms)
+{
+    SupportTimer timer;
+    hipError_t he = support_upload(c, &P, q_vids, q_labels, q_degrees, q_pde);
+    if (host_ids) {
+        const uint64_t words = ((uint64_t)c->n + 31) / 32;
+        if (he == hipSuccess) he = hipMemcpyAsync(const_cast<uint32_t *>(d_ids), host_ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, c->stream);
+        if (he == hipSuccess) he = timer.begin(device_ms != nullptr, c->stream);
+        if (he == hipSuccess) he = hipMemsetAsync(const_cast<uint32_t *>(d_tbits), 0, words * 4, c->stream);
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(k_support_set_scatter, dim3((n_ids + 255) / 256), dim3(256), 0, c->stream, n_ids, d_ids, const_cast<uint32_t *>(d_tbits));
+            he = hipGetLastError();
+        }
+    } else if (he == hipSuccess)
+        he = timer.begin(device_ms != nullptr, c->stream);
+    if (he == hipSuccess)
+        he = support_launches(c, P, n_ids, d_ids, d_tbits, true, eps, (uint64_t)(int64_t)sign, static_cast<unsigned long long *>(dev_table));
+    return support_result(who, timer.end(he, c->stream, device_ms));
+}
+
 }  // namespace gnnpe
 
 using namespace gnnpe;
@@ -445,18 +470,30 @@ int gnnpe_filter_support_exact_delta(gnnpe_ctx *c, uint32_t l, const uint32_t co
     GNNPE_HIP_TRY(hipSetDevice(c->device));
     if ((rc = c->q_plan.reserve(P.total * 12 + P.total * P.e * 8 + 64)) || (rc = c->q_work.reserve((words + n_ids) * 4))) return rc;
     uint32_t *d_tbits = c->q_work.as<uint32_t>(), *d_ids = d_tbits + words;
-    SupportTimer timer;
-    hipError_t he = support_upload(c, &P, q_vids, q_labels, q_degrees, q_pde);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_ids, ids.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, c->stream);
-    if (he == hipSuccess) he = timer.begin(device_ms != nullptr, c->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(d_tbits, 0, words * 4, c->stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(k_support_set_scatter, dim3((n_ids + 255) / 256), dim3(256), 0, c->stream, n_ids, d_ids, d_tbits);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess)
-        he = support_launches(c, P, n_ids, d_ids, d_tbits, true, epsilon, (uint64_t)(int64_t)sign, static_cast<unsigned long long *>(dev_table));
-    return support_result(who, timer.end(he, c->stream, device_ms));  // `ids` lives until the wait inside
+    // T from the host list: its upload, a zeroed bitmap and a bit per id; then the launches the device form makes
+    return support_delta_run(who, c, P, q_vids, q_labels, q_degrees, q_pde, epsilon, ids.data(), d_tbits, d_ids, n_ids, sign, dev_table,
+                             device_ms);  // `ids` lives until the wait inside
+}
+
+int gnnpe_filter_support_exact_delta_device(gnnpe_ctx *c, uint32_t l, const uint32_t counts[3], const uint32_t *q_vids,
+                                            const uint32_t *q_labels, const uint32_t *q_degrees, const double *q_pde,
+                                            uint32_t n_query_vertices, double epsilon, const void *dev_bits, const void *dev_ids,
+                                            uint64_t n_ids, int sign, void *dev_table, double *device_ms)
+{
+    const char *who = "gnnpe_filter_support_exact_delta_device";
+    SupportPlan P;
+    int rc = support_check(who, c, l, counts, q_vids, q_labels, q_degrees, q_pde, n_query_vertices, dev_table, &P);
+    if (rc) return rc;
+    GNNPE_REQUIRE(sign == 1 || sign == -1, GNNPE_ERR_ARG, "%s: sign = %d (+1 or -1)", who, sign);
+    GNNPE_REQUIRE(n_ids <= c->n, GNNPE_ERR_ARG, "%s: %llu ids, the graph has %u vertices", who, (unsigned long long)n_ids, c->n);
+    if (device_ms) *device_ms = 0.0;
+    if (n_ids == 0) return GNNPE_OK;  // nothing is launched, the table's bytes stay
+    GNNPE_REQUIRE(dev_bits && dev_ids && ((reinterpret_cast<uintptr_t>(dev_bits) | reinterpret_cast<uintptr_t>(dev_ids)) & 3u) == 0, GNNPE_ERR_ARG,
+                  "%s: dev_bits and dev_ids must be 4-byte aligned device pointers", who);
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    if ((rc = c->q_plan.reserve(P.total * 12 + P.total * P.e * 8 + 64))) return rc;
+    return support_delta_run(who, c, P, q_vids, q_labels, q_degrees, q_pde, epsilon, nullptr, static_cast<const uint32_t *>(dev_bits),
+                             static_cast<const uint32_t *>(dev_ids), (uint32_t)n_ids, sign, dev_table, device_ms);
 }
 
 int gnnpe_filter_support_bitmap(gnnpe_ctx *c, uint32_t n_query_vertices, const void *dev_table, uint32_t *host_bitmap, double *device_ms)

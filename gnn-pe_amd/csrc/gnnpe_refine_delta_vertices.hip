@@ -84,36 +84,43 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_vertices(SetsPlan P, ui
 
 using namespace gnnpe;
 
-extern "C" int gnnpe_refine_sets_delta_vertices(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
-                                                const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
-                                                uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+// The entry and its form on resident sets.  With `res` (gnnpe_standing.hip) neither the query file nor a host bitmap is read: the
+// kernels read res->d_bitmap, the rows stay in res->d_rows and res->rows_held says how many were written.
+static int refine_delta_vertices_run(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap, const uint32_t *vertices,
+                                     uint64_t n_vertices, uint64_t limit, uint32_t mode, uint64_t *answers, uint32_t *matches,
+                                     uint64_t matches_cap, double *device_ms, SetsResident *res = nullptr)
 {
     const char *who = "gnnpe_refine_sets_delta_vertices";
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && (vertices || n_vertices == 0), GNNPE_ERR_ARG, "%s: null argument",
-                  who);
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers && (vertices || n_vertices == 0), GNNPE_ERR_ARG,
+                  "%s: null argument", who);
     *answers = 0;
     if (device_ms) *device_ms = 0.0;
+    if (res) res->rows_held = 0;
     // the staging is vertices_plans / _reserve / _stage / _launches of the shared header; this entry's own are the rows
     VerticesPlans V;
-    int rc = vertices_plans(who, c, query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, &V);
+    int rc = vertices_plans(who, c, query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, &V, res);
     if (rc || V.nothing) return rc;  // limit 0, an empty set, no S, no vertex of S in any set: nothing is launched
     const uint32_t nq = V.Q.nq;
     const uint64_t words = V.Q.words;
     const std::vector<VerticesLaunch> &L = V.L;
-    if (!matches) matches_cap = 0;
+    if (res) matches_cap = res->rows_cap;
+    else if (!matches) matches_cap = 0;
     matches_cap = std::min(matches_cap, limit);
-    if ((rc = vertices_reserve(c, &V)) || (matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4)))) return rc;
+    if ((rc = vertices_reserve(c, &V, nullptr, nullptr, nullptr, nullptr, res)) ||
+        (!res && matches_cap && (rc = c->q_matches.reserve((size_t)matches_cap * nq * 4))))
+        return rc;
     SetsCounters *ctr = c->q_work.as<SetsCounters>();
-    uint32_t *d_rows = matches_cap ? c->q_matches.as<uint32_t>() : nullptr;
+    uint32_t *d_rows = !matches_cap ? nullptr : res ? res->d_rows : c->q_matches.as<uint32_t>();
+    const uint32_t *d_bitmap = res ? res->d_bitmap : c->q_bitmap.as<uint32_t>();
     SetsCall call(who, c, device_ms != nullptr);
-    vertices_stage(call, c, V, candidate_bitmap);
+    vertices_stage(call, c, V, candidate_bitmap, nullptr, 0, nullptr, nullptr, res);
     if (c->sw.debug)
         fprintf(stderr, "[refine_delta_vertices] vertices=%zu launches=%zu cands=%zu shift=%u hubs=%u pairs=%u nonedges=%u\n", V.ids.size(),
                 L.size(), V.cand_all.size(), L[0].w_shift, c->n_hub, L[0].K.n_pairs, L[0].K.n_non);
     vertices_launches(call, c, V, [&](size_t, const VerticesLaunch &l, uint32_t blocks, uint32_t *cand, uint32_t *item_off, auto... ord) {
         hipLaunchKernelGGL((k_refine_delta_vertices<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0, c->stream,
                            l.K.P, l.earlier, V.sbits, l.n_cand, cand, item_off, l.w_shift, c->adj_start.as<uint32_t>(),
-                           c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), words,
+                           c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), d_bitmap, words,
                            (unsigned long long)limit, ctr, d_rows, (unsigned long long)matches_cap, ord...);
     });
     call.wait(ctr, 16);
@@ -121,7 +128,25 @@ extern "C" int gnnpe_refine_sets_delta_vertices(gnnpe_ctx *c, const char *query_
         *answers = std::min<uint64_t>(c->h_pinned[0], limit);
         // every find reserved a row, so the first min(cursor, cap) rows are written
         const uint64_t n_rows = std::min<uint64_t>(c->h_pinned[1], matches_cap);
-        if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
+        if (res) res->rows_held = n_rows;
+        else if (n_rows) call.he = hipMemcpy(matches, d_rows, (size_t)n_rows * nq * 4, hipMemcpyDeviceToHost);
     }
     return call.finish(device_ms);
 }
+
+extern "C" int gnnpe_refine_sets_delta_vertices(gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                                const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode,
+                                                uint64_t *answers, uint32_t *matches, uint64_t matches_cap, double *device_ms)
+{
+    return refine_delta_vertices_run(c, query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, answers, matches, matches_cap,
+                                     device_ms);
+}
+
+// the same on resident sets, for gnnpe_standing.hip (declared there)
+namespace gnnpe {
+int refine_delta_vertices_resident(gnnpe_ctx *c, const uint32_t *vertices, uint64_t n_vertices, uint32_t mode, uint64_t *answers, SetsResident *res,
+                                   double *device_ms)
+{
+    return refine_delta_vertices_run(c, nullptr, nullptr, vertices, n_vertices, ~0ull, mode, answers, nullptr, 0, device_ms, res);
+}
+}  // namespace gnnpe

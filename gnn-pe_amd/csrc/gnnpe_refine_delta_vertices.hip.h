@@ -22,6 +22,28 @@ static __global__ void k_vset_scatter(uint32_t n_ids, const uint32_t *__restrict
     if (v < n) atomicOr(&sbits[v >> 5], 1u << (v & 31u));
 }
 
+// Which ids of a list are in which resident set: one lane per (query vertex u, id), the wave's 64 answers one __ballot.
+// out[u * chunks + c] = the ids c * 64 .. c * 64 + 63 of the list (every id < n) that are in row u of the bitmap.  grid: a wave per
+// (u, c), one writer per word.
+static __global__ __launch_bounds__(kBlock) void k_vset_member_of(uint32_t n_ids, const uint32_t *__restrict__ ids, uint32_t nq, uint64_t words,
+                                                                  const uint32_t *__restrict__ bitmap, unsigned long long *__restrict__ out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t chunks = ((uint64_t)n_ids + 63) / 64, items = chunks * nq;
+    uint64_t w = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (; w < items; w += nw) {  // wave-uniform: every lane reaches the __ballot
+        const uint64_t u = w / chunks, i = (w - u * chunks) * 64 + lane;
+        bool in = false;
+        if (i < n_ids) {
+            const uint32_t v = ids[i];
+            in = ((bitmap[u * words + (v >> 5)] >> (v & 31u)) & 1u) != 0;
+        }
+        const unsigned long long m = __ballot(in);
+        if (lane == 0) out[w] = m;
+    }
+}
+
 // the work buffer of a call: [counters 32 B | cand of every launch | item_off of every launch (n_cand + 1 each) | chunks, the same]
 struct VerticesWork {
     SetsCounters *ctr;
@@ -53,11 +75,36 @@ struct VerticesPlans {
     uint32_t *sbits = nullptr, *d_ids = nullptr;  // S on the device (vertices_reserve)
 };
 
-// sets_prepare, S as ascending ids -- an id the graph does not have is refused here, before anything is launched -- and the launches
-static inline int vertices_plans(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
-                                 const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode, VerticesPlans *V)
+// The resident form of "S n C(u)": the k ids of S go up, k_vset_member_of answers for every (u, id), and nq x ceil(k / 64) words
+// come back in one wait -- nothing proportional to n crosses.  The ids and the answers live in the context's q_delta, which
+// vertices_reserve sizes again afterwards (grow-only: the call's S lands where these ids were).
+static inline int vset_members_resident(gnnpe_ctx *c, const std::vector<uint32_t> &ids, uint32_t nq, uint64_t words, const uint32_t *d_bitmap,
+                                        std::vector<unsigned long long> *in_set)
 {
-    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &V->Q, &V->q);
+    const size_t k = ids.size(), chunks = (k + 63) / 64, ids_bytes = (k * 4 + 7) & ~(size_t)7;
+    in_set->assign(chunks * nq, 0ull);
+    if (!k) return GNNPE_OK;
+    int rc = c->q_delta.reserve(ids_bytes + chunks * nq * 8);
+    if (rc) return rc;
+    uint32_t *d_ids = c->q_delta.as<uint32_t>();
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->q_delta.as<char>() + ids_bytes);
+    GNNPE_HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), k * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_vset_member_of, dim3(grid_for((uint64_t)chunks * nq * 64)), dim3(kBlock), 0, c->stream, (uint32_t)k, d_ids, nq, words, d_bitmap,
+                       d_out);
+    GNNPE_HIP_TRY(hipGetLastError());
+    GNNPE_HIP_TRY(hipMemcpyAsync(in_set->data(), d_out, chunks * nq * 8, hipMemcpyDeviceToHost, c->stream));
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    return GNNPE_OK;
+}
+
+// sets_prepare, S as ascending ids -- an id the graph does not have is refused here, before anything is launched -- and the launches
+// With `res` (a standing query: the sets are on the device) S n C(u) comes from vset_members_resident and neither the file nor the
+// host bitmap is read.
+static inline int vertices_plans(const char *who, gnnpe_ctx *c, const char *query_graph_path, const uint32_t *candidate_bitmap,
+                                 const uint32_t *vertices, uint64_t n_vertices, uint64_t limit, uint32_t mode, VerticesPlans *V,
+                                 const SetsResident *res = nullptr)
+{
+    int rc = sets_prepare(who, c, query_graph_path, candidate_bitmap, mode, limit, &V->Q, &V->q, res);
     if (rc) return rc;
     std::string err;
     if (gnnpe_host::delta_vertex_ids(c->n, vertices, n_vertices, &V->ids, &err) != 0) {
@@ -69,10 +116,16 @@ static inline int vertices_plans(const char *who, gnnpe_ctx *c, const char *quer
     const uint32_t nq = V->Q.nq, n = c->n;
     const uint64_t words = V->Q.words;
     const bool distinct = (mode & GNNPE_MATCH_DISTINCT) != 0, induced = (mode & GNNPE_MATCH_INDUCED) != 0;
+    std::vector<unsigned long long> in_set;  // of a resident call: the answers of k_vset_member_of
+    const size_t chunks = (V->ids.size() + 63) / 64;
+    if (res && (rc = vset_members_resident(c, V->ids, nq, words, res->d_bitmap, &in_set))) return rc;
     for (uint32_t u = 0; u < nq; u++) {
         const size_t before = V->cand_all.size();
-        for (uint32_t s : V->ids)
-            if ((candidate_bitmap[(size_t)u * words + (s >> 5)] >> (s & 31u)) & 1u) V->cand_all.push_back(s);
+        for (size_t i = 0; i < V->ids.size(); i++) {
+            const uint32_t s = V->ids[i];
+            if (res ? (in_set[u * chunks + i / 64] >> (i & 63u)) & 1ull : (candidate_bitmap[(size_t)u * words + (s >> 5)] >> (s & 31u)) & 1u)
+                V->cand_all.push_back(s);
+        }
         if (V->cand_all.size() == before) continue;
         gnnpe_host::MatchOrder mo;
         if (gnnpe_host::build_match_order_from_vertex(V->q, u, &mo, &err) != 0) {
@@ -99,7 +152,7 @@ static inline int vertices_plans(const char *who, gnnpe_ctx *c, const char *quer
 // for the longest list -- all before the first launch (an entry reserves its rows or its table beside them)
 // (a cursor hands in its own buffers in the place of the context's q_work, q_bitmap, q_delta and q_tmp)
 static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V, DevBuf *work = nullptr, DevBuf *bm = nullptr, DevBuf *fset = nullptr,
-                                   DevBuf *tmp = nullptr)
+                                   DevBuf *tmp = nullptr, const SetsResident *res = nullptr)
 {
     DevBuf &b_work = work ? *work : c->q_work, &b_bm = bm ? *bm : c->q_bitmap, &b_set = fset ? *fset : c->q_delta, &b_tmp = tmp ? *tmp : c->q_tmp;
     const uint32_t nq = V->Q.nq;
@@ -111,7 +164,7 @@ static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V, DevBuf *work 
         tmp_bytes = std::max(tmp_bytes, tb);
     }
     int rc;
-    if ((rc = b_work.reserve(VerticesWork::bytes(V->cand_all.size(), V->L.size()))) || (rc = b_bm.reserve((size_t)nq * words * 4)) ||
+    if ((rc = b_work.reserve(VerticesWork::bytes(V->cand_all.size(), V->L.size()))) || (!res && (rc = b_bm.reserve((size_t)nq * words * 4))) ||
         (rc = b_set.reserve((words + V->ids.size()) * 4)) || (nq > 1 && (rc = b_tmp.reserve(tmp_bytes))))
         return rc;
     V->sbits = b_set.as<uint32_t>();
@@ -120,9 +173,9 @@ static inline int vertices_reserve(gnnpe_ctx *c, VerticesPlans *V, DevBuf *work 
 }
 
 // the uploads, the zeroed counters, the start of the timed span, then inside it the zeroing of `zero` (a context-owned table; may
-// be null) and S as a bitmap
+// be null) and S as a bitmap.  With `res` the sets are on the device already and no bitmap goes up.
 static inline void vertices_stage(SetsCall &call, gnnpe_ctx *c, const VerticesPlans &V, const uint32_t *candidate_bitmap, void *zero = nullptr,
-                                  size_t zero_bytes = 0, const DevBuf *work = nullptr, const DevBuf *bm = nullptr)
+                                  size_t zero_bytes = 0, const DevBuf *work = nullptr, const DevBuf *bm = nullptr, const SetsResident *res = nullptr)
 {
     const size_t n_cand_all = V.cand_all.size(), n_ids = V.ids.size();
     const uint64_t words = V.Q.words;
@@ -130,7 +183,7 @@ static inline void vertices_stage(SetsCall &call, gnnpe_ctx *c, const VerticesPl
     uint32_t *sbits = V.sbits, *d_ids = V.d_ids;
     if (call.ok()) call.he = hipMemcpyAsync(W.cand, V.cand_all.data(), n_cand_all * 4, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemcpyAsync(d_ids, V.ids.data(), n_ids * 4, hipMemcpyHostToDevice, c->stream);
-    if (call.ok()) call.he = hipMemcpyAsync((bm ? *bm : c->q_bitmap).p, candidate_bitmap, (size_t)V.Q.nq * words * 4, hipMemcpyHostToDevice, c->stream);
+    if (call.ok() && !res) call.he = hipMemcpyAsync((bm ? *bm : c->q_bitmap).p, candidate_bitmap, (size_t)V.Q.nq * words * 4, hipMemcpyHostToDevice, c->stream);
     if (call.ok()) call.he = hipMemsetAsync(W.ctr, 0, SetsWork::kCtrBytes, c->stream);
     if (call.ok() && call.ev0) call.he = hipEventRecord(call.ev0, c->stream);
     if (call.ok() && zero_bytes) call.he = hipMemsetAsync(zero, 0, zero_bytes, c->stream);  // once per call, before the first launch

@@ -187,9 +187,9 @@ __global__ __launch_bounds__(kBlock) void k_refine_delta_vertices_ecount(SetsPla
 static int vertices_counts_call(const char *who, const char *tag, bool edge_table, gnnpe_ctx *c, const char *query_graph_path,
                                 const uint32_t *candidate_bitmap, const uint32_t *vertices, uint64_t n_vertices, uint64_t limit,
                                 uint32_t mode, uint64_t *answers, int *complete, uint64_t *host_counts, void **dev_counts, void *dev_accum,
-                                int sign, double *device_ms)
+                                int sign, double *device_ms, const SetsResident *res = nullptr)
 {
-    GNNPE_REQUIRE(c && query_graph_path && candidate_bitmap && answers && complete && (vertices || n_vertices == 0), GNNPE_ERR_ARG,
+    GNNPE_REQUIRE(c && (res || (query_graph_path && candidate_bitmap)) && answers && complete && (vertices || n_vertices == 0), GNNPE_ERR_ARG,
                   "%s: null argument", who);
     *answers = 0;
     *complete = 0;
@@ -198,7 +198,7 @@ static int vertices_counts_call(const char *who, const char *tag, bool edge_tabl
     GNNPE_REQUIRE(sign == 1 || (sign == -1 && dev_accum), GNNPE_ERR_ARG, "%s: sign must be +1, or -1 with dev_accum (got %d)", who, sign);
     GNNPE_REQUIRE(!(dev_accum && host_counts), GNNPE_ERR_ARG, "%s: host_counts must be NULL with dev_accum", who);
     VerticesPlans V;
-    int rc = vertices_plans(who, c, query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, &V);
+    int rc = vertices_plans(who, c, query_graph_path, candidate_bitmap, vertices, n_vertices, limit, mode, &V, res);
     if (rc || limit == 0) return rc;  // limit 0: nothing is launched, and nothing is complete
     const uint32_t nq = V.Q.nq, n = c->n, nqe = (uint32_t)gnnpe_host::query_edges(V.q).size();
     const uint64_t entries = c->nbr_used;  // offsets[n] of gnnpe_load_csr
@@ -227,12 +227,13 @@ static int vertices_counts_call(const char *who, const char *tag, bool edge_tabl
         const uint32_t got = ecount_edges_from_plan(V.L[k].K.P, &X[k], &flips, &backflips);
         GNNPE_REQUIRE(got == nqe, GNNPE_ERR_ARG, "%s: the plan of launch %zu has %u query edges, the query %u", who, k, got, nqe);
     }
-    if ((rc = vertices_reserve(c, &V))) return rc;
+    if ((rc = vertices_reserve(c, &V, nullptr, nullptr, nullptr, nullptr, res))) return rc;
     SetsCounters *ctr = c->q_work.as<SetsCounters>();
     const unsigned long long one = sign == 1 ? 1ull : ~0ull;
     const uint64_t words = V.Q.words;
+    const uint32_t *d_bitmap = res ? res->d_bitmap : c->q_bitmap.as<uint32_t>();  // (a standing query's sets are on the device already)
     SetsCall call(who, c, device_ms != nullptr);
-    vertices_stage(call, c, V, candidate_bitmap, table, dev_accum ? 0 : table_bytes);
+    vertices_stage(call, c, V, candidate_bitmap, table, dev_accum ? 0 : table_bytes, nullptr, nullptr, res);
     if (c->sw.debug)
         fprintf(stderr, "[%s] vertices=%zu launches=%zu cands=%zu shift=%u hubs=%u pairs=%u nonedges=%u accum=%d sign=%d\n", tag, V.ids.size(),
                 V.L.size(), V.cand_all.size(), V.L[0].w_shift, c->n_hub, V.L[0].K.n_pairs, V.L[0].K.n_non, dev_accum != nullptr, sign);
@@ -241,12 +242,12 @@ static int vertices_counts_call(const char *who, const char *tag, bool edge_tabl
             hipLaunchKernelGGL((k_refine_delta_vertices_ecount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0,
                                c->stream, l.K.P, nq > 1 ? X[k] : EcountEdges{}, l.earlier, V.sbits, l.n_cand, cand, item_off, l.w_shift,
                                c->adj_start.as<uint32_t>(), c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(),
-                               c->q_bitmap.as<uint32_t>(), words, c->revpos.as<uint32_t>(), (unsigned long long)limit, ctr, table, entries, one,
+                               d_bitmap, words, c->revpos.as<uint32_t>(), (unsigned long long)limit, ctr, table, entries, one,
                                ord...);
         else
             hipLaunchKernelGGL((k_refine_delta_vertices_vcount<kSetsOrdered<decltype(ord)...>, decltype(ord)...>), dim3(blocks), dim3(kBlock), 0,
                                c->stream, l.K.P, l.earlier, V.sbits, l.n_cand, cand, item_off, l.w_shift, c->adj_start.as<uint32_t>(),
-                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), c->q_bitmap.as<uint32_t>(), words,
+                               c->adj_deg.as<uint32_t>(), c->nbrs.as<uint32_t>(), c->labels.as<uint32_t>(), d_bitmap, words,
                                (unsigned long long)limit, ctr, table, n, one, ord...);
     });
     call.wait(ctr, 16);
@@ -259,6 +260,16 @@ static int vertices_counts_call(const char *who, const char *tag, bool edge_tabl
         if (host_counts && *complete && table_bytes) call.he = hipMemcpy(host_counts, table, table_bytes, hipMemcpyDeviceToHost);
     }
     return call.finish(device_ms);
+}
+
+// the two on resident sets, for gnnpe_standing.hip (declared there): sign * (the table over S) added to the handle's scratch table
+int refine_delta_vertices_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *vertices, uint64_t n_vertices, uint32_t mode,
+                                          uint64_t *answers, const SetsResident *res, void *dev_accum, int sign, double *device_ms)
+{
+    int complete = 0;
+    return vertices_counts_call(edge_table ? "gnnpe_refine_sets_delta_vertices_edge_counts" : "gnnpe_refine_sets_delta_vertices_vertex_counts",
+                                edge_table ? "refine_delta_vertices_ecount" : "refine_delta_vertices_vcount", edge_table, c, nullptr, nullptr, vertices,
+                                n_vertices, ~0ull, mode, answers, &complete, nullptr, nullptr, dev_accum, sign, device_ms, res);
 }
 
 }  // namespace gnnpe

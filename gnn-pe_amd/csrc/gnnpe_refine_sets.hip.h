@@ -26,6 +26,7 @@
 #include "../host/refine_sets.h"
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_common.h"
+#include "gnnpe_touched.hip.h"
 
 namespace gnnpe {
 
@@ -504,10 +505,7 @@ struct SetsResident {
     uint64_t rows_held = 0;  // out
 };
 
-// k_sets_members of gnnpe_standing.hip on the stream: the ascending ids below n of the `words`-word bitmap row d_row into d_out (at
-// most cap of them), their number into *d_total if that is given.  Waits for nothing.
-hipError_t sets_members_launch(hipStream_t stream, const uint32_t *d_row, uint64_t words, uint32_t n, uint32_t *d_out, uint64_t cap,
-                               unsigned long long *d_total);
+// (sets_members_launch, which writes the start candidates of a resident row: gnnpe_touched.hip.h)
 
 // Everything between a call's own argument checks and the device: the state of the context, the query graph, the set sizes and the
 // matching order -- a disconnected query is refused whatever the limit -- then the plan, the pairs and the start candidates.

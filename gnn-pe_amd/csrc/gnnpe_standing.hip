@@ -15,13 +15,9 @@
 //     sets_stage_items and delta_stage that says "the sets are already on the device".
 //
 // k_sets_sizes: one workgroup per bitmap row, lanes over the words, __popc, a DPP wave sum and four LDS words.
-// k_sets_members: an ORDERED stream compaction, no atomics, so that the ids come out ascending as gnnpe_host::set_members gives
-//   them.  One workgroup walks the row tile by tile (kMembersTile words = 8192 vertices): a lane's word, its popcount, the
-//   inclusive DPP scan of the wave (wave_scan_add of gnnpe_dpp.hip.h), the four wave totals through LDS, and the lane expands its
-//   word into the tile's ids in LDS at its exclusive offset; then the workgroup stores the tile's ids to carry + i with consecutive
-//   lanes on consecutive words (the expansion's scattered stores stay in LDS), and the carry moves on by the tile's total.  The last
-//   word of the row is masked to the bits below n.  One workgroup is enough for what calls it: the start candidates of a full count
-//   at open and refresh, and gnnpe_standing_set_members; no batch runs it.
+// k_sets_members (csrc/gnnpe_touched.hip, libgnnpe_hip.so, since the touched sets of a relabel or a vertex batch end with it too): the
+//   ordered compaction of a bitmap row into ascending ids, one workgroup.  Here it writes the start candidates of a full count at
+//   open and refresh, and gnnpe_standing_set_members.
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) and the measurement: profiles/online_standing.txt.
 //
 // COUNT TABLES (gnnpe_standing_keep_counts): a handle can keep V (nq x n) and E (query edges x entries) exact across the batches.
@@ -34,20 +30,12 @@
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_dpp.hip.h"
 #include "gnnpe_refine_delta.hip.h"
+#include "gnnpe_touched.hip.h"
 
 #include <iterator>
 #include <memory>
 
 namespace gnnpe {
-
-constexpr uint32_t kMembersTile = kBlock;  // words of a row per step of k_sets_members: one per lane
-
-// the bits of word w of a row that stand for vertices below n
-__device__ __forceinline__ uint32_t sets_word_below_n(uint32_t x, uint64_t w, uint64_t words, uint32_t n)
-{
-    const uint32_t tail = n & 31u;
-    return tail && w == words - 1 ? x & ((1u << tail) - 1u) : x;
-}
 
 // sizes[u] = the set bits below n of row u; grid = nq workgroups
 static __global__ __launch_bounds__(kBlock) void k_sets_sizes(const uint32_t *__restrict__ bitmap, uint64_t words, uint32_t n,
@@ -67,48 +55,6 @@ static __global__ __launch_bounds__(kBlock) void k_sets_sizes(const uint32_t *__
     }
 }
 
-// out[0 .. min(cap, k)) = the first ids of the k set bits below n of `row`, ascending; *total = k (total may be null: the walk then
-// ends with the tile that fills cap).  One workgroup of kBlock lanes.
-static __global__ __launch_bounds__(kBlock) void k_sets_members(const uint32_t *__restrict__ row, uint64_t words, uint32_t n,
-                                                                uint32_t *__restrict__ out, uint64_t cap, unsigned long long *__restrict__ total)
-{
-    __shared__ uint32_t s_ids[kMembersTile * 32];  // the ids of one tile: 32 KiB
-    __shared__ uint32_t s_wave[kBlock / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    uint64_t carry = 0;  // ids of the tiles before this one
-    for (uint64_t w0 = 0; w0 < words; w0 += kMembersTile) {
-        if (!total && carry >= cap) break;  // (uniform)
-        const uint64_t w = w0 + t;
-        uint32_t x = w < words ? sets_word_below_n(row[w], w, words, n) : 0u;
-        const uint32_t c = (uint32_t)__popc(x);
-        const uint32_t incl = wave_scan_add(c);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, tile_total = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < kBlock / 64; i++) {
-            const uint32_t v = s_wave[i];
-            before += i < wave ? v : 0u;
-            tile_total += v;
-        }
-        uint32_t o = before + incl - c;  // at most kMembersTile * 32 - c: the expansion stays inside s_ids
-        for (; x; x &= x - 1u) s_ids[o++] = (uint32_t)(w * 32u) + (uint32_t)__ffs((int)x) - 1u;
-        __syncthreads();
-        for (uint32_t i = t; i < tile_total; i += kBlock)
-            if (carry + i < cap) out[carry + i] = s_ids[i];
-        carry += tile_total;
-        __syncthreads();  // s_wave and s_ids are written again in the next step
-    }
-    if (t == 0 && total) *total = carry;
-}
-
-hipError_t sets_members_launch(hipStream_t stream, const uint32_t *d_row, uint64_t words, uint32_t n, uint32_t *d_out, uint64_t cap,
-                               unsigned long long *d_total)
-{
-    hipLaunchKernelGGL(k_sets_members, dim3(1), dim3(kBlock), 0, stream, d_row, words, n, d_out, cap, d_total);
-    return hipGetLastError();
-}
-
 // gnnpe_refine_sets.hip, gnnpe_refine_delta.hip, gnnpe_refine_delta_nonedges.hip: the three searches on resident sets, limit 2^64 - 1
 int refine_sets_resident(gnnpe_ctx *c, uint32_t mode, uint64_t limit, uint64_t *answers, SetsResident *res, double *device_ms);
 int refine_delta_resident(gnnpe_ctx *c, const uint32_t *edges, uint64_t n_edges, uint32_t mode, uint64_t *answers, SetsResident *res,
@@ -124,6 +70,20 @@ int refine_delta_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *
                                  const SetsResident *res, void *dev_accum, int sign, double *device_ms);
 int refine_delta_nonedges_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *pairs, uint64_t n_pairs, uint32_t mode,
                                           uint64_t *answers, const SetsResident *res, void *dev_accum, int sign, double *device_ms);
+
+// gnnpe_refine_delta_vertices.hip, gnnpe_refine_delta_vertices_counts.hip: the search anchored at a set of data vertices and its two
+// tables on resident sets -- S n C(u) by k_vset_member_of, no walk over C on the host
+int refine_delta_vertices_resident(gnnpe_ctx *c, const uint32_t *vertices, uint64_t n_vertices, uint32_t mode, uint64_t *answers, SetsResident *res,
+                                   double *device_ms);
+int refine_delta_vertices_counts_resident(gnnpe_ctx *c, bool edge_table, const uint32_t *vertices, uint64_t n_vertices, uint32_t mode,
+                                          uint64_t *answers, const SetsResident *res, void *dev_accum, int sign, double *device_ms);
+
+// labels[i] = table[ids[i]]: the labels a relabel batch would replace (gnnpe_standing_set_labels)
+static __global__ void k_standing_gather(uint32_t count, const uint32_t *__restrict__ ids, const uint32_t *__restrict__ table, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = table[ids[i]];
+}
 
 // A count table a handle keeps (gnnpe_standing_keep_counts): T, the scratch table D the delta count kernels of a batch add into and
 // gnnpe_table_fold empties, for the per-entry table the spare of the out-of-place carry, and the change list of the last batch.
@@ -168,6 +128,7 @@ struct gnnpe_standing {
     uint32_t n = 0;      // the graph's vertices the buffers are sized for
     uint64_t words = 0;
     DevBuf table, bitmap, d_sizes, members;
+    DevBuf table_spare;  // of the out-of-place carry of S through a vertex map: reserved at the first vertex batch
     DevBuf rows[2][2];  // [0 created, 1 destroyed][the kept rows, the batch being applied]
     int cur = 0;        // which of the two holds the kept rows
     uint64_t rows_cap = 0;
@@ -386,10 +347,13 @@ int standing_open(const char *who, gnnpe_ctx *c, const char *query_graph_path, u
 // A handle that keeps count tables runs the table kernels of the same search with its scratch tables as dev_accum: sign -1 for what
 // the step destroys (which == 1), +1 for what it creates.  Their answers are the search's, so with rows_cap == 0 the row search is
 // left out and no match is searched twice; with rows it runs as well, and must agree.
-int standing_delta(gnnpe_standing *h, bool nonedges, const std::vector<uint32_t> &edges, int which, uint64_t *sum, double *ms)
+// `items`: the pairs of the delta search (two words each), or with `vertices` the data vertices the search DeltaV is anchored at
+// (gnnpe_standing_set_labels, gnnpe_standing_apply_vertices).  `who`: the entry the step belongs to, for its messages.
+int standing_delta(const char *who, gnnpe_standing *h, bool nonedges, const std::vector<uint32_t> &items, int which, uint64_t *sum, double *ms,
+                   bool vertices = false)
 {
-    if (edges.empty()) return GNNPE_OK;
-    const char *who = "gnnpe_standing_apply_edges";
+    if (items.empty()) return GNNPE_OK;
+    const uint64_t n_items = vertices ? items.size() : items.size() / 2;
     uint64_t found = 0;
     bool have = false;
     for (int t = 0; t < 2; t++) {
@@ -397,8 +361,10 @@ int standing_delta(gnnpe_standing *h, bool nonedges, const std::vector<uint32_t>
         const SetsResident R = standing_sets(h);
         uint64_t got = 0;
         double ms1 = 0.0;
-        const int rc = (nonedges ? refine_delta_nonedges_counts_resident : refine_delta_counts_resident)(
-            h->c, t == 1, edges.data(), edges.size() / 2, h->mode, &got, &R, h->kc[t].delta.p, which == 1 ? -1 : 1, ms ? &ms1 : nullptr);
+        const int rc = (vertices   ? refine_delta_vertices_counts_resident
+                        : nonedges ? refine_delta_nonedges_counts_resident
+                                   : refine_delta_counts_resident)(h->c, t == 1, items.data(), n_items, h->mode, &got, &R,
+                                                                   h->kc[t].delta.p, which == 1 ? -1 : 1, ms ? &ms1 : nullptr);
         if (rc) return rc;
         if (ms) *ms += ms1;
         GNNPE_REQUIRE(!have || got == found, GNNPE_ERR_HIP, "%s: internal error: the two table searches found %llu and %llu matches", who,
@@ -415,8 +381,10 @@ int standing_delta(gnnpe_standing *h, bool nonedges, const std::vector<uint32_t>
         }
         uint64_t rows_found = 0;
         double ms1 = 0.0;
-        const int rc = (nonedges ? refine_delta_nonedges_resident : refine_delta_resident)(h->c, edges.data(), edges.size() / 2, h->mode, &rows_found,
-                                                                                          &R, ms ? &ms1 : nullptr);
+        const int rc = (vertices   ? refine_delta_vertices_resident
+                        : nonedges ? refine_delta_nonedges_resident
+                                   : refine_delta_resident)(h->c, items.data(), n_items, h->mode, &rows_found, &R,
+                                                            ms ? &ms1 : nullptr);
         if (rc) return rc;
         if (ms) *ms += ms1;
         GNNPE_REQUIRE(!have || rows_found == found, GNNPE_ERR_HIP, "%s: internal error: the row search found %llu matches, the table search %llu",
@@ -449,6 +417,7 @@ int standing_zero_deltas(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H)
 int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const std::vector<uint32_t> &I, const std::vector<uint32_t> &D, bool *swapped,
                   double *ms, bool want_map)
 {
+    const char *who = "gnnpe_standing_apply_edges";
     *swapped = false;
     std::vector<uint32_t> T(I);  // the end vertices of the step, each once
     T.insert(T.end(), D.begin(), D.end());
@@ -460,8 +429,8 @@ int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const st
         if (H[i]->filter && !(rc = standing_support_delta(H[i], T, -1, ms))) reduced.push_back(H[i]);
     for (size_t i = 0; i < H.size() && !rc; i++) {
         gnnpe_standing *h = H[i];
-        rc = standing_delta(h, false, D, 1, &h->p_destroyed, ms);
-        if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(h, true, I, 1, &h->p_destroyed, ms);
+        rc = standing_delta(who, h, false, D, 1, &h->p_destroyed, ms);
+        if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(who, h, true, I, 1, &h->p_destroyed, ms);
     }
     double ms1 = 0.0;
     void *map = nullptr;
@@ -493,8 +462,8 @@ int standing_step(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const st
         if (H[i]->filter && !(rc = standing_support_delta(H[i], T, +1, ms))) rc = standing_derive(H[i], ms);
     for (size_t i = 0; i < H.size() && !rc; i++) {
         gnnpe_standing *h = H[i];
-        rc = standing_delta(h, false, I, 0, &h->p_created, ms);
-        if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(h, true, D, 0, &h->p_created, ms);
+        rc = standing_delta(who, h, false, I, 0, &h->p_created, ms);
+        if (!rc && (h->mode & GNNPE_MATCH_INDUCED)) rc = standing_delta(who, h, true, D, 0, &h->p_created, ms);
     }
     return rc;
 }
@@ -570,9 +539,322 @@ int standing_check_batch(const char *who, gnnpe_ctx *c, const std::vector<uint32
     return GNNPE_OK;
 }
 
+
+// ---- relabels and vertex batches through the handle ---------------------------------------------------------------------------
+
+// The touched sets of a batch in c->q_touched, sized for `room` vertices (the larger of n and n'):
+//   [ids of the batch, room words | their gathered labels, room words | T: bits, ids | T': bits, ids]
+struct StandingTouched {
+    uint32_t *batch = nullptr, *gathered = nullptr, *bits[2] = {nullptr, nullptr}, *ids[2] = {nullptr, nullptr};
+    uint64_t n_ids[2] = {0, 0}, room = 0;
+};
+
+int standing_touched_reserve(gnnpe_ctx *c, uint64_t room, StandingTouched *T)
+{
+    const uint64_t words = (room + 31) / 32;
+    const int rc = c->q_touched.reserve((2 * room + 2 * (words + room)) * 4 + 8);
+    if (rc) return rc;
+    T->room = room;
+    T->batch = c->q_touched.as<uint32_t>();
+    T->gathered = T->batch + room;
+    T->bits[0] = T->gathered + room, T->ids[0] = T->bits[0] + words;
+    T->bits[1] = T->ids[0] + room, T->ids[1] = T->bits[1] + words;
+    return GNNPE_OK;
+}
+
+// S += sign * S_T of the handle, T from the device (set `w` of StandingTouched): no host list, no sort, no upload
+int standing_support_delta_device(gnnpe_standing *h, const StandingTouched &T, int w, int sign, double *ms)
+{
+    double ms1 = 0.0;
+    const int rc = gnnpe_filter_support_exact_delta_device(h->c, h->l, h->counts, h->qv, h->ql, h->qd, h->qp, h->nq, h->eps, T.bits[w], T.ids[w],
+                                                           T.n_ids[w], sign, h->table.p, ms ? &ms1 : nullptr);
+    if (ms) *ms += ms1;
+    return rc;
+}
+
+// room for `need` bytes in a buffer whose first `used` bytes must survive: a larger one is made aside and takes them over
+int standing_grow_keep(gnnpe_ctx *c, DevBuf &b, size_t need, size_t used)
+{
+    if (need <= b.bytes) return GNNPE_OK;
+    DevBuf fresh;
+    const int rc = fresh.reserve(need);
+    if (rc) return rc;
+    if (used) GNNPE_HIP_TRY(hipMemcpyAsync(fresh.p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
+    GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+    StandingCounts::swap(b, fresh);
+    return GNNPE_OK;
+}
+
+// Before a vertex batch changes anything: S, its spare, C, and T, D and the spare of every kept table get room for `n_max` vertices
+// (the entries only shrink), so that nothing is allocated behind the swap.  The spares are made here, at the first vertex batch:
+// a handle that only sees edge batches never owns them.  A refusal leaves every table intact (a scratch table without its zeros
+// poisons the handle, as in standing_size_edge_tables).
+int standing_size_for_vertices(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, uint64_t n_max)
+{
+    for (gnnpe_standing *h : H) {
+        const size_t s_need = std::max<uint64_t>((uint64_t)h->nq * n_max * 8, 8), c_need = std::max<uint64_t>((uint64_t)h->nq * ((n_max + 31) / 32) * 4, 4);
+        int rc;
+        if ((rc = h->table_spare.reserve(s_need)) || (rc = standing_grow_keep(c, h->table, s_need, (size_t)h->nq * h->n * 8)) ||
+            (rc = standing_grow_keep(c, h->bitmap, c_need, (size_t)h->nq * h->words * 4)))
+            return rc;
+        for (int t = 0; t < 2; t++) {
+            StandingCounts &K = h->kc[t];
+            if (!K.kept) continue;
+            const size_t need = std::max<uint64_t>(K.rows * (t == 1 ? K.cols : n_max) * 8, 8);
+            if ((rc = K.spare.reserve(need)) || (rc = standing_grow_keep(c, K.table, need, K.cells() * 8))) return rc;
+            if (K.delta.bytes < need) {
+                if ((rc = K.delta.reserve(need))) {
+                    h->graph_gen = kStandingPoison;
+                    return rc;
+                }
+                GNNPE_HIP_TRY(hipMemsetAsync(K.delta.p, 0, need, c->stream));
+            }
+        }
+    }
+    return GNNPE_OK;
+}
+
+// after a refusal before the swap: S is put back on the unchanged graph, the scratch tables lose what the searches subtracted (the
+// message of the failure is kept)
+void standing_roll_back(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, const std::vector<gnnpe_standing *> &reduced, const StandingTouched &T)
+{
+    const std::string why = gnnpe_last_error();
+    for (gnnpe_standing *h : reduced)
+        if (standing_support_delta_device(h, T, 0, +1, nullptr)) h->graph_gen = kStandingPoison;
+    if (standing_zero_deltas(c, H))
+        for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
+    set_error("%s", why.c_str());
+}
+
+// one gnnpe_table_fold per kept table: D into T, D = 0, the batch's change list in the cells of G'
+int standing_fold_all(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, double *device_ms)
+{
+    int rc = GNNPE_OK;
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        for (StandingCounts &K : H[i]->kc) {
+            if (!K.kept || rc) continue;
+            double ms1 = 0.0;
+            rc = gnnpe_table_fold(c, K.table.p, K.delta.p, K.cells(), K.ch_cells.p, K.ch_deltas.p, H[i]->changes_cap, &K.n_changes,
+                                  device_ms ? &ms1 : nullptr);
+            if (device_ms) *device_ms += ms1;
+        }
+    return rc;
+}
+
+// what a batch leaves in every handle once all of them got through (`moved`: the graph changed, the kept rows are the batch's)
+void standing_commit(gnnpe_ctx *c, const std::vector<gnnpe_standing *> &H, bool moved)
+{
+    for (gnnpe_standing *h : H) {
+        if (!moved) h->kc[0].n_changes = h->kc[1].n_changes = 0;  // the empty batch changes no cell
+        h->created = h->p_created;
+        h->destroyed = h->p_destroyed;
+        h->count += h->p_created - h->p_destroyed;
+        h->held[0] = h->p_held[0];
+        h->held[1] = h->p_held[1];
+        if (moved) h->cur ^= 1;
+        h->graph_gen = c->graph_gen;
+    }
+}
+
+// the live handles of the context, in a call's first lines
+int standing_handles(const char *who, gnnpe_ctx *c, std::vector<gnnpe_standing *> *H)
+{
+    for (void *p : c->standing) {
+        H->push_back(static_cast<gnnpe_standing *>(p));
+        STANDING_LIVE(who, H->back());
+    }
+    return GNNPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gnnpe_standing_set_labels(gnnpe_ctx *c, const uint32_t *vertices, const uint32_t *labels, uint64_t count, double *device_ms)
+{
+    const char *who = "gnnpe_standing_set_labels";
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c && ((vertices && labels) || count == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    int rc = standing_whole_graph(who, c);
+    if (rc) return rc;
+    std::vector<gnnpe_standing *> H;
+    if ((rc = standing_handles(who, c, &H))) return rc;
+    if (H.empty()) {  // a context without a handle gets the plain relabel (and gnnpe_vde): no gather, no touched set
+        if ((rc = gnnpe_set_vertex_labels(c, vertices, labels, count, device_ms))) return rc;
+        return count && c->have_table ? gnnpe_vde(c, nullptr, nullptr, nullptr) : GNNPE_OK;
+    }
+    bool filter = false;
+    for (gnnpe_standing *h : H) filter = filter || h->filter;
+    const uint32_t n = c->n;
+    // every (vertex, label) pair once, as gnnpe_set_vertex_labels reads the lists; a label without a row in the table would fail
+    // gnnpe_vde behind the change
+    std::vector<uint64_t> pairs(count);
+    for (uint64_t i = 0; i < count; i++) {
+        GNNPE_REQUIRE(vertices[i] < n, GNNPE_ERR_ARG, "%s: vertex %u is not a vertex of the graph (n = %u)", who, vertices[i], n);
+        GNNPE_REQUIRE(!(filter && c->have_table) || labels[i] < c->n_labels, GNNPE_ERR_ARG, "%s: label %u of vertex %u has no row in the %u-row label table",
+                      who, labels[i], vertices[i], c->n_labels);
+        pairs[i] = ((uint64_t)vertices[i] << 32) | labels[i];
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    const size_t k = pairs.size();
+    for (size_t i = 1; i < k; i++)
+        GNNPE_REQUIRE((uint32_t)(pairs[i] >> 32) != (uint32_t)(pairs[i - 1] >> 32), GNNPE_ERR_ARG, "%s: vertex %u is listed with the labels %u and %u", who,
+                      (uint32_t)(pairs[i] >> 32), (uint32_t)pairs[i - 1], (uint32_t)pairs[i]);
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    StandingTouched T;
+    if ((rc = standing_touched_reserve(c, n, &T))) return rc;
+    // R*: the pairs that change a label -- one gather of 4 k bytes says which
+    std::vector<uint32_t> R, L;
+    if (k) {
+        std::vector<uint32_t> ids(k), now(k);
+        for (size_t i = 0; i < k; i++) ids[i] = (uint32_t)(pairs[i] >> 32);
+        GNNPE_HIP_TRY(hipMemcpyAsync(T.batch, ids.data(), k * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_standing_gather, dim3((uint32_t)((k + 255) / 256)), dim3(256), 0, c->stream, (uint32_t)k, T.batch, c->labels.as<uint32_t>(),
+                           T.gathered);
+        GNNPE_HIP_TRY(hipGetLastError());
+        GNNPE_HIP_TRY(hipMemcpyAsync(now.data(), T.gathered, k * 4, hipMemcpyDeviceToHost, c->stream));
+        GNNPE_HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < k; i++)
+            if (now[i] != (uint32_t)pairs[i]) R.push_back(ids[i]), L.push_back((uint32_t)pairs[i]);
+    }
+    for (gnnpe_standing *h : H) h->p_created = h->p_destroyed = h->p_held[0] = h->p_held[1] = 0;
+    if (R.empty()) {  // nothing changes: neither the graph nor its generation
+        standing_commit(c, H, false);
+        return GNNPE_OK;
+    }
+    double ms1 = 0.0;
+    // T = R* u N(R*), once for every handle: the label of R* and the vde of its neighbours change
+    if ((rc = gnnpe_csr_closed_neighbourhood(c, R.data(), R.size(), T.bits[0], T.ids[0], T.room, &T.n_ids[0], device_ms ? &ms1 : nullptr))) return rc;
+    if (device_ms) *device_ms += ms1;
+    std::vector<gnnpe_standing *> reduced;  // the handles whose S has lost S_T(G)
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        if (H[i]->filter && !(rc = standing_support_delta_device(H[i], T, 0, -1, device_ms))) reduced.push_back(H[i]);
+    for (size_t i = 0; i < H.size() && !rc; i++) rc = standing_delta(who, H[i], false, R, 1, &H[i]->p_destroyed, device_ms, true);
+    if (!rc) rc = gnnpe_set_vertex_labels(c, R.data(), L.data(), R.size(), device_ms ? &ms1 : nullptr);
+    if (rc) {  // nothing of the context has changed
+        standing_roll_back(c, H, reduced, T);
+        return rc;
+    }
+    if (device_ms) *device_ms += ms1;
+    // behind the change: a failure leaves the graph moved on and the handles not
+    if (c->have_table) rc = gnnpe_vde(c, nullptr, nullptr, nullptr);
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        if (H[i]->filter && !(rc = standing_support_delta_device(H[i], T, 0, +1, device_ms))) rc = standing_derive(H[i], device_ms);
+    for (size_t i = 0; i < H.size() && !rc; i++) rc = standing_delta(who, H[i], false, R, 0, &H[i]->p_created, device_ms, true);
+    if (!rc) rc = standing_fold_all(c, H, device_ms);
+    if (rc) {
+        for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
+        return rc;
+    }
+    standing_commit(c, H, true);
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_apply_vertices(gnnpe_ctx *c, const uint32_t *remove, uint64_t n_remove, const uint32_t *add_labels, uint64_t n_add,
+                                  uint32_t *n_after, double *device_ms)
+{
+    const char *who = "gnnpe_standing_apply_vertices";
+    if (device_ms) *device_ms = 0.0;
+    GNNPE_REQUIRE(c && (remove || n_remove == 0) && (add_labels || n_add == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    if (n_after) *n_after = c->n;
+    int rc = standing_whole_graph(who, c);
+    if (rc) return rc;
+    std::vector<gnnpe_standing *> H;
+    if ((rc = standing_handles(who, c, &H))) return rc;
+    if (H.empty()) {  // a context without a handle gets the plain apply (and gnnpe_vde): no touched set, no carry
+        const uint64_t gen = c->graph_gen;
+        if ((rc = gnnpe_csr_apply_vertices(c, remove, n_remove, add_labels, n_add, n_after, nullptr, nullptr, nullptr, nullptr, device_ms))) return rc;
+        return c->graph_gen != gen && c->have_table ? gnnpe_vde(c, nullptr, nullptr, nullptr) : GNNPE_OK;
+    }
+    bool want_map = false;  // a handle on the context keeps E: the apply hands out the entry map
+    for (gnnpe_standing *h : H) {
+        GNNPE_REQUIRE(h->filter, GNNPE_ERR_UNSUPPORTED,
+                      "%s: a gnnpe_standing_open_sets handle is open on the context: its bitmap was made for %u vertices (close it first)", who, h->n);
+        want_map = want_map || h->kc[1].kept;
+    }
+    // gnnpe_csr_apply_vertices' own refusals, decided here because S changes before the apply is asked
+    const uint32_t n = c->n;
+    std::vector<uint32_t> R(remove, remove + n_remove);
+    for (uint32_t v : R) GNNPE_REQUIRE(v < n, GNNPE_ERR_ARG, "%s: vertex %u is not a vertex of the graph (n = %u)", who, v, n);
+    std::sort(R.begin(), R.end());
+    R.erase(std::unique(R.begin(), R.end()), R.end());
+    const uint32_t n_surv = n - (uint32_t)R.size();
+    GNNPE_REQUIRE(n_add < 0xFFFFFFFFull, GNNPE_ERR_RANGE, "%s: %llu added vertices exceed 32-bit ids", who, (unsigned long long)n_add);
+    const uint64_t n2_64 = (uint64_t)n_surv + n_add;
+    GNNPE_REQUIRE(n2_64 != 0, GNNPE_ERR_ARG, "%s: the batch leaves no vertex", who);
+    GNNPE_REQUIRE(n2_64 < 0xFFFFFFFFull, GNNPE_ERR_RANGE, "%s: %llu vertices exceed 32-bit ids", who, (unsigned long long)n2_64);
+    for (uint64_t i = 0; i < n_add && !H.empty() && c->have_table; i++)
+        GNNPE_REQUIRE(add_labels[i] < c->n_labels, GNNPE_ERR_ARG, "%s: label %u of added vertex %llu has no row in the %u-row label table", who,
+                      add_labels[i], (unsigned long long)i, c->n_labels);
+    const uint32_t n2 = (uint32_t)n2_64;
+    for (gnnpe_standing *h : H) h->p_created = h->p_destroyed = h->p_held[0] = h->p_held[1] = 0;
+    if (R.empty() && n_add == 0) {  // the empty batch: neither the graph nor its generation changes
+        standing_commit(c, H, false);
+        return GNNPE_OK;
+    }
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    StandingTouched T;
+    const uint64_t n_max = std::max(n, n2);
+    if ((rc = standing_touched_reserve(c, n_max, &T)) || (rc = standing_size_for_vertices(c, H, n_max))) return rc;
+    double ms1 = 0.0;
+    // T = R u N_G(R): what the removal takes from the paths of S (an empty R gives the empty set, which T' starts from)
+    if ((rc = gnnpe_csr_closed_neighbourhood(c, R.data(), R.size(), T.bits[0], T.ids[0], T.room, &T.n_ids[0], device_ms ? &ms1 : nullptr))) return rc;
+    if (device_ms) *device_ms += ms1;
+    std::vector<gnnpe_standing *> reduced;
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        if (!(rc = standing_support_delta_device(H[i], T, 0, -1, device_ms))) reduced.push_back(H[i]);
+    for (size_t i = 0; i < H.size() && !rc; i++) rc = standing_delta(who, H[i], false, R, 1, &H[i]->p_destroyed, device_ms, true);
+    void *vmap = nullptr, *emap = nullptr;
+    if (!rc)
+        rc = gnnpe_csr_apply_vertices(c, R.data(), R.size(), add_labels, n_add, nullptr, nullptr, nullptr, &vmap, want_map ? &emap : nullptr,
+                                      device_ms ? &ms1 : nullptr);
+    if (rc) {  // nothing of the context has changed
+        standing_roll_back(c, H, reduced, T);
+        return rc;
+    }
+    if (device_ms) *device_ms += ms1;
+    if (n_after) *n_after = c->n;
+    // behind the swap: S, V and its scratch table through the vertex map, E and its scratch table through the entry map.  The
+    // columns of R and the entries at R hold what the searches above left there and are dropped: their cells are gone, not listed.
+    auto carry = [&](bool entries, uint32_t rows, DevBuf &buf, DevBuf &spare) {
+        const int r = (entries ? gnnpe_csr_carry_entries : gnnpe_csr_carry_vertices)(c, rows, 8, buf.p, spare.p, device_ms ? &ms1 : nullptr);
+        if (!r) {
+            if (device_ms) *device_ms += ms1;
+            StandingCounts::swap(buf, spare);
+        }
+        return r;
+    };
+    for (size_t i = 0; i < H.size() && !rc; i++) {
+        gnnpe_standing *h = H[i];
+        rc = carry(false, h->nq, h->table, h->table_spare);
+        for (int t = 0; t < 2 && !rc; t++) {
+            StandingCounts &K = h->kc[t];
+            if (!K.kept) continue;
+            if (!(rc = carry(t == 1, (uint32_t)K.rows, K.table, K.spare))) rc = carry(t == 1, (uint32_t)K.rows, K.delta, K.spare);
+            K.cols = t == 1 ? c->nbr_used : c->n;
+        }
+        h->n = c->n;
+        h->words = ((uint64_t)c->n + 31) / 32;
+    }
+    // T' = the new ids of T's survivors together with the added vertices, through the same map, before gnnpe_vde
+    if (!rc) rc = gnnpe_csr_carry_vertex_set(c, T.bits[0], 1, T.bits[1], T.ids[1], T.room, &T.n_ids[1], device_ms ? &ms1 : nullptr);
+    if (!rc && device_ms) *device_ms += ms1;
+    if (!rc && c->have_table) rc = gnnpe_vde(c, nullptr, nullptr, nullptr);
+    for (size_t i = 0; i < H.size() && !rc; i++)
+        if (!(rc = standing_support_delta_device(H[i], T, 1, +1, device_ms))) rc = standing_derive(H[i], device_ms);
+    // an added vertex is isolated: it completes a match of a single-vertex query only, which the general search covers
+    std::vector<uint32_t> A(n_add);
+    for (uint64_t i = 0; i < n_add; i++) A[i] = n_surv + (uint32_t)i;
+    for (size_t i = 0; i < H.size() && !rc; i++) rc = standing_delta(who, H[i], false, A, 0, &H[i]->p_created, device_ms, true);
+    if (!rc) rc = standing_fold_all(c, H, device_ms);
+    if (rc) {
+        for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
+        return rc;
+    }
+    standing_commit(c, H, true);
+    return GNNPE_OK;
+}
 
 int gnnpe_standing_open(gnnpe_ctx *c, const char *query_graph_path, uint32_t l, double epsilon, uint32_t mode, uint64_t rows_cap,
                         gnnpe_standing **sq, uint64_t *count, double *device_ms)
@@ -638,30 +920,13 @@ int gnnpe_standing_apply_edges(gnnpe_ctx *c, const uint32_t *insert_edges, uint6
         if (rc && !swapped) return rc;  // refused with everything as it was
         if (!rc && split) rc = standing_step(c, H, I, none, &swapped, device_ms, want_map);
         // the batch is through: one fold per kept table moves D into T and leaves the batch's change list, in the cells of G'
-        for (size_t i = 0; i < H.size() && !rc; i++)
-            for (StandingCounts &K : H[i]->kc) {
-                if (!K.kept || rc) continue;
-                double ms1 = 0.0;
-                rc = gnnpe_table_fold(c, K.table.p, K.delta.p, K.cells(), K.ch_cells.p, K.ch_deltas.p, H[i]->changes_cap, &K.n_changes,
-                                      device_ms ? &ms1 : nullptr);
-                if (device_ms) *device_ms += ms1;
-            }
+        if (!rc) rc = standing_fold_all(c, H, device_ms);
         if (rc) {  // a failure behind a swap: the graph has moved on and the handles have not
             for (gnnpe_standing *h : H) h->graph_gen = kStandingPoison;
             return rc;
         }
-    } else {
-        for (gnnpe_standing *h : H) h->kc[0].n_changes = h->kc[1].n_changes = 0;  // the empty batch changes no cell
     }
-    for (gnnpe_standing *h : H) {
-        h->created = h->p_created;
-        h->destroyed = h->p_destroyed;
-        h->count += h->p_created - h->p_destroyed;
-        h->held[0] = h->p_held[0];
-        h->held[1] = h->p_held[1];
-        if (n_insert || n_delete) h->cur ^= 1;
-        h->graph_gen = c->graph_gen;
-    }
+    standing_commit(c, H, n_insert || n_delete);
     return GNNPE_OK;
 }
 

@@ -66,7 +66,9 @@ struct Options {
     // --apply-edges FILE (exact -m online / -m filter only): lines `+ x y` / `- x y`, a batch of edge insertions and deletions
     // applied to the loaded data graph on the device before anything is computed from it (gnnpe_csr_apply_edges)
     std::string apply_edges_file;
-    std::vector<std::string> apply_edges_files;  // every --apply-edges in the order given: the batches of --standing
+    std::vector<std::string> apply_edges_files;  // every --apply-edges in the order given
+    // the batches of --standing in command-line order: {'e' --apply-edges, 'l' --set-labels, 'v' --apply-vertices, FILE}
+    std::vector<std::pair<char, std::string>> standing_batches;
     bool standing = false;  // --standing: a standing exact query carried through the batches (gnnpe_standing_* of include/gnnpe_online.h)
     // --standing-vertex-counts FILE, --standing-edge-counts FILE (need --standing): the handle keeps the table (gnnpe_standing_keep_counts),
     // every batch prints `changes: <n>`, and the table after the last batch is written in the format of --vertex-counts / --edge-counts
@@ -203,15 +205,19 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       --edge-counts): FILE has one data vertex id per line; the\n"
                    "       answer is the number of matches with at least one image among them, each match once, and --matches writes those;\n"
                    "       --set-labels FILE (exact mode only: --exact or -l 3): FILE has one line `v label` per vertex; the labels are set\n"
-                   "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's\n"
+                   "       on the device after --apply-edges and the query runs on the result: the metadata block is the relabelled graph's;\n"
+                   "       under --standing it may be repeated and is a batch of its own (gnnpe_standing_set_labels)\n"
                    "       --apply-vertices FILE (exact mode only: --exact or -l 3): FILE has one line `- v` (remove vertex v with its edges;\n"
                    "       the survivors keep their order under new ids) or `+ label` (append a vertex with that label and no edges) per\n"
-                   "       change; applied on the device first, so that --apply-edges, --set-labels and --delta-vertices name the new ids\n"
+                   "       change; applied on the device first, so that --apply-edges, --set-labels and --delta-vertices name the new ids;\n"
+                   "       under --standing it may be repeated and is a batch of its own (gnnpe_standing_apply_vertices): there the\n"
+                   "       --apply-edges, --set-labels and --apply-vertices batches are applied in command-line order, one `standing:`\n"
+                   "       line each, and a batch names the ids the batches before it left\n"
                    "       --incremental (with --apply-edges, --set-labels or --apply-vertices): the candidate sets come from the exact\n"
                    "       filter's support table, built on the graph as loaded and patched around every batch, not from a filter pass over\n"
                    "       the updated graph; same sets, same answer\n"
                    "       --standing-vertex-counts FILE, --standing-edge-counts FILE (need --standing; either or both): the standing query\n"
-                   "       keeps the table across the --apply-edges batches, prints `changes: <n>` per batch (the cells the batch changed,\n"
+                   "       keeps the table across the batches (--apply-edges, --set-labels, --apply-vertices), prints `changes: <n>` per batch (the cells the batch changed,\n"
                    "       over the kept tables) and writes the table after the last batch as --vertex-counts / --edge-counts do\n",
                    tool, tool);
             exit(0);
@@ -243,10 +249,10 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
             if (a == "--delta-nonedges") { o.delta_nonedges_file = argv[++i]; continue; }
             if (a == "--delta-vertex-counts") { o.delta_vertex_counts_file = argv[++i]; continue; }
             if (a == "--delta-edge-counts") { o.delta_edge_counts_file = argv[++i]; continue; }
-            if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; o.apply_edges_files.push_back(o.apply_edges_file); continue; }
+            if (a == "--apply-edges") { o.apply_edges_file = argv[++i]; o.apply_edges_files.push_back(o.apply_edges_file); o.standing_batches.emplace_back('e', o.apply_edges_file); continue; }
             if (a == "--delta-vertices") { o.delta_vertices_file = argv[++i]; continue; }
-            if (a == "--set-labels") { o.set_labels_file = argv[++i]; continue; }
-            if (a == "--apply-vertices") { o.apply_vertices_file = argv[++i]; continue; }
+            if (a == "--set-labels") { o.set_labels_file = argv[++i]; o.standing_batches.emplace_back('l', o.set_labels_file); continue; }
+            if (a == "--apply-vertices") { o.apply_vertices_file = argv[++i]; o.standing_batches.emplace_back('v', o.apply_vertices_file); continue; }
             o.refine = argv[++i];
             if (o.refine != "start" && o.refine != "sets") die("--refine must be start or sets");
             continue;

@@ -457,10 +457,11 @@ static void read_edge_batch(const std::string &path, std::vector<uint32_t> *ins,
     fclose(af);
 }
 
-// -m online --exact [-l 3] --standing --apply-edges FILE [--apply-edges FILE ...]: a standing exact query (gnnpe_standing_open, with
-// --distinct / --induced in its mode) opened on the graph as loaded and carried through the batches in the order given, one
-// gnnpe_standing_apply_edges each.  Prints `standing: count created destroyed device_ms` for the open (created = destroyed = 0) and
-// after every batch.  No order and no membership.txt are read: the support calls need none.
+// -m online --exact [-l 3] --standing with one or more of --apply-edges FILE, --set-labels FILE, --apply-vertices FILE, each
+// repeatable: a standing exact query (gnnpe_standing_open, with --distinct / --induced in its mode) opened on the graph as loaded
+// and carried through the batches in command-line order, one gnnpe_standing_apply_edges, gnnpe_standing_set_labels or
+// gnnpe_standing_apply_vertices each.  Prints `standing: count created destroyed device_ms` for the open (created = destroyed = 0)
+// and after every batch.  No order and no membership.txt are read: the support calls need none.
 int run_standing(const Options &o)
 {
     StaticGraph g;
@@ -472,8 +473,12 @@ int run_standing(const Options &o)
     }
     if (rc != 0) die(o.data_graph + ": " + err);
     if (!g.simple) die(o.data_graph + " repeats an edge (duplicate `e` lines): --standing needs a simple graph");
-    std::vector<std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> batches(o.apply_edges_files.size());
-    for (size_t i = 0; i < batches.size(); i++) read_edge_batch(o.apply_edges_files[i], &batches[i].first, &batches[i].second);  // before a GPU is touched
+    // per batch two lists: insertions and deletions (pairs), vertices and labels, or removed vertices and added labels
+    std::vector<std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> batches(o.standing_batches.size());
+    for (size_t i = 0; i < batches.size(); i++) {  // before a GPU is touched
+        const char kind = o.standing_batches[i].first;
+        (kind == 'e' ? read_edge_batch : kind == 'l' ? read_label_list : read_vertex_batch)(o.standing_batches[i].second, &batches[i].first, &batches[i].second);
+    }
     if (gnnpe_device_count() <= 0) die("no HIP device: this tool has no CPU fallback");
     gnnpe_ctx *ctx = gnnpe_create(0);
     if (!ctx) die(std::string("gnnpe_create: ") + gnnpe_last_error());
@@ -495,11 +500,17 @@ int run_standing(const Options &o)
                           (o.standing_edge_counts_file.empty() ? 0u : GNNPE_STANDING_EDGE_COUNTS);
     if (keep) check(ONLINE(gnnpe_standing_keep_counts)(sq, keep, 0, nullptr), "standing_keep_counts");
     const auto apply = ONLINE(gnnpe_standing_apply_edges);
+    const auto relabel = ONLINE(gnnpe_standing_set_labels);
+    const auto apply_vertices = ONLINE(gnnpe_standing_apply_vertices);
     const auto result = ONLINE(gnnpe_standing_result);
     const auto changes = ONLINE(gnnpe_standing_count_changes);
     for (size_t i = 0; i < batches.size(); i++) {
-        const std::vector<uint32_t> &ins = batches[i].first, &del = batches[i].second;
-        check(apply(ctx, ins.data(), ins.size() / 2, del.data(), del.size() / 2, &ms), ("--apply-edges " + o.apply_edges_files[i]).c_str());
+        const std::vector<uint32_t> &a = batches[i].first, &b = batches[i].second;
+        const char kind = o.standing_batches[i].first;
+        const std::string &file = o.standing_batches[i].second;
+        if (kind == 'e') check(apply(ctx, a.data(), a.size() / 2, b.data(), b.size() / 2, &ms), ("--apply-edges " + file).c_str());
+        else if (kind == 'l') check(relabel(ctx, a.data(), b.data(), a.size(), &ms), ("--set-labels " + file).c_str());
+        else check(apply_vertices(ctx, a.data(), a.size(), b.data(), b.size(), &g.n, &ms), ("--apply-vertices " + file).c_str());
         uint64_t out[6];
         check(result(sq, out), "standing_result");
         printf("standing: %llu %llu %llu %.3f\n", (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], ms);
@@ -513,7 +524,7 @@ int run_standing(const Options &o)
             printf("changes: %llu\n", (unsigned long long)total);
         }
     }
-    if (keep) {  // the tables after the last batch, on the graph as it is now
+    if (keep) {  // the tables after the last batch, on the graph as it is now (g.n: as the last vertex batch left it)
         uint64_t entries = 0;
         g.offsets.assign((size_t)g.n + 1, 0);
         (void)gnnpe_csr_download(ctx, g.offsets.data(), nullptr, 0, &entries);  // no room: refused with the entry count set
@@ -926,20 +937,19 @@ int main(int argc, char **argv)
         die("--apply-vertices applies to exact -m online / -m filter only (--exact or -l 3): every other mode reads files that were "
             "made from the graph as it was");
     if (o.standing) {
-        if (!(o.mode == "online" && (o.exact || o.path_length == 3)) || o.apply_edges_files.empty())
-            die("--standing applies to exact -m online (--exact or -l 3) with one or more --apply-edges FILE");
-        if (o.incremental || !o.apply_vertices_file.empty() || !o.set_labels_file.empty())
-            die("--standing carries edge batches only: --incremental, --apply-vertices and --set-labels do not go with it");
+        if (!(o.mode == "online" && (o.exact || o.path_length == 3)) || o.standing_batches.empty())
+            die("--standing applies to exact -m online (--exact or -l 3) with one or more --apply-edges, --set-labels or --apply-vertices FILE");
+        if (o.incremental) die("--standing keeps its own support table: --incremental does not go with it");
     } else if (!o.standing_vertex_counts_file.empty() || !o.standing_edge_counts_file.empty())
         die("--standing-vertex-counts and --standing-edge-counts need --standing");
     if (o.incremental && o.apply_vertices_file.empty() && o.apply_edges_file.empty() && o.set_labels_file.empty())
         die("--incremental applies with --apply-vertices, --apply-edges or --set-labels: it carries the exact filter's support table "
             "across their batches");
-    if (!o.apply_vertices_file.empty()) {  // a malformed file is refused before a GPU is touched
+    if (!o.apply_vertices_file.empty() && !o.standing) {  // a malformed file is refused before a GPU is touched (--standing reads every batch there)
         std::vector<uint32_t> rem, add;
         read_vertex_batch(o.apply_vertices_file, &rem, &add);
     }
-    if (!o.set_labels_file.empty()) {  // a malformed file is refused before a GPU is touched
+    if (!o.set_labels_file.empty() && !o.standing) {  // a malformed file is refused before a GPU is touched
         std::vector<uint32_t> vs, ls;
         read_label_list(o.set_labels_file, &vs, &ls);
     }

@@ -699,6 +699,38 @@ int gnnpe_filter_support_bitmap(gnnpe_ctx *ctx, uint32_t n_query_vertices, const
 int gnnpe_filter_support_bitmap_device(gnnpe_ctx *ctx, uint32_t n_query_vertices, const void *dev_table, void *dev_bitmap,
                                        double *device_ms);
 
+/* ---- touched sets on the device (headed by name, GNNPE_ABI_VERSION stays 20: symbols are added) ----------------------------------
+ * The relabel loop and the vertex-batch loop above need T = R u N_G(R) and T' = the new ids of T's survivors with the added
+ * vertices.  A caller with a host copy of the rows builds them there; these three make and use them on the device, from the
+ * resident rows and the resident vertex map, so that nothing proportional to n or m crosses to the host per batch
+ * (csrc/gnnpe_touched.hip).  A set has two forms, both in the CALLER's device memory on the context's device: a bitmap of ceil(n/32)
+ * uint32 (every word written, the bits at and above n zero) and its ascending ids.
+ *
+ * gnnpe_csr_closed_neighbourhood: T = R u N_G(R) for R = vertices (n_vertices ids < n; a repeated id means the vertex once) into
+ *   dev_bits and dev_ids (room for ids_cap ids), *n_ids = |T|.  One wave per vertex of R marks its row with atomicOr into the zeroed
+ *   bitmap; the ids come from the ordered compaction of the bitmap.  If ids_cap < |T| the call returns GNNPE_ERR_ARG with *n_ids set
+ *   and the bitmap written; of the ids only the first ids_cap are.  n_vertices == 0 gives the empty set.  Refused before any launch:
+ *   an id >= n, a null list with a count > 0, a null or misaligned pointer (GNNPE_ERR_ARG); a slab context or the multigraph state
+ *   (GNNPE_ERR_UNSUPPORTED).  One host wait, for the count.
+ * gnnpe_csr_carry_vertex_set: a set of G through the context's valid vertex map.  Bit v' of dev_bits_new (ceil(n'/32) words) is
+ *   set where vertex_map[v'] is a vertex of dev_bits_old (ceil(n/32) words) and, with with_added != 0, where the map says
+ *   GNNPE_NO_VERTEX.  One lane per vertex of G', the wave's answers one ballot stored as two words: no atomics.  ids_cap, *n_ids and
+ *   the wait as above.  Without a valid vertex map it is refused as gnnpe_csr_carry_vertices is (a following gnnpe_csr_apply_edges
+ *   ends the map); the two bitmaps must not overlap.
+ * gnnpe_filter_support_exact_delta_device: gnnpe_filter_support_exact_delta with T taken from dev_bits and dev_ids (n_ids ascending
+ *   ids, each < n, each once, the bitmap holding exactly them: the caller's promise, which the two calls above keep).  It makes that
+ *   call's launches without the host sort, the upload and the scatter of the list -- the two share their body -- so for the same T
+ *   the two leave byte-equal tables.  n_ids == 0 succeeds and launches nothing.  Requirements and refusals as the host-list call.
+ * *device_ms (may be NULL): the time on the device between the uploads and the wait. */
+int gnnpe_csr_closed_neighbourhood(gnnpe_ctx *ctx, const uint32_t *vertices, uint64_t n_vertices, void *dev_bits, void *dev_ids,
+                                   uint64_t ids_cap, uint64_t *n_ids, double *device_ms);
+int gnnpe_csr_carry_vertex_set(gnnpe_ctx *ctx, const void *dev_bits_old, int with_added, void *dev_bits_new, void *dev_ids,
+                               uint64_t ids_cap, uint64_t *n_ids, double *device_ms);
+int gnnpe_filter_support_exact_delta_device(gnnpe_ctx *ctx, uint32_t l, const uint32_t counts[3], const uint32_t *q_vids,
+                                            const uint32_t *q_labels, const uint32_t *q_degrees, const double *q_pde,
+                                            uint32_t n_query_vertices, double epsilon, const void *dev_bits, const void *dev_ids,
+                                            uint64_t n_ids, int sign, void *dev_table, double *device_ms);
+
 /* The refinement half of the reference's online step (custom.h:634-932) is outside SURVEY section 8's scope (frozen since round 1)
  * and ships in a library of its own since round 6: include/gnnpe_online.h, libgnnpe_online.so (gnnpe_refine, gnnpe_host_refine). */
 

@@ -735,7 +735,8 @@ int gnnpe_refine_pages_open_delta_vertices(gnnpe_ctx *ctx, const char *query_gra
  * STALENESS.  A handle remembers the graph generation and the label table it is exact for.  gnnpe_set_vertex_labels,
  *   gnnpe_csr_apply_vertices, gnnpe_load_csr (and the other loaders), gnnpe_set_label_table and a plain gnnpe_csr_apply_edges[_map]
  *   behind its back make it stale: every call on it except refresh and close returns GNNPE_ERR_ARG with a message naming
- *   gnnpe_standing_refresh, and gnnpe_standing_apply_edges on the context refuses as well, before touching anything.
+ *   gnnpe_standing_refresh, and gnnpe_standing_apply_edges (like gnnpe_standing_set_labels and gnnpe_standing_apply_vertices below) on
+ *   the context refuses as well, before touching anything.
  * refresh: S, C and the count again from the graph as it is (it needs what open needs, a current gnnpe_vde included): the state of a
  *   fresh open, no rows.  An open_sets handle keeps its bitmap, and is refused if n changed.
  * close: frees everything; close(NULL) does nothing.
@@ -784,8 +785,54 @@ int gnnpe_refine_pages_open_delta_vertices(gnnpe_ctx *ctx, const char *query_gra
  *   across the two different sound sets.  open_sets handles rely on the caller's promise above that the bitmap is sound for every
  *   graph the handle will see.
  *
- * Not yet: vertex and label batches through the handle (refresh serves them for now), a fused carry-and-fold for E (T and D of E are
- * carried as two gathers per apply), paged change lists (what is behind changes_cap is counted, not held), a device plan handle for
+ * LABEL AND VERTEX BATCHES THROUGH THE HANDLE (GNNPE_ABI_VERSION stays 20: symbols are added, and a process that never calls the two
+ * entries below runs, launch for launch, what it ran before).  The other two updates of the resident graph, gnnpe_set_vertex_labels
+ * and gnnpe_csr_apply_vertices, for the graph AND every handle open on the context, with created / destroyed rows and change lists
+ * where gnnpe_standing_refresh has none.  What kept the hand-written loops of include/gnnpe_hip.h off this path is on the device now:
+ * the touched sets (gnnpe_csr_closed_neighbourhood, gnnpe_csr_carry_vertex_set, gnnpe_filter_support_exact_delta_device) and S n C(u)
+ * of the vertex-anchored searches (k_vset_member_of: nq x ceil(k / 64) ballot words come back for a list of k ids).  DeltaV below is
+ * gnnpe_refine_sets_delta_vertices on the resident sets; a kept table takes the tables of the same search into D.
+ *
+ * gnnpe_standing_set_labels(ctx, vertices, labels, count): the pairs are read as gnnpe_set_vertex_labels reads them.  The current
+ *   labels of the listed vertices come back in one gather of 4 count bytes; R* is the vertices whose label really changes, and with
+ *   T = R* u N(R*), built once per call, every handle runs
+ *       S -= S_T(G);  destroyed = DeltaV(G, C, R*);  gnnpe_set_vertex_labels(R*);  gnnpe_vde;  S += S_T(G');  C' = bitmap(S);
+ *       created = DeltaV(G', C', R*);  one gnnpe_table_fold per kept table.
+ *   WHY created AND destroyed ARE EXACT.  Let f be a match of G (in any mode: a match maps query vertices to data vertices of equal
+ *   label).  If f uses no vertex of R*, every label, edge and non-edge it rests on is the same in G', so f is a match of G' too: it
+ *   is in neither difference, and DeltaV(., ., R*) does not find it.  If f uses some r in R* as the image of u, then in G' the
+ *   label of r differs from label(u) = label_G(r), so f is no match of G': f is in M(G) \ M(G').  So M(G) \ M(G') is exactly the
+ *   matches of G through R*, which is what DeltaV(G, C, R*) finds for a sound C; by the same argument with G and G' exchanged
+ *   M(G') \ M(G) is DeltaV(G', C', R*).  A listed vertex that keeps its label would break the second step: a match through it
+ *   survives, and both searches would report it.  That is why the no-ops are dropped before anything else.
+ *   No edge changes, so an induced handle needs no non-edge search, entries do not move and E needs no carry.  With rows_cap == 0
+ *   and a kept table the count kernels' answers serve as created / destroyed, as in the edge path.  An empty R* (count == 0
+ *   included) succeeds, touches neither graph nor generation, and reports created = destroyed = 0 with empty change lists.
+ *   open_sets handles go along under the promise that their bitmap is sound for every graph the handle sees -- which a LABEL bitmap
+ *   does not keep across a relabel: use gnnpe_standing_set_bitmap, or a bitmap that does not depend on the labels.
+ *   TRANSACTIONAL as gnnpe_standing_apply_edges.  Decided before anything changes, leaving graph, generation and every handle byte
+ *   for byte as they were (GNNPE_ERR_ARG): an id >= n, one vertex listed with two labels, a stale handle, and -- where a filter
+ *   handle is open and the context has a label table -- a new label without a row in the table, which gnnpe_vde would refuse
+ *   behind the change.  A failure before the relabel puts S back and zeroes D; a failure after it makes the handles stale.
+ *
+ * gnnpe_standing_apply_vertices(ctx, remove, n_remove, add_labels, n_add, &n_after): with R the removed vertices, A the added ones
+ *   (the last n_add ids of G') and T = R u N_G(R), every handle runs
+ *       S -= S_T(G);  destroyed = DeltaV(G, C, R);  gnnpe_csr_apply_vertices (with the entry map where a handle keeps E);
+ *       S, and T and D of V, through gnnpe_csr_carry_vertices;  T and D of E through gnnpe_csr_carry_entries;  gnnpe_vde;
+ *       T' = gnnpe_csr_carry_vertex_set(T, with_added);  S += S_T'(G');  C' = bitmap(S) at n';  created = DeltaV(G', C', A);  fold.
+ *   A match of G is lost exactly when it uses a removed vertex; a match of G' is new exactly when it uses an added one, and an added
+ *   vertex is isolated, so it completes a match of a single-vertex query only -- the general search covers that.
+ *   The destroyed rows are in the ids of G; the created rows and both change lists are in the ids of G'.  The cells of removed
+ *   vertices and entries are gone and not listed, the rule the E change list has for deleted entries.
+ *   The out-of-place carries of S and V need a spare each; they and every table are given room for max(n, n') before the swap, and
+ *   the spares are made at the first vertex batch, so a handle that only sees edge batches allocates nothing new.
+ *   Refusals before anything changes: gnnpe_csr_apply_vertices' own (a null list, an id >= n, n' == 0, the id ranges), an added label
+ *   without a row in the label table, a stale handle, and a gnnpe_standing_open_sets handle open on the context
+ *   (GNNPE_ERR_UNSUPPORTED: its bitmap was made for the old n).  A refusal inside the apply before its swap puts S back and zeroes
+ *   D.  The empty batch is a no-op.  *n_after = n'.
+ *
+ * Not yet: vertex batches with an open_sets handle on the context, an automatic switch to gnnpe_standing_refresh where a batch
+ * touches so much that recomputing is cheaper (profiles/online_standing_updates.txt has where that is), a fused carry-and-fold for E (T and D of E are carried as two gathers per apply), paged change lists (what is behind changes_cap is counted, not held), a device plan handle for
  * the support calls (their plan is uploaded per call), slab contexts, multigraph rows. */
 #define GNNPE_STANDING_VERTEX_COUNTS 1u
 #define GNNPE_STANDING_EDGE_COUNTS 2u
@@ -797,6 +844,9 @@ int gnnpe_standing_open_sets(gnnpe_ctx *ctx, const char *query_graph_path, uint3
 int gnnpe_standing_set_bitmap(gnnpe_standing *sq, const uint32_t *host_bitmap);
 int gnnpe_standing_apply_edges(gnnpe_ctx *ctx, const uint32_t *insert_edges, uint64_t n_insert, const uint32_t *delete_edges,
                                uint64_t n_delete, double *device_ms);
+int gnnpe_standing_set_labels(gnnpe_ctx *ctx, const uint32_t *vertices, const uint32_t *labels, uint64_t count, double *device_ms);
+int gnnpe_standing_apply_vertices(gnnpe_ctx *ctx, const uint32_t *remove, uint64_t n_remove, const uint32_t *add_labels, uint64_t n_add,
+                                  uint32_t *n_after, double *device_ms);
 int gnnpe_standing_result(gnnpe_standing *sq, uint64_t out[6]);
 int gnnpe_standing_rows(gnnpe_standing *sq, int which, uint32_t *host_rows, uint64_t cap, uint64_t *n_rows);
 int gnnpe_standing_set_sizes(gnnpe_standing *sq, uint64_t *sizes);
