@@ -58,6 +58,8 @@ SIGNATURES = {
     "gnnpe_csr_apply_edges_map": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, C.POINTER(_vp), _f64p]),
     "gnnpe_csr_carry_entries": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _f64p]),
     "gnnpe_table_fold": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _u64p, _f64p]),
+    "gnnpe_host_csr_edges_below": (C.c_int, [C.c_uint32, _u32p, _u32p, _u64p, C.c_uint32, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p]),
+    "gnnpe_csr_edges_below": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p, _f64p]),
     "gnnpe_set_vertex_labels": (C.c_int, [_vp, _u32p, _u32p, C.c_uint64, _f64p]),
     "gnnpe_labels_download": (C.c_int, [_vp, _u32p]),
     "gnnpe_host_csr_apply_vertices": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p, C.c_uint64, _u32p, C.c_uint64, _u32p, _u32p, C.c_uint64,
@@ -178,6 +180,9 @@ ONLINE_SIGNATURES = {
     "gnnpe_standing_keep_counts": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _f64p]),
     "gnnpe_standing_counts": (C.c_int, [_vp, C.c_uint32, _u64p, C.POINTER(_vp), _u64p, _u64p]),
     "gnnpe_standing_count_changes": (C.c_int, [_vp, C.c_uint32, _u64p, C.POINTER(C.c_int64), C.c_uint64, _u64p]),
+    "gnnpe_standing_peel": (C.c_int, [_vp, C.c_uint64, C.c_uint32, _u32p, _u32p, C.c_uint64, _u64p, _f64p]),
+    "gnnpe_standing_truss_levels": (C.c_int, [_vp, C.c_int, _u32p, _u64p, C.c_uint64, _u64p, _f64p]),
+    "gnnpe_host_truss_levels": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint32, _u32p, _u64p, C.c_uint64, _u64p]),
     "gnnpe_standing_refresh": (C.c_int, [_vp, _u64p, _f64p]),
     "gnnpe_standing_close": (C.c_int, [_vp]),
     "gnnpe_host_refine": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, C.c_char_p, _u32p, C.c_uint64, _u64p]),
@@ -695,6 +700,40 @@ def host_entry_map(g_old, g_new):
     return out
 
 
+def host_edges_below(g, table, threshold, cap=None):
+    """gnnpe_host_csr_edges_below: the undirected edges of g whose support in `table` (n_rows x entries uint64: the sum over the
+    rows of the cells of the edge's two entries, mod 2^64) is below `threshold`, as ascending (x, y) pairs with x < y.  Returns
+    (the first min(cap, n_selected) pairs as an (k, 2) uint32 array, n_selected, min_kept); cap=None: room for every edge."""
+    lib = load()
+    off, nb = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32)
+    tab = np.ascontiguousarray(table, np.uint64)
+    if tab.ndim != 2 or tab.shape[1] != len(nb):
+        raise GnnpeError(f"host_edges_below: the table is {tab.shape}, the graph has {len(nb)} entries")
+    cap = len(nb) // 2 if cap is None else int(cap)
+    pairs, n_sel, low = np.zeros((max(cap, 1), 2), np.uint32), C.c_uint64(), C.c_uint64()
+    rc = lib.gnnpe_host_csr_edges_below(len(off) - 1, _ptr(off, _u32p), _ptr(nb, _u32p), _ptr(tab, _u64p), tab.shape[0],
+                                        int(threshold), _ptr(pairs, _u32p) if cap else None, cap, C.byref(n_sel), C.byref(low))
+    if rc:
+        raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
+    return pairs[:min(cap, n_sel.value)].copy(), int(n_sel.value), int(low.value)
+
+
+def host_truss_levels(g, query_path, bitmap, distinct=False):
+    """gnnpe_host_truss_levels: the truss level of every edge of g for the query (include/gnnpe_online.h, "PEELING THE GRAPH BY EDGE
+    SUPPORT"), by peeling with a full recount every round: (edges (m, 2) uint32 in removal order, levels uint64, out) with out =
+    [edges, distinct levels, largest level, rounds]."""
+    lib, online = load(), load_online()
+    off, nb, lab = _np(g["offsets"], np.uint32), _np(g["nbrs"], np.uint32), _np(g["labels"], np.uint32)
+    bm = _np(bitmap, np.uint32)
+    m = len(nb) // 2
+    edges, levels, out = np.zeros((max(m, 1), 2), np.uint32), np.zeros(max(m, 1), np.uint64), (C.c_uint64 * 4)()
+    rc = online.gnnpe_host_truss_levels(len(off) - 1, _ptr(off, _u32p), _ptr(nb, _u32p), _ptr(lab, _u32p), query_path.encode(), _ptr(bm, _u32p),
+                                        match_mode(distinct, False), _ptr(edges, _u32p), _ptr(levels, _u64p), m, out)
+    if rc:
+        raise GnnpeError(f"[{rc}] " + lib.gnnpe_last_error().decode())
+    return edges[:out[0]].copy(), levels[:out[0]].copy(), [int(x) for x in out]
+
+
 NO_VERTEX = 0xFFFFFFFF  # GNNPE_NO_VERTEX of include/gnnpe_hip.h
 
 
@@ -1087,6 +1126,45 @@ class StandingQuery:
         n = C.c_uint64()
         self.eng._ck(self.online.gnnpe_standing_count_changes(self.handle, self._which(which), None, None, 0, C.byref(n)))
         return int(n.value)
+
+    def peel(self, min_support, max_rounds=0, timing=False):
+        """gnnpe_standing_peel: rounds of "select the edges whose support in the kept E is below min_support on the device, delete
+        them as one standing_apply_edges batch" until nothing is selected (max_rounds=0) or max_rounds rounds have deleted
+        something.  Needs keep_counts(edge=True).  Returns (removed (k, 2) uint32 in removal order, their rounds uint32 counted
+        from 1, out) with out = [rounds, edges removed, undirected edges left, converged]; the device ms appended with timing."""
+        cap = self.eng.rows_held()[1] // 2
+        removed, rounds = np.zeros((max(cap, 1), 2), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        out, ms = (C.c_uint64 * 4)(), C.c_double()
+        rc = self.online.gnnpe_standing_peel(self.handle, int(min_support), int(max_rounds), _ptr(removed, _u32p), _ptr(rounds, _u32p), cap, out,
+                                             C.byref(ms) if timing else None)
+        self._graph_moved(out[0] != 0)  # (a peel that failed in a later round has moved the graph too)
+        self.eng._ck(rc)
+        res = (removed[:out[1]].copy(), rounds[:out[1]].copy(), [int(x) for x in out])
+        return res + (ms.value,) if timing else res
+
+    def _graph_moved(self, moved):
+        """the engine's own bookkeeping after a call that applied batches inside the library, as standing_apply_edges keeps it"""
+        eng = self.eng
+        eng._map_call += 1
+        if moved:
+            eng._rows_gen += 1
+            eng.slab = (0, eng.n)
+            eng.entries = eng.rows_held()[1]
+
+    def truss_levels(self, restore=True, timing=False):
+        """gnnpe_standing_truss_levels: the truss level of every edge of the resident graph by peeling it level by level; with
+        restore the removed edges are inserted again at the end, without it the context is left with the empty graph.  Returns
+        (edges (m, 2) uint32 in removal order, levels uint64, out) with out = [edges, distinct levels, largest level, rounds]; the
+        device ms appended with timing."""
+        cap = self.eng.rows_held()[1] // 2
+        edges, levels = np.zeros((max(cap, 1), 2), np.uint32), np.zeros(max(cap, 1), np.uint64)
+        out, ms = (C.c_uint64 * 4)(), C.c_double()
+        rc = self.online.gnnpe_standing_truss_levels(self.handle, 1 if restore else 0, _ptr(edges, _u32p), _ptr(levels, _u64p), cap, out,
+                                                     C.byref(ms) if timing else None)
+        self._graph_moved(out[0] != 0)
+        self.eng._ck(rc)
+        res = (edges[:out[0]].copy(), levels[:out[0]].copy(), [int(x) for x in out])
+        return res + (ms.value,) if timing else res
 
     def refresh(self, timing=False):
         """S, C and the count again from the graph as it is now: the state of a fresh open"""
@@ -1881,6 +1959,17 @@ class Engine:
         self._ck(self.lib.gnnpe_table_fold(self.ctx, _dev(table), _dev(delta), int(cells), _dev(change_cells), _dev(change_deltas),
                                            int(cap), C.byref(n), C.byref(ms) if timing else None))
         return (n.value, ms.value) if timing else n.value
+
+    def edges_below(self, table, n_rows, threshold, pairs=None, cap=0, timing=False):
+        """gnnpe_csr_edges_below: the undirected edges of the resident graph whose support in `table` (n_rows x entries uint64 on
+        the device: an int, a tensor, or an object with data_ptr()) is below `threshold`; the first `cap` of them go to the device
+        array `pairs` (cap x 2 uint32, ascending (x, y) with x < y), which may be None only with cap == 0.  Returns (n_selected,
+        min_kept): the true number of selected edges and the smallest support among the others (2^64 - 1 without one); the device
+        ms appended with timing=True."""
+        n, low, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        self._ck(self.lib.gnnpe_csr_edges_below(self.ctx, _dev(table), int(n_rows), int(threshold), _dev(pairs), int(cap), C.byref(n), C.byref(low),
+                                                C.byref(ms) if timing else None))
+        return (n.value, low.value, ms.value) if timing else (n.value, low.value)
 
     def apply_vertices(self, remove=None, add_labels=None, entry_map=False, timing=False):
         """gnnpe_csr_apply_vertices: the vertices of `remove` (ids of the graph on the device, repeats tolerated) leave with their

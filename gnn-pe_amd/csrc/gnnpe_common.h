@@ -309,6 +309,9 @@ struct gnnpe_ctx {
     // and its ascending ids, for the larger of n and n'; in front of them the batch's ids and the labels gathered for them
     gnnpe::DevBuf q_touched;
     gnnpe::DevBuf fold_tiles;  // gnnpe_table_fold (gnnpe_table_fold.hip): the changed cells per tile and their exclusive sums
+    // gnnpe_csr_edges_below (gnnpe_edges_below.hip): the selected edges and the smallest kept support per tile, their scan and minimum;
+    // below_pairs: the pairs a round of gnnpe_standing_peel selects (libgnnpe_online.so), 8 bytes per undirected edge of the graph
+    gnnpe::DevBuf below_tiles, below_pairs;
     bool have_deg_all = false;
     bool vkey_valid = false;
     uint32_t vkey_zb = 0, vkey_lb = 0, vkey_sbits = 32;  // sbits 32 = wide (64-bit) table only

@@ -27,6 +27,11 @@
 // gnnpe_csr_carry_entries, and after the last step one gnnpe_table_fold per table does T += D, D = 0 and writes the change list
 // (csrc/gnnpe_table_fold.hip says why D exists).  T, D and the spare of E take turns, so all three are sized for the largest graph
 // of the batch before its first step (standing_size_edge_tables): nothing is allocated behind a swap.  profiles/online_standing_counts.txt.
+//
+// PEELING BY EDGE SUPPORT (gnnpe_standing_peel, gnnpe_standing_truss_levels): no kernel of their own.  A round is one
+// gnnpe_csr_edges_below (csrc/gnnpe_edges_below.hip, libgnnpe_hip.so) on the kept E into c->below_pairs, the selected pairs to the host,
+// and one gnnpe_standing_apply_edges with them as the deletions: the transaction, the other handles and the tables are that call's.
+// profiles/online_standing_peel.txt.
 #include "../../include/gnnpe_online.h"
 #include "gnnpe_dpp.hip.h"
 #include "gnnpe_refine_delta.hip.h"
@@ -1093,6 +1098,116 @@ int gnnpe_standing_count_changes(gnnpe_standing *h, uint32_t which, uint64_t *ho
         GNNPE_HIP_TRY(hipStreamSynchronize(h->c->stream));
         GNNPE_HIP_TRY(hipMemcpy(host_cells, K->ch_cells.p, take * 8, hipMemcpyDeviceToHost));
         GNNPE_HIP_TRY(hipMemcpy(host_deltas, K->ch_deltas.p, take * 8, hipMemcpyDeviceToHost));
+    }
+    return GNNPE_OK;
+}
+
+// ---- peeling by edge support (the header: "PEELING THE GRAPH BY EDGE SUPPORT") -------------------------------------------------------
+
+// what gnnpe_standing_peel and gnnpe_standing_truss_levels refuse before anything changes
+static int standing_peel_check(const char *who, gnnpe_standing *h)
+{
+    STANDING_LIVE(who, h);
+    GNNPE_REQUIRE(!(h->mode & GNNPE_MATCH_INDUCED), GNNPE_ERR_UNSUPPORTED,
+                  "%s: an induced handle: a deletion can create induced matches, so the peel has no unique fixpoint", who);
+    GNNPE_REQUIRE(h->nqe != 0, GNNPE_ERR_ARG, "%s: a query without an edge has no per-edge table", who);
+    GNNPE_REQUIRE(h->kc[1].kept, GNNPE_ERR_ARG, "%s: the handle does not keep E (gnnpe_standing_keep_counts with GNNPE_STANDING_EDGE_COUNTS)", who);
+    std::vector<gnnpe_standing *> H;  // every handle on the context goes along: a stale one would refuse the first round
+    return standing_handles(who, h->c, &H);
+}
+
+// The rounds of one threshold: select, stop if nothing is selected, delete the selection as one batch.  The pairs of every round are
+// appended to *removed (and the round, counted from round_base + 1, once per pair to *round if it is given).  out as
+// gnnpe_standing_peel's; *min_kept: of the last select.  A failure returns with out saying how far the loop came.
+static int standing_peel_rounds(gnnpe_standing *h, uint64_t min_support, uint32_t max_rounds, std::vector<uint32_t> *removed, std::vector<uint32_t> *round,
+                                uint32_t round_base, uint64_t out[4], uint64_t *min_kept, double *ms)
+{
+    gnnpe_ctx *c = h->c;
+    out[0] = out[1] = out[3] = 0;
+    out[2] = c->nbr_used / 2;
+    *min_kept = ~0ull;
+    GNNPE_HIP_TRY(hipSetDevice(c->device));
+    while (max_rounds == 0 || out[0] < max_rounds) {
+        const StandingCounts &K = h->kc[1];
+        const uint64_t room = c->nbr_used / 2;
+        int rc = c->below_pairs.reserve(std::max<uint64_t>(room * 8, 8));
+        if (rc) return rc;
+        uint64_t n_sel = 0;
+        double ms1 = 0.0;
+        if ((rc = gnnpe_csr_edges_below(c, K.table.p, (uint32_t)K.rows, min_support, c->below_pairs.p, room, &n_sel, min_kept, ms ? &ms1 : nullptr))) return rc;
+        if (ms) *ms += ms1;
+        if (n_sel == 0) {
+            out[3] = 1;
+            break;
+        }
+        GNNPE_REQUIRE(n_sel <= room, GNNPE_ERR_HIP, "gnnpe_standing_peel: internal error: %llu edges selected of %llu", (unsigned long long)n_sel,
+                      (unsigned long long)room);
+        const size_t at = removed->size();
+        removed->resize(at + 2 * n_sel);
+        GNNPE_HIP_TRY(hipMemcpy(removed->data() + at, c->below_pairs.p, n_sel * 8, hipMemcpyDeviceToHost));
+        if ((rc = gnnpe_standing_apply_edges(c, nullptr, 0, removed->data() + at, n_sel, ms ? &ms1 : nullptr))) {
+            removed->resize(at);  // the round was refused as a batch is: graph and handles are those of the round before
+            return rc;
+        }
+        if (ms) *ms += ms1;
+        out[0]++;
+        out[1] += n_sel;
+        out[2] = c->nbr_used / 2;
+        if (round) round->insert(round->end(), n_sel, round_base + (uint32_t)out[0]);
+    }
+    return GNNPE_OK;
+}
+
+int gnnpe_standing_peel(gnnpe_standing *h, uint64_t min_support, uint32_t max_rounds, uint32_t *host_removed, uint32_t *host_round, uint64_t cap,
+                        uint64_t out[4], double *device_ms)
+{
+    const char *who = "gnnpe_standing_peel";
+    if (device_ms) *device_ms = 0.0;
+    if (out) out[0] = out[1] = out[2] = out[3] = 0;
+    GNNPE_REQUIRE(h && out && (host_removed || cap == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    int rc = standing_peel_check(who, h);
+    if (rc) return rc;
+    std::vector<uint32_t> removed, round;
+    uint64_t min_kept = 0;
+    rc = standing_peel_rounds(h, min_support, max_rounds, &removed, &round, 0, out, &min_kept, device_ms);
+    const uint64_t take = std::min<uint64_t>(cap, removed.size() / 2);  // what was removed is reported after a failure too
+    if (take) memcpy(host_removed, removed.data(), take * 8);
+    if (take && host_round) memcpy(host_round, round.data(), take * 4);
+    return rc;
+}
+
+int gnnpe_standing_truss_levels(gnnpe_standing *h, int restore, uint32_t *host_edges, uint64_t *host_levels, uint64_t cap, uint64_t out[4],
+                                double *device_ms)
+{
+    const char *who = "gnnpe_standing_truss_levels";
+    if (device_ms) *device_ms = 0.0;
+    if (out) out[0] = out[1] = out[2] = out[3] = 0;
+    GNNPE_REQUIRE(h && out && ((host_edges && host_levels) || cap == 0), GNNPE_ERR_ARG, "%s: null argument", who);
+    int rc = standing_peel_check(who, h);
+    if (rc) return rc;
+    gnnpe_ctx *c = h->c;
+    std::vector<uint32_t> removed;
+    uint64_t part[4], t = 0, listed = 0;
+    // the first level: the smallest support of the graph, from a select that selects nothing
+    if ((rc = standing_peel_rounds(h, 0, 1, &removed, nullptr, 0, part, &t, device_ms))) return rc;
+    while (c->nbr_used) {
+        GNNPE_REQUIRE(t != ~0ull, GNNPE_ERR_RANGE, "%s: a support of 2^64 - 1 has no threshold above it", who);
+        const uint64_t level = t;
+        rc = standing_peel_rounds(h, level + 1, 0, &removed, nullptr, 0, part, &t, device_ms);
+        out[0] += part[1];
+        out[3] += part[0];
+        if (part[1]) out[1]++, out[2] = level;
+        for (; listed < removed.size() / 2 && listed < cap; listed++) host_levels[listed] = level;
+        if (rc) break;
+        GNNPE_REQUIRE(part[1] != 0, GNNPE_ERR_HIP, "%s: internal error: no edge has the smallest support %llu", who, (unsigned long long)level);
+    }
+    const uint64_t take = std::min<uint64_t>(cap, removed.size() / 2);
+    if (take) memcpy(host_edges, removed.data(), take * 8);
+    if (rc) return rc;
+    if (restore && !removed.empty()) {
+        double ms1 = 0.0;
+        if ((rc = gnnpe_standing_apply_edges(c, removed.data(), removed.size() / 2, nullptr, 0, device_ms ? &ms1 : nullptr))) return rc;
+        if (device_ms) *device_ms += ms1;
     }
     return GNNPE_OK;
 }

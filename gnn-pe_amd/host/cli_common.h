@@ -68,7 +68,11 @@ struct Options {
     std::string apply_edges_file;
     std::vector<std::string> apply_edges_files;  // every --apply-edges in the order given
     // the batches of --standing in command-line order: {'e' --apply-edges, 'l' --set-labels, 'v' --apply-vertices, FILE}
+    // ... and {'p' --peel, T} / {'t' --truss-levels, FILE}: a peel of the graph by edge support (gnnpe_standing_peel) and the truss
+    // level of every edge (gnnpe_standing_truss_levels, with restore), in the same order
     std::vector<std::pair<char, std::string>> standing_batches;
+    std::vector<std::pair<size_t, std::string>> standing_peel_outs;  // --peel-out FILE: {index of the --peel before it, FILE}
+    bool standing_peels = false;                                     // a --peel or --truss-levels was given
     bool standing = false;  // --standing: a standing exact query carried through the batches (gnnpe_standing_* of include/gnnpe_online.h)
     // --standing-vertex-counts FILE, --standing-edge-counts FILE (need --standing): the handle keeps the table (gnnpe_standing_keep_counts),
     // every batch prints `changes: <n>`, and the table after the last batch is written in the format of --vertex-counts / --edge-counts
@@ -218,7 +222,13 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
                    "       the updated graph; same sets, same answer\n"
                    "       --standing-vertex-counts FILE, --standing-edge-counts FILE (need --standing; either or both): the standing query\n"
                    "       keeps the table across the batches (--apply-edges, --set-labels, --apply-vertices), prints `changes: <n>` per batch (the cells the batch changed,\n"
-                   "       over the kept tables) and writes the table after the last batch as --vertex-counts / --edge-counts do\n",
+                   "       over the kept tables) and writes the table after the last batch as --vertex-counts / --edge-counts do\n"
+                   "       --peel T [--peel-out FILE], --truss-levels FILE (need --standing, not --induced; repeatable, applied in\n"
+                   "       command-line order with the batch files): the standing query keeps its per-edge table and the graph is peeled\n"
+                   "       by edge support on the device.  --peel T deletes, round by round, every edge whose support is below T and\n"
+                   "       prints `peel: <rounds> <edges removed> <edges left> <converged> <count> <device ms>`; FILE gets one `x y round`\n"
+                   "       line per removed edge.  --truss-levels writes `x y level` for every edge, restores the graph and prints\n"
+                   "       `truss: <edges> <levels> <largest level> <rounds> <device ms>`\n",
                    tool, tool);
             exit(0);
         }
@@ -238,8 +248,23 @@ inline Options parse_args(int argc, char **argv, const char *tool = "gnnpe_main"
         if (a == "--refine" || a == "--matches" || a == "--vertex-counts" || a == "--edge-counts" || a == "--delta-edges" ||
             a == "--delta-nonedges" ||
             a == "--apply-edges" || a == "--delta-vertex-counts" || a == "--delta-edge-counts" || a == "--delta-vertices" ||
-            a == "--set-labels" || a == "--apply-vertices" || a == "--standing-vertex-counts" || a == "--standing-edge-counts") {
+            a == "--set-labels" || a == "--apply-vertices" || a == "--standing-vertex-counts" || a == "--standing-edge-counts" ||
+            a == "--peel" || a == "--peel-out" || a == "--truss-levels") {
             if (i + 1 >= argc) die(a + " needs a value");
+            if (a == "--peel") {
+                char *end = nullptr;
+                (void)strtoull(argv[++i], &end, 10);
+                if (*end || end == argv[i] || argv[i][0] == '-') die("--peel must be an unsigned integer (the smallest support an edge keeps)");
+                o.standing_batches.emplace_back('p', argv[i]);
+                o.standing_peels = true;
+                continue;
+            }
+            if (a == "--peel-out") {
+                if (o.standing_batches.empty() || o.standing_batches.back().first != 'p') die("--peel-out FILE follows the --peel T it belongs to");
+                o.standing_peel_outs.emplace_back(o.standing_batches.size() - 1, argv[++i]);
+                continue;
+            }
+            if (a == "--truss-levels") { o.standing_batches.emplace_back('t', argv[++i]); o.standing_peels = true; continue; }
             if (a == "--standing-vertex-counts") { o.standing_vertex_counts_file = argv[++i]; continue; }
             if (a == "--standing-edge-counts") { o.standing_edge_counts_file = argv[++i]; continue; }
             if (a == "--matches") { o.matches_file = argv[++i]; continue; }

@@ -571,4 +571,47 @@ int gnnpe_host_csr_apply_vertices(uint32_t n, const uint32_t *offsets, const uin
     return GNNPE_OK;
 }
 
+// The host form of gnnpe_csr_edges_below: a plain loop over the entries (x -> y) with x < y, the reverse entry by a binary search
+// in row y.  It shares no code with the device form.
+int gnnpe_host_csr_edges_below(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint64_t *table, uint32_t n_rows, uint64_t threshold,
+                               uint32_t *pairs, uint64_t cap, uint64_t *n_selected, uint64_t *min_kept)
+{
+    const char *who = "gnnpe_host_csr_edges_below";
+    if (!offsets || !n_selected || !min_kept || (!nbrs && offsets[n]) || (!table && offsets[n]) || (!pairs && cap)) {
+        gnnpe::set_error("%s: null argument", who);
+        return GNNPE_ERR_ARG;
+    }
+    if (n_rows == 0) {
+        gnnpe::set_error("%s: a table without rows", who);
+        return GNNPE_ERR_ARG;
+    }
+    const uint64_t entries = offsets[n];
+    uint64_t found = 0, low = ~0ull;
+    for (uint32_t x = 0; x < n; x++)
+        for (uint64_t j = offsets[x]; j < offsets[x + 1]; j++) {
+            const uint32_t y = nbrs[j];
+            if (y >= n) {
+                gnnpe::set_error("%s: neighbour %u of vertex %u is not a vertex (n = %u)", who, y, x, n);
+                return GNNPE_ERR_ARG;
+            }
+            if (x >= y) continue;
+            const uint32_t *lo = nbrs + offsets[y], *hi = nbrs + offsets[y + 1], *at = std::lower_bound(lo, hi, x);
+            if (at == hi || *at != x) {
+                gnnpe::set_error("%s: the graph has (%u -> %u) without (%u -> %u)", who, x, y, y, x);
+                return GNNPE_ERR_ARG;
+            }
+            const uint64_t r = (uint64_t)(at - nbrs);
+            uint64_t sup = 0;
+            for (uint32_t k = 0; k < n_rows; k++) sup += table[(uint64_t)k * entries + j] + table[(uint64_t)k * entries + r];
+            if (sup < threshold) {
+                if (found < cap) pairs[2 * found] = x, pairs[2 * found + 1] = y;
+                found++;
+            } else
+                low = std::min(low, sup);
+        }
+    *n_selected = found;
+    *min_kept = low;
+    return GNNPE_OK;
+}
+
 }  // extern "C"

@@ -477,6 +477,7 @@ int run_standing(const Options &o)
     std::vector<std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> batches(o.standing_batches.size());
     for (size_t i = 0; i < batches.size(); i++) {  // before a GPU is touched
         const char kind = o.standing_batches[i].first;
+        if (kind == 'p' || kind == 't') continue;  // --peel T, --truss-levels FILE: no batch file to read
         (kind == 'e' ? read_edge_batch : kind == 'l' ? read_label_list : read_vertex_batch)(o.standing_batches[i].second, &batches[i].first, &batches[i].second);
     }
     if (gnnpe_device_count() <= 0) die("no HIP device: this tool has no CPU fallback");
@@ -498,7 +499,9 @@ int run_standing(const Options &o)
     // --standing-vertex-counts / --standing-edge-counts: the handle keeps the tables; only the number of changed cells is asked for
     const uint32_t keep = (o.standing_vertex_counts_file.empty() ? 0u : GNNPE_STANDING_VERTEX_COUNTS) |
                           (o.standing_edge_counts_file.empty() ? 0u : GNNPE_STANDING_EDGE_COUNTS);
-    if (keep) check(ONLINE(gnnpe_standing_keep_counts)(sq, keep, 0, nullptr), "standing_keep_counts");
+    // --peel / --truss-levels select on the kept E; the `changes:` lines and the table files stay those of the two flags above
+    if (keep || o.standing_peels)
+        check(ONLINE(gnnpe_standing_keep_counts)(sq, keep | (o.standing_peels ? GNNPE_STANDING_EDGE_COUNTS : 0u), 0, nullptr), "standing_keep_counts");
     const auto apply = ONLINE(gnnpe_standing_apply_edges);
     const auto relabel = ONLINE(gnnpe_standing_set_labels);
     const auto apply_vertices = ONLINE(gnnpe_standing_apply_vertices);
@@ -508,6 +511,37 @@ int run_standing(const Options &o)
         const std::vector<uint32_t> &a = batches[i].first, &b = batches[i].second;
         const char kind = o.standing_batches[i].first;
         const std::string &file = o.standing_batches[i].second;
+        if (kind == 'p' || kind == 't') {  // a peel by edge support, or the truss level of every edge (the graph is restored)
+            uint64_t held_rows = 0, entries = 0, res[4], out[6];
+            uint32_t hubs = 0;
+            check(gnnpe_rows_held(ctx, &held_rows, &entries, &hubs), "rows_held");
+            const uint64_t cap = entries / 2;
+            std::vector<uint32_t> pairs(2 * cap + 2), rounds(cap + 1);
+            std::vector<uint64_t> levels(cap + 1);
+            std::string out_file = kind == 't' ? file : "";
+            for (const auto &po : o.standing_peel_outs)
+                if (po.first == i) out_file = po.second;
+            if (kind == 'p')
+                check(ONLINE(gnnpe_standing_peel)(sq, strtoull(file.c_str(), nullptr, 10), 0, pairs.data(), rounds.data(), cap, res, &ms), ("--peel " + file).c_str());
+            else
+                check(ONLINE(gnnpe_standing_truss_levels)(sq, 1, pairs.data(), levels.data(), cap, res, &ms), ("--truss-levels " + file).c_str());
+            check(result(sq, out), "standing_result");
+            if (kind == 'p')
+                printf("peel: %llu %llu %llu %llu %llu %.3f\n", (unsigned long long)res[0], (unsigned long long)res[1], (unsigned long long)res[2],
+                       (unsigned long long)res[3], (unsigned long long)out[0], ms);
+            else
+                printf("truss: %llu %llu %llu %llu %.3f\n", (unsigned long long)res[0], (unsigned long long)res[1], (unsigned long long)res[2],
+                       (unsigned long long)res[3], ms);
+            if (!out_file.empty()) {
+                FILE *f = fopen(out_file.c_str(), "w");
+                if (!f) die("cannot write " + out_file);
+                const uint64_t k = kind == 'p' ? res[1] : res[0];
+                for (uint64_t e = 0; e < k; e++)
+                    fprintf(f, "%u %u %llu\n", pairs[2 * e], pairs[2 * e + 1], kind == 'p' ? (unsigned long long)rounds[e] : (unsigned long long)levels[e]);
+                fclose(f);
+            }
+            continue;
+        }
         if (kind == 'e') check(apply(ctx, a.data(), a.size() / 2, b.data(), b.size() / 2, &ms), ("--apply-edges " + file).c_str());
         else if (kind == 'l') check(relabel(ctx, a.data(), b.data(), a.size(), &ms), ("--set-labels " + file).c_str());
         else check(apply_vertices(ctx, a.data(), a.size(), b.data(), b.size(), &g.n, &ms), ("--apply-vertices " + file).c_str());
@@ -938,10 +972,13 @@ int main(int argc, char **argv)
             "made from the graph as it was");
     if (o.standing) {
         if (!(o.mode == "online" && (o.exact || o.path_length == 3)) || o.standing_batches.empty())
-            die("--standing applies to exact -m online (--exact or -l 3) with one or more --apply-edges, --set-labels or --apply-vertices FILE");
+            die("--standing applies to exact -m online (--exact or -l 3) with one or more --apply-edges, --set-labels, --apply-vertices FILE, "
+                "--peel T or --truss-levels FILE");
         if (o.incremental) die("--standing keeps its own support table: --incremental does not go with it");
     } else if (!o.standing_vertex_counts_file.empty() || !o.standing_edge_counts_file.empty())
         die("--standing-vertex-counts and --standing-edge-counts need --standing");
+    else if (o.standing_peels)
+        die("--peel and --truss-levels need --standing");
     if (o.incremental && o.apply_vertices_file.empty() && o.apply_edges_file.empty() && o.set_labels_file.empty())
         die("--incremental applies with --apply-vertices, --apply-edges or --set-labels: it carries the exact filter's support table "
             "across their batches");

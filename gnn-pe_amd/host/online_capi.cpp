@@ -1,5 +1,6 @@
 // online_capi.cpp -- C-ABI of the host refinements (include/gnnpe_online.h).  Compiled into libgnnpe_online.so, which links
 // against libgnnpe_hip.so for the loader and the error text.  Out of SURVEY section 8's scope (frozen).
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -281,6 +282,89 @@ int gnnpe_host_query_nonedges(const char *query_graph_path, uint32_t *pairs, uin
         pairs[2 * k] = qn[k].first;
         pairs[2 * k + 1] = qn[k].second;
     }
+    return 0;
+}
+
+// The host form of gnnpe_standing_truss_levels, and the library's own slow statement of the definition: every round counts the
+// table E of the graph as it is from scratch (gnnpe_host_refine_sets_edge_counts), selects with gnnpe_host_csr_edges_below and
+// rebuilds the CSR without the selected edges.
+int gnnpe_host_truss_levels(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels, const char *query_graph_path,
+                            const uint32_t *candidate_bitmap, uint32_t mode, uint32_t *edges, uint64_t *levels, uint64_t cap, uint64_t out[4])
+{
+    const char *who = "gnnpe_host_truss_levels";
+    if (!offsets || (!nbrs && offsets[n]) || (!labels && n) || !query_graph_path || !candidate_bitmap || !out || ((!edges || !levels) && cap)) {
+        gnnpe::set_error("%s: null argument", who);
+        return GNNPE_ERR_ARG;
+    }
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (mode & ~(GNNPE_MATCH_DISTINCT | GNNPE_MATCH_INDUCED)) {
+        gnnpe::set_error("%s: unknown mode bits 0x%x", who, mode);
+        return GNNPE_ERR_ARG;
+    }
+    if (mode & GNNPE_MATCH_INDUCED) {
+        gnnpe::set_error("%s: induced matching: a deletion can create matches, so the peel has no unique fixpoint", who);
+        return GNNPE_ERR_UNSUPPORTED;
+    }
+    gnnpe_host::StaticGraph q;
+    if (int rc = load_query(query_graph_path, &q)) return rc;
+    const uint32_t nqe = (uint32_t)gnnpe_host::query_edges(q).size();
+    if (nqe == 0) {
+        gnnpe::set_error("%s: a query without an edge has no per-edge table", who);
+        return GNNPE_ERR_ARG;
+    }
+    std::vector<uint32_t> off(offsets, offsets + n + 1), nb(nbrs, nbrs + offsets[n]), sel, off2, nb2;
+    std::vector<uint64_t> table;
+    uint64_t t = 0, n_out = 0;
+    bool have_t = false, counted = false;
+    while (!nb.empty()) {
+        const uint64_t entries = nb.size();
+        if (!counted) {
+            table.assign((size_t)nqe * entries, 0);
+            uint64_t answers = 0;
+            int complete = 0;
+            if (int rc = gnnpe_host_refine_sets_edge_counts(n, off.data(), nb.data(), labels, query_graph_path, candidate_bitmap, ~0ull, mode, &answers,
+                                                            &complete, table.data()))
+                return rc;
+            counted = true;
+        }
+        uint64_t n_sel = 0, low = 0;
+        sel.resize(entries);  // two words per undirected edge
+        if (int rc = gnnpe_host_csr_edges_below(n, off.data(), nb.data(), table.data(), nqe, have_t ? t + 1 : 0, sel.data(), entries / 2, &n_sel, &low))
+            return rc;
+        if (n_sel == 0) {  // the level is peeled (or not known yet): the next one is the smallest support left
+            if (low == ~0ull) {
+                gnnpe::set_error("%s: a support of 2^64 - 1 has no threshold above it", who);
+                return GNNPE_ERR_RANGE;
+            }
+            t = low;
+            have_t = true;
+            out[1]++;
+            continue;
+        }
+        for (uint64_t i = 0; i < n_sel; i++, n_out++)
+            if (n_out < cap) edges[2 * n_out] = sel[2 * i], edges[2 * n_out + 1] = sel[2 * i + 1], levels[n_out] = t;
+        out[3]++;
+        // the CSR without the selected edges: `sel` is ascending in (x, y)
+        std::vector<uint64_t> gone;
+        gone.reserve(2 * n_sel);
+        for (uint64_t i = 0; i < n_sel; i++) {
+            gone.push_back(((uint64_t)sel[2 * i] << 32) | sel[2 * i + 1]);
+            gone.push_back(((uint64_t)sel[2 * i + 1] << 32) | sel[2 * i]);
+        }
+        std::sort(gone.begin(), gone.end());
+        off2.assign((size_t)n + 1, 0);
+        nb2.clear();
+        for (uint32_t x = 0; x < n; x++) {
+            for (uint32_t j = off[x]; j < off[x + 1]; j++)
+                if (!std::binary_search(gone.begin(), gone.end(), ((uint64_t)x << 32) | nb[j])) nb2.push_back(nb[j]);
+            off2[x + 1] = (uint32_t)nb2.size();
+        }
+        off.swap(off2);
+        nb.swap(nb2);
+        counted = false;
+    }
+    out[0] = n_out;
+    out[2] = have_t ? t : 0;
     return 0;
 }
 

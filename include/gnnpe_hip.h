@@ -252,6 +252,33 @@ int gnnpe_csr_carry_entries(gnnpe_ctx *ctx, uint32_t n_rows, uint32_t elem_bytes
 int gnnpe_table_fold(gnnpe_ctx *ctx, void *dev_table, void *dev_delta, uint64_t cells, void *dev_change_cells, void *dev_change_deltas,
                      uint64_t cap, uint64_t *n_changes, double *device_ms);
 
+/* ---- the edges whose support in a per-entry table lies below a threshold --------------------------------------------------------------
+ * (Headed by name: GNNPE_ABI_VERSION stays 20, this section only adds symbols.)
+ * dev_table is n_rows x entries uint64, row-major, over the adjacency entries of the whole simple graph resident now (the table E of
+ * ABI 14, or what a standing query keeps).  The undirected edge {x, y} has the entry j = (x -> y) and its reverse entry r = (y -> x);
+ *     sup(x, y) = sum over k < n_rows of (table[k][j] + table[k][r]),  a uint64 sum mod 2^64 like every table sum here.
+ * gnnpe_csr_edges_below selects the edges with sup < threshold, each once, as (x, y) with x < y, in ascending order of the entry
+ *   x -> y, which is ascending (x, y).  The first min(cap, *n_selected) pairs go to dev_pairs (cap x 2 uint32 on the context's
+ *   device); nothing is written at or behind cap.  *n_selected is the true number of selected edges whatever cap is.  *min_kept is
+ *   the smallest support among the edges NOT selected, 2^64 - 1 if there is none: the next threshold at which something happens,
+ *   which lets a decomposition jump from level to level.  threshold == 0 selects nothing and still reports *min_kept.  The table
+ *   is only read.  A graph without edges succeeds with 0 and 2^64 - 1.  The work runs on the context's stream with one host wait,
+ *   for the two result words.  dev_pairs may be NULL iff cap == 0; device_ms may be NULL.
+ *   GNNPE_ERR_ARG, with nothing launched and nothing written: a null argument, a table not aligned to 8 bytes (dev_pairs: to 4), dev_pairs
+ *   overlapping the table, cap > 0 without dev_pairs, n_rows == 0, a slab context (anything but gnnpe_load_csr's whole graph) or
+ *   the multigraph state.
+ *   Device code (csrc/gnnpe_edges_below.hip): the two passes over fixed tiles of 2 048 entries of gnnpe_table_fold, no atomics.  One
+ *   lane per entry; the lane of the direction x < y reads the 2 x n_rows cells, the cells at r as gathers of 8 bytes through the
+ *   context's reverse positions.  A tile without a selected edge costs the second pass one word.
+ * gnnpe_host_csr_edges_below: the host form and the yardstick (host/host_capi.cpp): a plain loop with a binary search for the reverse
+ *   entry, on any compact simple CSR.  It shares no code with the device form.  GNNPE_ERR_ARG: a null argument, n_rows == 0, a
+ *   neighbour >= n, an entry without its reverse.
+ * The consumer is gnnpe_standing_peel of include/gnnpe_online.h.  Out of scope: slab contexts, multigraph rows, a vertex form. */
+int gnnpe_host_csr_edges_below(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint64_t *table, uint32_t n_rows,
+                               uint64_t threshold, uint32_t *pairs, uint64_t cap, uint64_t *n_selected, uint64_t *min_kept);
+int gnnpe_csr_edges_below(gnnpe_ctx *ctx, const void *dev_table, uint32_t n_rows, uint64_t threshold, void *dev_pairs, uint64_t cap,
+                          uint64_t *n_selected, uint64_t *min_kept, double *device_ms);
+
 /* ---- vertex relabel on the resident graph -----------------------------------------------------------------------------------------
  * (Headed by name: GNNPE_ABI_VERSION stays 20, this section and gnnpe_refine_sets_delta_vertices of include/gnnpe_online.h only add
  * symbols.)

@@ -831,7 +831,58 @@ int gnnpe_refine_pages_open_delta_vertices(gnnpe_ctx *ctx, const char *query_gra
  *   (GNNPE_ERR_UNSUPPORTED: its bitmap was made for the old n).  A refusal inside the apply before its swap puts S back and zeroes
  *   D.  The empty batch is a no-op.  *n_after = n'.
  *
- * Not yet: vertex batches with an open_sets handle on the context, an automatic switch to gnnpe_standing_refresh where a batch
+ * PEELING THE GRAPH BY EDGE SUPPORT: the (Q, t)-truss and the truss level of every edge (GNNPE_ABI_VERSION stays 20: symbols are
+ * added, and a process that never calls the two entries below runs, launch for launch, what it ran before).  The consumer the table
+ * E was introduced for, written against the library without taking E off the device: gnnpe_csr_edges_below of include/gnnpe_hip.h
+ * selects on the resident table, and only the selected pairs, 8 bytes per edge, cross to the host.
+ * Definitions.  The handle keeps E with nqe rows.  The undirected edge {x, y} has the entry j = (x -> y) and its reverse r = (y -> x).
+ *     SUPPORT  sup(x, y) = sum over k < nqe of (E[k][j] + E[k][r]), the uint64 sum mod 2^64 like every table sum here: the number of
+ *              (match, query edge) incidences on the data edge.  For a triangle handle in DISTINCT mode it is the number of
+ *              triangles on the edge, in mode 0 six times that.  The caller chooses the threshold in these units.
+ *     (Q, t)-TRUSS of G: the largest subgraph on the same vertices in which every edge has sup >= t, matches counted inside the
+ *              subgraph.
+ *     LEVEL    of an edge: the largest t for which it belongs to the (Q, t)-truss.
+ * WHY THE FIXPOINT IS UNIQUE.  For a handle that is not INDUCED a match of a subgraph H of G is a match of G: it rests on edges and
+ *   labels only.  So deleting edges only destroys matches, whichever sound candidate sets the steps search with (the argument of
+ *   "WHY THE TABLES STAY EXACT" above: the tables are those of the graph itself), and sup is monotone under deletion: sup_H <= sup_G
+ *   on the edges of H.  If H1 and H2 have all supports >= t, so has their union, since each of its edges lies in an Hi and
+ *   sup of the union >= sup_Hi: there is a largest such subgraph.  An edge with sup < t in some graph between G and the truss has
+ *   sup < t in every smaller graph and is not in the truss, so every peeling order removes exactly the edges outside it and ends at
+ *   the same graph.  INDUCED handles are refused (GNNPE_ERR_UNSUPPORTED): a deletion can create induced matches, support is not
+ *   monotone and the fixpoint is not unique.
+ * gnnpe_standing_peel(sq, min_support, max_rounds, host_removed, host_round, cap, out): each round
+ *       gnnpe_csr_edges_below(E of sq, nqe, min_support) into a context-owned, grow-only pair buffer;
+ *       nothing selected: stop, converged;
+ *       the selected pairs cross to the host and are the delete_edges of ONE gnnpe_standing_apply_edges on the context.
+ *   All edges below the threshold go at once, so the rounds are determined.  Going through gnnpe_standing_apply_edges means that every
+ *   handle open on the context moves forward exactly as for a caller's batch (an induced handle of another query is fine there: the
+ *   batch only deletes), and every kept table and every handle's S, C and count stay exact.  max_rounds == 0 means no limit;
+ *   otherwise the loop ends after max_rounds rounds that deleted something.  out = {rounds that deleted something, edges removed,
+ *   undirected edges left, converged}: converged is 1 only if a select found nothing, so a peel cut by max_rounds reports 0 and a
+ *   second call goes on where it stopped.  host_removed (cap x 2 uint32) and host_round (cap uint32, may be NULL; rounds count from
+ *   1) get the first cap removed edges in removal order.  The handle's result, rows and count_changes describe the last round, as for
+ *   any batch; a peel that removes nothing (min_support == 0 for instance) touches neither graph nor generation nor those.
+ *   Refused before anything changes: a stale handle (this one or another on the context), a handle that does not keep E
+ *   (GNNPE_ERR_ARG, naming gnnpe_standing_keep_counts), a query without an edge (no E), an INDUCED handle (GNNPE_ERR_UNSUPPORTED).
+ *   A failure inside round i leaves the graph and all handles in the state after round i - 1, because each round is one
+ *   transactional batch; out and host_removed say how far the loop came.
+ * gnnpe_standing_truss_levels(sq, restore, host_edges, host_levels, cap, out): t = min_kept of a select with threshold 0; peel with
+ *   min_support = t + 1, everything removed gets level t; t = the new min_kept, which is larger; until no edge is left.  The jump
+ *   makes the number of peels the number of distinct levels, not the largest support.  out = {edges, distinct levels, largest
+ *   level, rounds in all}; the first cap edges come out in removal order, which is by level, with their levels.  Refusals: those of
+ *   the peel.  restore != 0: one closing gnnpe_standing_apply_edges inserts every removed edge again; the graph is then the compact
+ *   CSR of the original and count, sets and tables are those of before the call (the generation has moved on).  Its cost is one delta
+ *   search over ALL edges, which the table of DESIGN.md section 3.7 prices at 1.3 to 4.8 full counts.  restore == 0 leaves the
+ *   context with the empty graph on n vertices.  A failure on the way leaves the graph peeled as far as the loop came, nothing is
+ *   restored, and out and host_edges say what was removed.  (A support of 2^64 - 1 has no threshold above it: GNNPE_ERR_RANGE.)
+ * gnnpe_host_truss_levels: the host form and the library's own slow statement of the definition (host/online_capi.cpp): it peels
+ *   the same way on a host CSR and counts E from scratch with gnnpe_host_refine_sets_edge_counts every round.  Modes as above.
+ * Out of scope: a vertex form (a (Q, t)-core: removing vertices renumbers ids), a device-list apply (the list has to reach the host
+ *   anyway to be reported), induced handles, slab contexts and multigraph rows, and a second-level split of hub items inside the
+ *   delta searches: the peel inherits the known cost of a batch that deletes hub edges under large queries (DESIGN.md section 3.7,
+ *   "Known and accepted").  csrc/gnnpe_standing.hip, profiles/online_standing_peel.txt.
+ *
+ * Not yet: a (Q, t)-core by vertex removal, a peel whose selected list stays on the device, vertex batches with an open_sets handle on the context, an automatic switch to gnnpe_standing_refresh where a batch
  * touches so much that recomputing is cheaper (profiles/online_standing_updates.txt has where that is), a fused carry-and-fold for E (T and D of E are carried as two gathers per apply), paged change lists (what is behind changes_cap is counted, not held), a device plan handle for
  * the support calls (their plan is uploaded per call), slab contexts, multigraph rows. */
 #define GNNPE_STANDING_VERTEX_COUNTS 1u
@@ -858,6 +909,13 @@ int gnnpe_standing_counts(gnnpe_standing *sq, uint32_t which, uint64_t *host_cou
                           uint64_t *n_cols);
 int gnnpe_standing_count_changes(gnnpe_standing *sq, uint32_t which, uint64_t *host_cells, int64_t *host_deltas, uint64_t cap,
                                  uint64_t *n_changes);
+int gnnpe_standing_peel(gnnpe_standing *sq, uint64_t min_support, uint32_t max_rounds, uint32_t *host_removed, uint32_t *host_round,
+                        uint64_t cap, uint64_t out[4], double *device_ms);
+int gnnpe_standing_truss_levels(gnnpe_standing *sq, int restore, uint32_t *host_edges, uint64_t *host_levels, uint64_t cap,
+                                uint64_t out[4], double *device_ms);
+int gnnpe_host_truss_levels(uint32_t n, const uint32_t *offsets, const uint32_t *nbrs, const uint32_t *labels,
+                            const char *query_graph_path, const uint32_t *candidate_bitmap, uint32_t mode, uint32_t *edges,
+                            uint64_t *levels, uint64_t cap, uint64_t out[4]);
 int gnnpe_standing_refresh(gnnpe_standing *sq, uint64_t *count, double *device_ms);
 int gnnpe_standing_close(gnnpe_standing *sq);
 
